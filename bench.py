@@ -4,10 +4,16 @@ materialised) of the fusion + DEER path at B = 4096 per GPU, bf16 MFMA / fp32 ac
 (BASELINE.json configs[2]; with --gpus N the same per-GPU batch, data parallel: configs[3]).
 
 Contract: W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both
-sides, MAX over ranks, rank 0 prints ONE JSON line.  `roofline` is the trimodal in_proj GEMM
-(M = 2B, K = 512, N = 1536), timed in situ with HIP events recorded around its launch on the launch
-stream.  `cpu_baseline` is the CPU oracle's train step (a port, validated against the imported
-reference by tests/test_oracle_golden.py) on the host cores, N = 1 only.
+sides, MAX over ranks, rank 0 prints ONE JSON line.  A plain run does only that (plus the set-up the
+headline depends on: the launch-plan choice); `--dump-outputs DIR` then writes what the last timed step
+returned as DIR/<name>.npy (float32), the inputs being the same from run to run for the same arguments.
+
+`--full` adds the figures that take runs of their own: the spread of the step time, the per-launch
+trace, the step with the optimiser, and `roofline`, the trimodal in_proj GEMM (M = 2B, K = 512,
+N = 1536) timed in situ with HIP events recorded around its launch on the launch stream; the
+committed profiles of these sources (`recorded_profile`); and `cpu_baseline`, the CPU oracle's train
+step (a port, validated against the imported reference by tests/test_oracle_golden.py) on the host
+cores, N = 1 only.
 """
 import argparse
 import json
@@ -26,6 +32,31 @@ import torch.distributed as dist  # noqa: E402
 
 BF16_MFMA_PEAK = 2.5e15   # dense bf16 FLOP/s, MI355X_MICROARCH.md "Peak BF16/FP16 MFMA"
 F32_MFMA_PEAK = 157.3e12
+DUMP_CAP_BYTES = 64 << 20
+
+
+def tensors_of(d):
+    """The tensors of a step's output dict; keys starting with "_" are internal."""
+    return {k: v for k, v in d.items() if torch.is_tensor(v) and not k.startswith("_")}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 stays float64).  Past DUMP_CAP_BYTES in all, every array
+    larger than its share is replaced by the same seeded sample of its elements (sorted flat indices) in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    if sum(a.nbytes for a in host.values()) > DUMP_CAP_BYTES:
+        share = DUMP_CAP_BYTES // len(host)
+        for name, a in host.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                host[name] = a.reshape(-1)[idx]
+    for name, a in host.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def kernel_sources_sha():
@@ -207,7 +238,14 @@ def bench_stackb(args, dev, world, rank):
     model = stackb.CompleteDEERModel(compute_dtype=args.dtype).to(dev).eval()
     data = synth.make_batch(B, seed=42, row_offset=rank * B)
     xs = [torch.from_numpy(data[k]).to(dev) for k in ("audio", "video", "text")]
-    step = (lambda: model(*xs)) if args.eager else model.capture(*xs).graph.replay
+    if args.eager:
+        step = lambda: model(*xs)  # noqa: E731
+    else:
+        captured = model.capture(*xs)           # replays write the same static output tensors every time
+
+        def step():
+            captured.graph.replay()
+            return captured.outputs
     for _ in range(W):
         step()
     if world > 1:
@@ -215,11 +253,13 @@ def bench_stackb(args, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(K):
-        step()
+        outputs = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tensors_of(outputs))
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt)
@@ -239,7 +279,7 @@ def bench_stackb(args, dev, world, rank):
            "roofline": {"bound": "mfma", "achieved": round(flops * K / dt / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
                         "frac": round(flops * K / dt / peak, 4), "traffic": None,
                         "note": "whole forward (25 launches), algorithmic GEMM flops / wall time; the layers are 4-14 us launches bound by fixed launch cost, not MFMA"}}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = stackb_cpu_baseline(B)
     print(json.dumps(out))
 
@@ -256,7 +296,7 @@ def bench_stackb_train(args, dev, world, rank):
     from mmdeer.optim import FlatAdamW
     B, K, W = args.batch, args.steps, args.warmup
     model = stackb.CompleteDEERModel(compute_dtype=args.dtype).to(dev).train()
-    twin = copy.deepcopy(model) if args.dtype == "bf16" else None
+    twin = copy.deepcopy(model) if args.full and args.dtype == "bf16" else None
     data = synth.make_batch(B, seed=42, row_offset=rank * B)
     a, v, t, y = (torch.from_numpy(data[k]).to(dev) for k in ("audio", "video", "text", "targets"))
     if args.dtype == "bf16":
@@ -295,11 +335,16 @@ def bench_stackb_train(args, dev, world, rank):
         dt = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-        return float(dt), float(ld["total_loss"]), rep
+        return float(dt), ld, flat_g
 
-    dt, loss, rep = timed(model, False)
-    dt_opt, _, _ = timed(model, True)
+    dt, ld, flat_g = timed(model, False)
+    loss = float(ld["total_loss"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**tensors_of(ld), "planes": ld["_planes"], "grad": flat_g})
     extra = {}
+    if args.full:
+        dt_opt, _, _ = timed(model, True)
+        extra["train_step_with_optimizer_ms"] = round(dt_opt / K * 1e3, 4)
     if twin is not None:
         twin.train_plan = "ops"
         dt_ops, _, _ = timed(twin, False)
@@ -321,7 +366,7 @@ def bench_stackb_train(args, dev, world, rank):
                       "launch": "hip-graph replay", "parallelism": f"replicas x{world}",
                       "plan": "layer chains (mmdeer_chain)" if st.get("frag") is not None else "launch by launch"},
            "grad_exchange": "none" if comm is None else f"{comm.algo} of the flat gradient buffer ({comm.payload} payload), host-enqueued behind the graph replay",
-           "train_step_with_optimizer_ms": round(dt_opt / K * 1e3, 4), "final_loss": round(loss, 6),
+           "final_loss": round(loss, 6),
            "roofline": {"bound": "mfma", "achieved": round(flops * K / dt / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
                         "frac": round(flops * K / dt / peak, 4), "traffic": None,
                         "note": "whole step, algorithmic GEMM flops (3 x forward) / wall time; a step of small layers: bound by the layer ends of its "
@@ -409,7 +454,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4096, help="samples per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: step-time spread, launch trace, roofline kernel, optimiser "
+                         "step, committed profiles, CPU baseline (each in runs of its own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--grad-comm", default="bf16", choices=["bf16", "fp32"],
                     help="payload of the data-parallel gradient all-reduce (N > 1): bf16 halves the bytes over xGMI")
     ap.add_argument("--workload", default="train_step", choices=["train_step", "stackb_infer", "stackb_train"],
@@ -660,6 +710,63 @@ def main():
         elapsed = float(tt.item())
     loss = float(ld["total_loss"])
     assert loss == loss, "loss is NaN"
+    if args.dump_outputs and rank == 0:
+        # the caller of the step receives the loss dict, the NIG head outputs and the gradients (views of the flat buffer)
+        dump_outputs(args.dump_outputs, {**tensors_of(ld), "nig": ld["_outputs"]["_nig"], "grad": model.flat_grad()})
+    if args.full:
+        full = full_figures(args, model, one_step, prof, sc, (a, v, t, y), dev, elapsed, own_elapsed)
+    if rank == 0:
+        out = {
+            "metric": "samples/sec fwd+bwd at B=4096 (84/256/768-dim)",
+            "value": round(world * B * K / elapsed, 1),
+            "unit": "samples/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": round(elapsed / K * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": f"configs[2]: fusion+DEER forward + MultiTaskDEERLoss + backward (dropout 0.3, gradients "
+                                   f"materialised in the flat buffer), B={B}/GPU, (B,84)+(B,256)+(B,768) {args.dtype} feature "
+                                   f"blocks, random-init weights; optimiser step excluded as the metric defines "
+                                   f"(it maintains the packed weight copies and is timed separately)", "global_batch": world * B,
+                       "parallelism": (f"dp{world} (one process per GPU, gradient all-reduce over RCCL, {args.grad_comm} payload, "
+                                        f"{comm_mode})" if world > 1 else "single")},
+            "inputs": "one resident batch replayed: the same (B,84)+(B,256)+(B,768) blocks every step (9 MB at B=4096 bf16, Infinity-Cache "
+                      "resident), fresh dropout masks per step; host-to-device copies are outside the metric (DESIGN.md section 7)",
+            "launch": "eager" if replay is None else "hip-graph replay",
+            # which launch plan ran: chosen by timing the plans on this GPU (untimed set-up), or the library's current options
+            "launch_plan": launch_plan if launch_plan is not None else
+                           {"plan": "as set", "options": {k: _lib.get_option(k) for k in ("chain", "chain_bwd", "chain_nig")},
+                            "why": "--no-autotune / --eager / MMDEER_CHAIN* given"},
+            "grad_exchange": comm_mode + (", exact-global loss statistics" if exact else ""),
+            "final_loss": round(loss, 6),
+        }
+        if dp is not None:
+            if per_rank_ms is not None:
+                dp["per_rank_ms_per_step"] = per_rank_ms
+            out["data_parallel"] = dp
+        if args.full:
+            out.update(full)
+            rp = recorded_profile(B, args.dtype)
+            if rp is not None:
+                out["recorded_profile"] = rp     # read from committed files, NOT measured by this run
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(B)
+        print(json.dumps(out), flush=True)
+    if world > 1 or force_comm:
+        dist.destroy_process_group()
+
+
+def full_figures(args, model, one_step, prof, sc, batch, dev, elapsed, own_elapsed):
+    """--full: the figures beside the metric that take runs of their own, after the timed steps -- the spread of the step time,
+    every launch of an eager step, the roofline kernel in situ, and the K steps again with the optimiser step inside."""
+    from mmdeer import _lib
+    a, v, t, y = batch
+    B, K = args.batch, args.steps
 
     # ---- spread of the step time: every replay between its own pair of events (a separate pass: event records inside the
     #      timed region would perturb the metric).  min / median / max over K steps.
@@ -760,76 +867,36 @@ def main():
     torch.cuda.synchronize()
     full_elapsed = time.perf_counter() - t1
 
-    if rank == 0:
-        avg_ms = sum(gemm_ms) / len(gemm_ms)
-        flops = 2.0 * (2 * B) * 512 * 1536                      # algorithmic: SURVEY 8d, 3.146 MFLOP/sample forward
-        step_flops = 3 * 2.0 * 3950336 * B                       # 7.90 MFLOP/sample forward, x3 for the train step
-        peak = BF16_MFMA_PEAK if args.dtype == "bf16" else F32_MFMA_PEAK
-        achieved = flops / (avg_ms * 1e-3)
-        traffic, traffic_src = measured_traffic(args.dtype, B)
-        out = {
-            "metric": "samples/sec fwd+bwd at B=4096 (84/256/768-dim)",
-            "value": round(world * B * K / elapsed, 1),
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": round(elapsed / K * 1e3, 4),
-            "ms_per_step_min": round(step_ms[0], 4), "ms_per_step_median": round(step_ms[len(step_ms) // 2], 4),
-            "ms_per_step_max": round(step_ms[-1], 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": f"configs[2]: fusion+DEER forward + MultiTaskDEERLoss + backward (dropout 0.3, gradients "
-                                   f"materialised in the flat buffer), B={B}/GPU, (B,84)+(B,256)+(B,768) {args.dtype} feature "
-                                   f"blocks, random-init weights; optimiser step excluded as the metric defines "
-                                   f"(it maintains the packed weight copies and is timed separately)", "global_batch": world * B,
-                       "parallelism": (f"dp{world} (one process per GPU, gradient all-reduce over RCCL, {args.grad_comm} payload, "
-                                        f"{comm_mode})" if world > 1 else "single")},
-            "inputs": "one resident batch replayed: the same (B,84)+(B,256)+(B,768) blocks every step (9 MB at B=4096 bf16, Infinity-Cache "
-                      "resident), fresh dropout masks per step; host-to-device copies are outside the metric (DESIGN.md section 7)",
-            "launch": "eager" if replay is None else "hip-graph replay",
-            # which launch plan ran: chosen by timing the plans on this GPU (untimed set-up), or the library's current options
-            "launch_plan": launch_plan if launch_plan is not None else
-                           {"plan": "as set", "options": {k: _lib.get_option(k) for k in ("chain", "chain_bwd", "chain_nig")},
-                            "why": "--no-autotune / --eager / MMDEER_CHAIN* given"},
-            "grad_exchange": comm_mode + (", exact-global loss statistics" if exact else ""),
-            # per-launch durations of eager steps of this run (median over 18 steps, HIP events behind every launch: kernel + the gap
-            # to the next one; the replayed graph the metric times has no gaps)
-            "launch_us": launch_us,
-            "final_loss": round(loss, 6),
-            "train_step_with_optimizer_ms": round(full_elapsed / K * 1e3, 4),     # fwd + bwd + clip + AdamW + weight pack
-            "optimizer_ms": round((full_elapsed - own_elapsed) / K * 1e3, 4),
-            "roofline": {"bound": "mfma",
-                         "kernel": ("tri_fused_kernel<0> (trimodal in_proj M=2B K=512 N=1536 + 2-token attention fused: q|k|v stay on chip)" if fused
-                                    else ("gemm_nt256_kernel<192>" if args.dtype == "bf16" else "gemm_group_kernel") + " (trimodal in_proj, M=2B K=512 N=1536)"),
-                         "achieved": round(achieved / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4),
-                         # HBM-side bytes of one launch from separate rocprofv3 --pmc passes (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE,
-                         # tools/gpu_pmc_fused.sh -> profiles/pmc_traffic.json); null unless taken on exactly these kernel sources
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         # fused: X 8.39 + W 1.57 + obar 4.19 + probs 0.52 MB; unfused GEMM: A 8.39 + W 1.57 + C 25.17 MB
-                         "algorithmic_bytes": (2 * B * 512 * 2 + 1536 * 512 * 2 + B * 512 * 2 + B * 32 * 4) if fused
-                                              else (2 * B * 512 * 2 + 1536 * 512 * 2 + 2 * B * 1536 * 2),
-                         "avg_launch_us": round(avg_ms * 1e3, 2), "median_launch_us": round(gemm_ms[len(gemm_ms) // 2] * 1e3, 2),
-                         "min_launch_us": round(gemm_ms[0] * 1e3, 2), "timing": roof_how,
-                         # the whole step against the same peak: 97.1 GFLOP (algorithmic) / step time
-                         "step_frac": round(step_flops / (elapsed / K) / peak, 4)},
-        }
-        if dp is not None:
-            if per_rank_ms is not None:
-                dp["per_rank_ms_per_step"] = per_rank_ms
-            out["data_parallel"] = dp
-        rp = recorded_profile(B, args.dtype)
-        if rp is not None:
-            out["recorded_profile"] = rp     # read from committed files, NOT measured by this run
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(B)
-        print(json.dumps(out), flush=True)
-    if world > 1 or force_comm:
-        dist.destroy_process_group()
+    avg_ms = sum(gemm_ms) / len(gemm_ms)
+    flops = 2.0 * (2 * B) * 512 * 1536                      # algorithmic: SURVEY 8d, 3.146 MFLOP/sample forward
+    step_flops = 3 * 2.0 * 3950336 * B                       # 7.90 MFLOP/sample forward, x3 for the train step
+    peak = BF16_MFMA_PEAK if args.dtype == "bf16" else F32_MFMA_PEAK
+    achieved = flops / (avg_ms * 1e-3)
+    traffic, traffic_src = measured_traffic(args.dtype, B)
+    return {
+        "ms_per_step_min": round(step_ms[0], 4), "ms_per_step_median": round(step_ms[len(step_ms) // 2], 4),
+        "ms_per_step_max": round(step_ms[-1], 4),
+        # per-launch durations of eager steps of this run (median over 18 steps, HIP events behind every launch: kernel + the gap
+        # to the next one; the replayed graph the metric times has no gaps)
+        "launch_us": launch_us,
+        "train_step_with_optimizer_ms": round(full_elapsed / K * 1e3, 4),     # fwd + bwd + clip + AdamW + weight pack
+        "optimizer_ms": round((full_elapsed - own_elapsed) / K * 1e3, 4),
+        "roofline": {"bound": "mfma",
+                     "kernel": ("tri_fused_kernel<0> (trimodal in_proj M=2B K=512 N=1536 + 2-token attention fused: q|k|v stay on chip)" if fused
+                                else ("gemm_nt256_kernel<192>" if args.dtype == "bf16" else "gemm_group_kernel") + " (trimodal in_proj, M=2B K=512 N=1536)"),
+                     "achieved": round(achieved / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
+                     "frac": round(achieved / peak, 4),
+                     # HBM-side bytes of one launch from separate rocprofv3 --pmc passes (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE,
+                     # tools/gpu_pmc_fused.sh -> profiles/pmc_traffic.json); null unless taken on exactly these kernel sources
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     # fused: X 8.39 + W 1.57 + obar 4.19 + probs 0.52 MB; unfused GEMM: A 8.39 + W 1.57 + C 25.17 MB
+                     "algorithmic_bytes": (2 * B * 512 * 2 + 1536 * 512 * 2 + B * 512 * 2 + B * 32 * 4) if fused
+                                          else (2 * B * 512 * 2 + 1536 * 512 * 2 + 2 * B * 1536 * 2),
+                     "avg_launch_us": round(avg_ms * 1e3, 2), "median_launch_us": round(gemm_ms[len(gemm_ms) // 2] * 1e3, 2),
+                     "min_launch_us": round(gemm_ms[0] * 1e3, 2), "timing": roof_how,
+                     # the whole step against the same peak: 97.1 GFLOP (algorithmic) / step time
+                     "step_frac": round(step_flops / (elapsed / K) / peak, 4)},
+    }
 
 
 if __name__ == "__main__":

@@ -109,11 +109,11 @@ def test_trainer_resume_with_dropout_continues_the_mask_stream(tmp_path):
         assert torch.equal(p1, p2), n1
 
 
-def test_clip_matches_torch_clip_grad_norm():
+def test_clip_matches_torch_clip_grad_norm(tmp_path):
     model = MultimodalDEER(ModelConfig(dropout=0.0)).to("cuda:0").train()
     b = {k: torch.from_numpy(v).to("cuda:0") for k, v in synth.make_batch(16, seed=4).items()}
-    tr = DEERTrainer(model, TrainingConfig(gradient_clip=0.05, output_dir="/tmp/mmdeer_t/o", log_dir="/tmp/mmdeer_t/l",
-                                           checkpoint_dir="/tmp/mmdeer_t/c"), "cuda:0")
+    tr = DEERTrainer(model, TrainingConfig(gradient_clip=0.05, output_dir=str(tmp_path / "o"), log_dir=str(tmp_path / "l"),
+                                           checkpoint_dir=str(tmp_path / "c")), "cuda:0")
     model.train_step(b["audio"], b["video"], b["text"], b["targets"])
     ref = [p.grad.clone() for p in model.parameters() if p.grad is not None]
     total_ref = torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], 1e9)

@@ -223,12 +223,14 @@ def _stackb_params(golden_dir, dtype=torch.float32):
 
 
 def test_stackb_eval_forward(golden_dir):
-    """complete_project.CompleteDEERModel: every output of the reference's eval forward."""
+    """complete_project.CompleteDEERModel: every output of the reference's eval forward.  The oracle runs in
+    float64: in float32 its rounding follows the host's GEMM kernels, and on some hosts one element of fused_features
+    lands just outside the tolerance."""
     g = _load(golden_dir, "stackb_B9.npz")
-    P = _stackb_params(golden_dir)
+    P = _stackb_params(golden_dir, torch.float64)
     b = synth.make_batch(9, seed=78)
     with torch.no_grad():
-        o = O.stackb_forward(P, *(torch.from_numpy(b[k]) for k in ("audio", "video", "text")))
+        o = O.stackb_forward(P, *(torch.from_numpy(b[k]).double() for k in ("audio", "video", "text")))
     keys = [k[4:] for k in g if k.startswith("out.")]
     assert len(keys) == 27
     for k in keys:

@@ -27,7 +27,7 @@ if stats:
     shutil.copy(stats[0], os.path.join(dst, f"{tag}_bench_kernel_stats.csv"))
     line = json.load(open(os.path.join(src, "bench_b4096_bf16.json")))
     meta = {"csv": f"{tag}_bench_kernel_stats.csv", "src_sha": sha, "batch": 4096, "dtype": "bf16",
-            "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline",
+            "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline",
             "bench_line_of_the_same_box": {k: line[k] for k in ("value", "ms_per_step", "steps", "warmup")}}
     # bytes of the weight-gradient fold (slabs in + gradient out) from the PMC pass over the step, when it ran on these sources
     try:
