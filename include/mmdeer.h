@@ -259,20 +259,27 @@ int mmdeer_gemm(const mmdeer_gemm_args* a);
  * launches of up to 16 problems each + one deterministic fold of their split-K slabs per group -- the form in which
  * mmdeer_backward runs all its weight gradients in ONE launch, for operator sequences built outside the library (Stack B
  * training, mmdeer/stackb_train.py).  `splitk` / `slab` of the individual problems are ignored: the slices are carved out of
- * `slab` (slab_elems floats; mmdeer_gemm_batch_slab_elems gives the need) with the library's own split policy. */
+ * `slab` (slab_elems floats; mmdeer_gemm_batch_slab_elems gives the need) with the library's own split policy.
+ * Writes C[r][0, N) (row stride ldc) and bias_grad[0, M) of every problem and the first mmdeer_gemm_batch_slab_elems floats of
+ * `slab`, nothing else.  Refuses (-1, writing nothing) unless every problem has M, N multiples of 4, lda >= M, ldw >= N, ldc >= N
+ * (multiples of 4), 16-byte aligned A / W, and the slab (16-byte aligned) holds the need.  A problem with ldc != N or an unaligned
+ * C / bias_grad is not split (one workgroup per tile runs its whole reduction), so acceptance never depends on K. */
 long long mmdeer_gemm_batch_slab_elems(const mmdeer_gemm_args* a, int n);
 int mmdeer_gemm_batch(const mmdeer_gemm_args* a, int n, float* slab, long long slab_elems, void* stream);
 
 /* n folds in ONE launch: dst[i][j] = sum over p < nparts[i] of src[i][p * stride[i] + j], j < count[i] (count and stride
  * multiples of 4, 16-byte aligned pointers; fixed order: deterministic).  nparts = 1 is a copy.  Operator sequences collect
  * the LayerNorm gamma / beta partials of mmdeer_layernorm_bwd(dgamma = NULL) and their gradient slices here instead of
- * paying one small launch each (up to 48 segments per launch; more are split over several). */
+ * paying one small launch each (up to 48 segments per launch; more are split over several).  Writes dst[i][0, count[i]) only;
+ * refuses (-1, writing nothing) if any segment has nparts < 1, count or stride not a multiple of 4, or a pointer not 16-byte aligned. */
 int mmdeer_reduce_batch(int n, const float* const* src, float* const* dst, const int32_t* nparts, const int32_t* count,
                         const long long* stride, void* stream);
 
 /* n transposed compute-dtype copies in ONE launch: for matrix i (fp32, rows[i] x cols[i], row-major, dense) W^T[c][r] is
  * written to dst + dst_off[i] + c * ld_dst[i] + dst_col[i] + r (elements of the compute dtype; ld_dst 0 = rows[i]): dX = dY W
- * then runs as an NT GEMM on the LDS-DMA kernels.  Up to 32 matrices per launch (more are split). */
+ * then runs as an NT GEMM on the LDS-DMA kernels.  Up to 32 matrices per launch (more are split).  Writes those rows * cols elements
+ * only (bf16: round to nearest even, NaN stays NaN); refuses (-1, writing nothing) if any matrix has no source, rows or cols < 1, a
+ * negative dst_off / dst_col / ld_dst, or ld_dst != 0 with dst_col + rows > ld_dst. */
 int mmdeer_pack_transposed_batch(int n, const float* const* src, const int32_t* rows, const int32_t* cols, void* dst,
                                  const long long* dst_off, const int32_t* ld_dst, const int32_t* dst_col, int dst_f32, void* stream);
 
@@ -374,9 +381,11 @@ int mmdeer_adamw_step(const mmdeer_adamw_args* a);
 
 /* The same update (clip_grad_norm_ + torch.optim.AdamW, training.py:121-150, 219-224) for ANY model whose parameters,
  * gradients and moments live in flat fp32 buffers with common offsets (Stack B: mmdeer/stackb.py): up to 56 learning-rate
- * segments [seg_begin[i], seg_begin[i] + seg_elems[i]) (multiples of 4 elements; elements outside every segment are not
- * touched), global norm over all flat_elems gradients.  `packed` (optional): compute-dtype copy of the updated
- * parameters at the same offsets (packed_f32 = 0: bf16), what the operator sequence's GEMMs read. */
+ * segments [seg_begin[i], seg_begin[i] + seg_elems[i]) (offsets and lengths multiples of 4 elements), global norm over the
+ * gradients of the segments (values outside every segment are neither read for the norm nor written).  `packed` (optional):
+ * compute-dtype copy of the updated parameters at the same offsets (packed_f32 = 0: bf16), what the operator sequence's GEMMs
+ * read.  Writes params, exp_avg, exp_avg_sq and packed inside the segments, scratch and grad_norm; refuses (-1, writing nothing)
+ * more than 56 segments, a segment past flat_elems or not 4-element aligned. */
 typedef struct mmdeer_adamw_flat_args {
   float* params; const float* grads; float* exp_avg; float* exp_avg_sq;
   void* packed; int32_t packed_f32;

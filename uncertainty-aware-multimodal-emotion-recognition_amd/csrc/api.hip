@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "../../include/mmdeer.h"
 #include "attention.h"
@@ -344,6 +345,9 @@ struct Exec {
     p.slab_b = p.bias_grad ? L->slab + (p.bias_grad - grads) : nullptr;
   }
   // segments that fold a split-K problem's slabs into its final destinations
+  // The counts round up to 4 (the fold's f32x4 granule) without reading or writing past C / bias_grad: every problem of the
+  // backward has M, N, ldc and batch strides multiples of 4 (the group launcher refuses a transposed A with M % 4, and any
+  // N % 4) and Stack C's parameter table (params.inc) has no size or offset that is not, so the rounding is exact.
   static void add_slab_segments(ReduceTable& t, const GemmProblem& p, const float* slab, float* grads) {
     if (p.splitk <= 1) return;
     const long long csz = (long long)(p.batch - 1) * p.sC + (long long)(p.M - 1) * p.ldc + p.N;   // extent of C incl. batches
@@ -1296,6 +1300,15 @@ int batch_splitk(int K, int f32, int boost) {
 // -L.  (Round 4 before this: a fixed 16 K-tiles per slice, times a boost that counted 256 x 256 tiles: Stack B's first group of 16
 // matrices ran as 592 workgroups in three rounds + a 17 us fold, 68 us, where 148 unsplit workgroups take one round of ~43 us.)
 // Other kernels: slices of ksteps_target K-tiles, times `boost` when the group would leave most of the chip idle.
+// Whether a problem of mmdeer_gemm_batch may be split: the fold of its slab slices runs over C and bias_grad as dense runs of a
+// multiple of 4 floats with 16-byte vector accesses.  The others (a C with ldc != N, an unaligned output) run their whole reduction
+// in one workgroup per tile, at any K: whether a call is accepted, and what it writes, does not depend on the split policy.
+bool batch_may_split(const mmdeer_gemm_args& q) {
+  return q.ldc == q.N && (long long)q.M * q.N % 4 == 0 && ((uintptr_t)q.C % 16) == 0 &&
+         (!q.bias_grad || (q.M % 4 == 0 && ((uintptr_t)q.bias_grad % 16) == 0));
+}
+int batch_problem_splitk(const mmdeer_gemm_args& q, int f32, int boost) { return batch_may_split(q) ? batch_splitk(q.K, f32, boost) : 1; }
+
 int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {
   if (!f32 && opt(OPT_DW_TILE) == 2 && opt(OPT_KSTEPS) == 0) {
     int bestL = 16;
@@ -1305,7 +1318,7 @@ int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {
       int longest = 0;
       for (int i = 0; i < n; ++i) {
         const long long tiles = (long long)((a[i].M + 127) / 128) * ((a[i].N + 127) / 128);
-        const int nk = gemm_ktiles(a[i].K, f32), sk = batch_splitk(a[i].K, f32, -L), len = (nk + sk - 1) / sk;
+        const int nk = gemm_ktiles(a[i].K, f32), sk = batch_problem_splitk(a[i], f32, -L), len = (nk + sk - 1) / sk;
         wgs += tiles * sk;
         if (sk > 1) slab_tiles += tiles * sk;
         if (len > longest) longest = len;
@@ -1319,12 +1332,32 @@ int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {
   const int t = (!f32 && opt(OPT_DW_TILE) == 2) ? 128 : 256;
   long long wgs = 0;
   for (int i = 0; i < n; ++i)
-    wgs += (long long)((a[i].M + t - 1) / t) * ((a[i].N + t - 1) / t) * batch_splitk(a[i].K, f32, 1);
+    wgs += (long long)((a[i].M + t - 1) / t) * ((a[i].N + t - 1) / t) * batch_problem_splitk(a[i], f32, 1);
   int boost = 1;
   while (boost < 4 && wgs * boost * 2 <= 256) boost *= 2;
   return boost;
 }
 long long batch_slice_elems(const mmdeer_gemm_args& a) { return ((long long)a.M * a.N + a.M + 63) / 64 * 64; }
+
+// Every check of mmdeer_gemm_batch (and of the group launcher it feeds), made before the first launch: a refused call writes nothing.
+int check_gemm_batch(const mmdeer_gemm_args* a, int n) {
+  for (int i = 0; i < n; ++i) {
+    const mmdeer_gemm_args& q = a[i];
+    MMDEER_CHECK(q.trans_a && q.trans_w && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 && !q.accumulate,
+                 "gemm_batch[%d]: weight-gradient problems only (both operands transposed, fp32 C, no epilogue)", i);
+    MMDEER_CHECK((q.compute_f32 ? 1 : 0) == (a[0].compute_f32 ? 1 : 0), "gemm_batch[%d]: all problems must share the compute dtype", i);
+    MMDEER_CHECK(!q.compute_f32 || (q.a_f32 && q.w_f32), "gemm_batch[%d]: fp32 compute needs fp32 operands", i);
+    MMDEER_CHECK(q.A && q.W && q.C, "gemm_batch[%d]: A / W / C must be non-NULL", i);
+    MMDEER_CHECK(q.M > 0 && q.N > 0 && q.K > 0 && q.M % 4 == 0 && q.N % 4 == 0,
+                 "gemm_batch[%d]: M=%d N=%d K=%d: positive, M and N multiples of 4", i, q.M, q.N, q.K);
+    MMDEER_CHECK(q.lda >= q.M && q.ldw >= q.N && q.ldc >= q.N && q.lda % 4 == 0 && q.ldw % 4 == 0 && q.ldc % 4 == 0,
+                 "gemm_batch[%d]: lda >= M, ldw >= N, ldc >= N, all multiples of 4", i);
+    MMDEER_CHECK((long long)q.lda * q.K >= 8 && (long long)q.ldw * q.K >= 8, "gemm_batch[%d]: operands must hold at least 8 elements", i);
+    MMDEER_CHECK(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.W % 16) == 0 && ((uintptr_t)q.C % 8) == 0,
+                 "gemm_batch[%d]: A and W must be 16-byte aligned, C 8-byte aligned", i);
+  }
+  return 0;
+}
 }  // namespace
 
 long long mmdeer_gemm_batch_slab_elems(const mmdeer_gemm_args* a, int n) {
@@ -1334,7 +1367,7 @@ long long mmdeer_gemm_batch_slab_elems(const mmdeer_gemm_args* a, int n) {
     const int cnt = (n - i0) < GEMM_MAX_PROBLEMS ? (n - i0) : GEMM_MAX_PROBLEMS, f32 = a[i0].compute_f32 ? 1 : 0;
     const int boost = batch_boost(a + i0, cnt, f32);
     for (int i = i0; i < i0 + cnt; ++i) {
-      const int sk = batch_splitk(a[i].K, f32, boost);
+      const int sk = batch_problem_splitk(a[i], f32, boost);
       if (sk > 1) tot += sk * batch_slice_elems(a[i]);
     }
   }
@@ -1343,43 +1376,54 @@ long long mmdeer_gemm_batch_slab_elems(const mmdeer_gemm_args* a, int n) {
 
 int mmdeer_gemm_batch(const mmdeer_gemm_args* a, int n, float* slab, long long slab_elems, void* stream) {
   MMDEER_CHECK(a != nullptr && n >= 0, "gemm_batch: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
+  TRY(check_gemm_batch(a, n));
+  const long long need = mmdeer_gemm_batch_slab_elems(a, n);
+  MMDEER_CHECK(need == 0 || (slab != nullptr && ((uintptr_t)slab % 16) == 0 && need <= slab_elems),
+               "gemm_batch: slab too small or unaligned (%lld floats given, %lld needed, 16-byte aligned)", slab_elems, need);
+  const int f32 = n > 0 && a[0].compute_f32 ? 1 : 0;
+  // every group is built and checked (operand source modes included) before the first launch
+  std::vector<GemmGroup> groups((n + GEMM_MAX_PROBLEMS - 1) / GEMM_MAX_PROBLEMS);
+  std::vector<ReduceTable> folds(groups.size());
+  std::vector<GemmTile> tiles(groups.size());
   long long used = 0;
-  for (int i0 = 0; i0 < n; i0 += GEMM_MAX_PROBLEMS) {
-    GemmGroup g{};
-    ReduceTable rt{};
-    const int f32 = a[i0].compute_f32 ? 1 : 0;
+  for (int i0 = 0, gi = 0; i0 < n; i0 += GEMM_MAX_PROBLEMS, ++gi) {
+    GemmGroup& g = groups[gi];
+    ReduceTable& rt = folds[gi];
+    g = GemmGroup{};
+    rt = ReduceTable{};
+    static_assert(2 * GEMM_MAX_PROBLEMS <= REDUCE_MAX_SEGMENTS, "the fold of one group (C and bias_grad per problem) is one launch");
     const int boost = batch_boost(a + i0, (n - i0) < GEMM_MAX_PROBLEMS ? (n - i0) : GEMM_MAX_PROBLEMS, f32);
     for (int i = i0; i < n && i < i0 + GEMM_MAX_PROBLEMS; ++i) {
       const mmdeer_gemm_args& q = a[i];
-      MMDEER_CHECK(q.trans_a && q.trans_w && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 && !q.accumulate,
-                   "gemm_batch[%d]: weight-gradient problems only (both operands transposed, fp32 C, no epilogue)", i);
-      MMDEER_CHECK((q.compute_f32 ? 1 : 0) == f32, "gemm_batch[%d]: all problems must share the compute dtype", i);
-      MMDEER_CHECK(q.A && q.W && q.C, "gemm_batch[%d]: A / W / C must be non-NULL", i);
       GemmProblem& p = g.p[g.nprob++];
       gemm_problem_defaults(p);
       p.A = q.A; p.B = q.W; p.C = q.C; p.bias_grad = q.bias_grad;
       p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldw; p.ldc = q.ldc;
       p.a_f32 = q.a_f32; p.b_f32 = q.w_f32; p.c_f32 = 1; p.trans_a = 1; p.trans_b = 1;
-      const int sk = batch_splitk(q.K, f32, boost);
-      if (sk > 1) {
+      const int sk = batch_problem_splitk(q, f32, boost);
+      if (sk > 1) {         // batch_may_split: C is dense (ldc == N) and M*N, M are multiples of 4 -- the fold counts are exact
         const long long per = batch_slice_elems(q);
-        MMDEER_CHECK(slab != nullptr && used + sk * per <= slab_elems, "gemm_batch: slab too small (%lld floats given)", slab_elems);
         p.splitk = sk; p.slab_stride = per; p.slab_c = slab + used; p.slab_b = slab + used + (long long)q.M * q.N;
         used += sk * per;
-        MMDEER_CHECK(rt.nseg + 2 <= REDUCE_MAX_SEGMENTS, "gemm_batch: too many fold segments");
         int k = rt.nseg;
-        rt.src[k] = p.slab_c; rt.dst[k] = reinterpret_cast<float*>(p.C); rt.nparts[k] = sk;
-        rt.n[k] = (int)(((long long)(q.M - 1) * q.ldc + q.N + 3) / 4 * 4); rt.stride[k] = per; ++k;
-        // the fold of C is one contiguous run only when ldc == N; otherwise fold row by row is not available: require it
-        MMDEER_CHECK(q.ldc == q.N, "gemm_batch[%d]: split-K needs a dense C (ldc == N)", i);
-        if (p.bias_grad) { rt.src[k] = p.slab_b; rt.dst[k] = p.bias_grad; rt.nparts[k] = sk; rt.n[k] = (q.M + 3) / 4 * 4; rt.stride[k] = per; ++k; }
+        rt.src[k] = p.slab_c; rt.dst[k] = reinterpret_cast<float*>(p.C); rt.nparts[k] = sk; rt.n[k] = q.M * q.N; rt.stride[k] = per; ++k;
+        if (p.bias_grad) { rt.src[k] = p.slab_b; rt.dst[k] = p.bias_grad; rt.nparts[k] = sk; rt.n[k] = q.M; rt.stride[k] = per; ++k; }
         rt.nseg = k;
       }
     }
     g.drop = make_drop(0.f, 0, 0);
-    TRY(launch_gemm_group(g, f32, pick_tile(g), s));
-    if (rt.nseg > 0) TRY(launch_reduce_partials(rt, s));
+    tiles[gi] = pick_tile(g);
+    TRY(prepare_gemm_group(g, f32, tiles[gi]));
+    // bf16 compute: the weight-gradient kernels read dY (A) in whole 16-byte chunks only (a padded M only where the whole group runs on
+    // the LDS-DMA kernels); W may be fp32 (converted by the loader) or bf16
+    for (int k = 0; k < g.nprob; ++k)
+      MMDEER_CHECK(f32 || g.p[k].a_mode == SRC_BF16_V16,
+                   "gemm_batch[%d]: bf16 compute needs a bf16 A (dY) with lda %% 8 == 0 and M %% 8 == 0", i0 + k);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    TRY(launch_gemm_group(groups[gi], f32, tiles[gi], s));
+    if (folds[gi].nseg > 0) TRY(launch_reduce_partials(folds[gi], s));
   }
   return 0;
 }
@@ -1387,12 +1431,13 @@ int mmdeer_gemm_batch(const mmdeer_gemm_args* a, int n, float* slab, long long s
 int mmdeer_reduce_batch(int n, const float* const* src, float* const* dst, const int32_t* nparts, const int32_t* count,
                         const long long* stride, void* stream) {
   MMDEER_CHECK(n >= 0 && (n == 0 || (src && dst && nparts && count && stride)), "reduce_batch: bad arguments");
+  for (int i = 0; i < n; ++i)       // every segment before the first launch: a refused call writes nothing
+    MMDEER_CHECK(src[i] && dst[i] && nparts[i] >= 1 && count[i] >= 0 && count[i] % 4 == 0 && stride[i] % 4 == 0 &&
+                     ((uintptr_t)src[i] % 16) == 0 && ((uintptr_t)dst[i] % 16) == 0,
+                 "reduce_batch[%d]: 16-byte aligned pointers, count and stride multiples of 4", i);
   for (int i0 = 0; i0 < n; i0 += REDUCE_MAX_SEGMENTS) {
     ReduceTable t{};
     for (int i = i0; i < n && i < i0 + REDUCE_MAX_SEGMENTS; ++i) {
-      MMDEER_CHECK(src[i] && dst[i] && nparts[i] >= 1 && count[i] >= 0 && count[i] % 4 == 0 && stride[i] % 4 == 0 &&
-                       ((uintptr_t)src[i] % 16) == 0 && ((uintptr_t)dst[i] % 16) == 0,
-                   "reduce_batch[%d]: 16-byte aligned pointers, count and stride multiples of 4", i);
       const int k = t.nseg++;
       t.src[k] = src[i]; t.dst[k] = dst[i]; t.nparts[k] = nparts[i]; t.n[k] = count[i]; t.stride[k] = stride[i];
     }
@@ -1404,10 +1449,14 @@ int mmdeer_reduce_batch(int n, const float* const* src, float* const* dst, const
 int mmdeer_pack_transposed_batch(int n, const float* const* src, const int32_t* rows, const int32_t* cols, void* dst,
                                  const long long* dst_off, const int32_t* ld_dst, const int32_t* dst_col, int dst_f32, void* stream) {
   MMDEER_CHECK(n >= 0 && (n == 0 || (src && rows && cols && dst && dst_off && ld_dst && dst_col)), "pack_transposed_batch: bad arguments");
+  for (int i = 0; i < n; ++i)       // every matrix before the first launch: a refused call writes nothing
+    MMDEER_CHECK(src[i] && rows[i] > 0 && cols[i] > 0 && dst_off[i] >= 0 && dst_col[i] >= 0 && ld_dst[i] >= 0 &&
+                     (ld_dst[i] == 0 || (long long)dst_col[i] + rows[i] <= ld_dst[i]),
+                 "pack_transposed_batch[%d]: bad matrix (rows %d, cols %d, dst_off %lld, ld_dst %d, dst_col %d)", i, rows[i], cols[i],
+                 dst_off[i], ld_dst[i], dst_col[i]);
   for (int i0 = 0; i0 < n; i0 += PACKT_MAX) {
     PackTTable t{};
     for (int i = i0; i < n && i < i0 + PACKT_MAX; ++i) {
-      MMDEER_CHECK(src[i] && rows[i] > 0 && cols[i] > 0 && dst_off[i] >= 0, "pack_transposed_batch[%d]: bad matrix", i);
       const int k = t.nmat++;
       t.src[k] = src[i]; t.rows[k] = rows[i]; t.cols[k] = cols[i]; t.dst_off[k] = dst_off[i]; t.ld_dst[k] = ld_dst[i]; t.dst_col[k] = dst_col[i];
     }

@@ -36,11 +36,9 @@ void gemm_problem_defaults(GemmProblem& p) {
   p.mask_scale = 1.f;
 }
 
-int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream) {
-  static const int bm_of[5] = {64, 128, 128, 256, 256}, bn_of[5] = {64, 64, 128, 256, 128};
+int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   MMDEER_CHECK(g.nprob >= 1 && g.nprob <= GEMM_MAX_PROBLEMS, "gemm: bad problem count %d", g.nprob);
   MMDEER_CHECK((int)tile_req >= 0 && (int)tile_req <= 4, "gemm: bad tile id %d", (int)tile_req);
-  g.xcd_remap = env_xcd();
   const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
   // the whole group can run on the 256x256 weight-gradient kernel (it alone tolerates padded, half-valid row ends)
   // the weight-gradient DMA kernel on 128x128 / 256x128 tiles (option dw_tile)
@@ -92,6 +90,16 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
       p.b_mode = p.b_f32 ? SRC_F32 : (bv16 ? SRC_BF16_V16 : SRC_BF16_V8);
     }
   }
+  return 0;
+}
+
+int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream) {
+  static const int bm_of[5] = {64, 128, 128, 256, 256}, bn_of[5] = {64, 64, 128, 256, 128};
+  if (prepare_gemm_group(g, compute_f32, tile_req) != 0) return -1;
+  g.xcd_remap = env_xcd();
+  const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
+  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && env_glds() && opt(OPT_DW_TILE) == 2;
+  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && env_glds();
   // One launch per distinct (A mode, B mode) pair: the kernels are specialised on the pair so that their K loop
   // has no data-dependent control flow.  Most groups are homogeneous (one launch).
   bool done[GEMM_MAX_PROBLEMS] = {};

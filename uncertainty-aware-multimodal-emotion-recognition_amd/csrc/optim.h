@@ -49,7 +49,7 @@ struct AdamImagedTable { bf16_t* base; int n, total_tiles; AdamImaged m[ADAM_MAX
 // The fused form: `t` lists the tensors WITHOUT images (vectors, the 4 x 64 last head layers, ...), `im` the imaged matrices.
 int launch_adamw_pack_images(AdamTable& t, AdamImagedTable& im, bf16_t* wdst, float* vdst, hipStream_t s);
 
-// grads are scaled by grad_scale, then by min(1, max_norm / (norm + 1e-6)) when max_norm > 0 (clip_grad_norm_),
+// grads are scaled by grad_scale, then by min(1, max_norm / (norm + 1e-6)) when max_norm > 0 (clip_grad_norm_ over the segments of t),
 // then torch.optim.AdamW's update is applied; packed copies go to wdst (compute dtype, matrices) / vdst (fp32, vectors).
 int launch_adamw_pack(AdamTable& t, void* wdst, int w_f32, float* vdst, hipStream_t s);
 

@@ -28,6 +28,29 @@ __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* g, lon
   if (threadIdx.x == 0) partials[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
 }
 
+// The same partials over the segments of an AdamTable only (launch_adamw_pack): values outside every segment do not enter the norm.
+// A chunk goes to the thread the flat pass above would give it (flat chunk index mod the grid's threads), so over a table sorted by
+// offset whose gaps hold zeros the partials are bit for bit those of the flat pass.
+__global__ __launch_bounds__(256) void sumsq_segments_kernel(const AdamTable t) {
+  __shared__ float sm[4];
+  const auto& T = karg<AdamTable>();
+  const long long nthr = gridDim.x * 256ll, me = blockIdx.x * 256ll + threadIdx.x;
+  float acc = 0.f;
+  for (int s = 0; s < T.nseg; ++s) {
+    const long long c0 = T.off[s] / 4, n4 = T.n[s] / 4;
+    long long j = (me - c0) % nthr;
+    if (j < 0) j += nthr;
+    for (; j < n4; j += nthr) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(T.grads + (c0 + j) * 4);
+      acc += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) T.partials[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
 struct AdamCoef { float gs, b1, b2, eps, wd, ibc1, isbc2; };
 
 // torch.optim.AdamW (decoupled decay): p *= 1 - lr*wd; m, v EMAs; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
@@ -287,7 +310,7 @@ int launch_adamw_pack(AdamTable& t, void* wdst, int w_f32, float* vdst, hipStrea
   for (int i = t.nseg; i <= ADAM_MAX_SEGMENTS; ++i) t.chunk_start[i] = c;
   t.total_chunks = c;
   if (c == 0) return 0;
-  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(ADAM_NPART), dim3(256), 0, s, t.grads, t.flat_elems / 4, t.partials);
+  hipLaunchKernelGGL(sumsq_segments_kernel, dim3(ADAM_NPART), dim3(256), 0, s, t);
   MMDEER_HIP(hipGetLastError());
   const int blocks = (c + 1023) / 1024;
   if (w_f32) hipLaunchKernelGGL(adamw_pack_kernel<true>, dim3(blocks), dim3(256), 0, s, t, wdst, vdst);

@@ -114,10 +114,10 @@ class FlatAdamW(torch.optim.Optimizer):
     'encoder' in their name at ``encoder_lr_scale`` x lr (training.py:125-140).  Parameters the backward never reaches (the
     calibration layer: ``grad is None`` under autograd, which torch's AdamW skips) are left untouched.
 
-    The clipping norm is taken over the WHOLE flat gradient buffer (one pass over contiguous memory): with ``params=`` naming a
-    subset (frozen encoders) it includes the excluded parameters' gradients, where ``clip_grad_norm_`` over the optimiser's own
-    parameters would not -- zero the frozen ranges of the gradient buffer if that matters.  betas / eps / weight_decay must be the
-    same in every group; ``step()`` re-checks it (a scheduler or a caller editing ``param_groups`` later is not ignored silently)."""
+    The clipping norm is taken over the optimiser's own parameters (the segments of the flat gradient buffer it updates), as
+    ``clip_grad_norm_`` over them would: with ``params=`` naming a subset (frozen encoders) the excluded parameters' gradients do not
+    enter it.  betas / eps / weight_decay must be the same in every group; ``step()`` re-checks it (a scheduler or a caller editing
+    ``param_groups`` later is not ignored silently)."""
 
     def __init__(self, model, params: Optional[Iterable] = None, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, encoder_lr_scale: float = 0.5, skip=("calibration_layer.",)):
