@@ -246,13 +246,27 @@ typedef struct mmdeer_gemm_args {
   uint64_t seed, offset;
   const uint64_t* offset_dev; /* optional device counter added to `offset` when the kernel runs (HIP-graph replays draw fresh masks) */
   /* split-K (weight-gradient shapes: few output tiles, long reduction): splitk > 1 reduces K in slices whose fp32
-   * partials go to `slab` (splitk * (M*N + M) floats, rounded up to a multiple of 4 per slice) and are then
-   * summed in a fixed order; needs an fp32 C and no epilogue. */
+   * partials go to `slab` (splitk * (M*N + M) floats, rounded up to a multiple of 4 per slice, 16-byte aligned) and are
+   * then summed in a fixed order; needs an fp32 C and no epilogue.  A problem with ldc != N, a C not 16-byte aligned, or a
+   * bias_grad with M % 4 != 0 or not 16-byte aligned is not split (one workgroup per tile runs its whole reduction). */
   int32_t splitk;
   float* slab;
   void* debug;   /* diagnostic builds (-DMMDEER_STAMPS) only: uint64 buffer for in-kernel cycle stamps; NULL otherwise */
   void* stream;
 } mmdeer_gemm_args;
+/* Writes C[r][0, N) for r < M (row stride ldc), bias_grad[0, M) when given, and, when the problem is split, the first
+ * splitk * (M*N + M rounded up to 4) floats of `slab`; nothing else (M = 0 writes nothing).  Operand elements past K (past M /
+ * N for a transposed operand) and rows past the operand are never read into a stored output.  Refuses (-1, writing nothing,
+ * message in mmdeer_last_error()) unless: A, W, C non-NULL; N % 4 == 0; K % 4 == 0 for a k-contiguous operand; M % 4 == 0 for a
+ * transposed A; lda, ldw, ldc (and ldy with Y) multiples of 4 with lda >= (trans_a ? M : K), ldw >= (trans_w ? N : K),
+ * ldc >= N, ldy >= N; A and W 16-byte aligned, C 8-byte aligned; accumulate only with an fp32 C; splitk > 1 only with a slab, an
+ * fp32 C and no epilogue (bias, relu, Y, accumulate, drop_site, regen_site); fp32 compute only with fp32 operands; not
+ * (trans_a = 1, trans_w = 0).  Under bf16 compute an operand is read as fp32 (converted), as bf16 in 16-byte chunks (ld % 8 == 0
+ * and extent % 8 == 0) or as bf16 in 8-byte chunks, and only these (A, W) pairs are instantiated -- (trans_a, trans_w) = (0, 0):
+ * (16, 16), (f32, 16), (f32, 8), (8, 8); (0, 1): (16, 16), (16, 8); (1, 1): (16, 16), (16, f32), (16, 8).  Exception: a transposed
+ * bf16 operand with extent % 8 != 0 and ld >= extent rounded up to 8 is read in 16-byte chunks when the call runs on the
+ * weight-gradient DMA kernel (tile 3 or 4, or tile 2 under option dw_tile = 2; both operands bf16, K % 32 == 0, a 16-byte aligned
+ * fp32 C, no epilogue but bias_grad / accumulate), so such an A is accepted there and refused elsewhere. */
 int mmdeer_gemm(const mmdeer_gemm_args* a);
 
 /* n weight-gradient problems (every one trans_a = trans_w = 1, fp32 C, no epilogue; the same compute dtype) as grouped

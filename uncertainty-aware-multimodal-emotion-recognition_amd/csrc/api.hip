@@ -1242,6 +1242,16 @@ int mmdeer_pack_weights(const void* const* params, void* weights, size_t weights
 }
 
 // ------------------------------------------------------------------ single operators
+namespace {
+// Whether a problem of mmdeer_gemm / mmdeer_gemm_batch may be split: the fold of its slab slices runs over C and bias_grad as dense
+// runs of a multiple of 4 floats with 16-byte vector accesses.  The others (a C with ldc != N, an unaligned output) run their whole
+// reduction in one workgroup per tile, at any K: whether a call is accepted, and what it writes, does not depend on the split policy.
+bool batch_may_split(const mmdeer_gemm_args& q) {
+  return q.ldc == q.N && (long long)q.M * q.N % 4 == 0 && ((uintptr_t)q.C % 16) == 0 &&
+         (!q.bias_grad || (q.M % 4 == 0 && ((uintptr_t)q.bias_grad % 16) == 0));
+}
+}  // namespace
+
 int mmdeer_gemm(const mmdeer_gemm_args* a) {
   MMDEER_CHECK(a != nullptr, "args is NULL");
   GemmGroup g{};
@@ -1256,24 +1266,33 @@ int mmdeer_gemm(const mmdeer_gemm_args* a) {
   p.mask_scale = a->mask_scale;
   MMDEER_CHECK(a->A && a->W && a->C, "gemm: A / W / C must be non-NULL");
   if (a->splitk > 1) {
-    MMDEER_CHECK(a->slab != nullptr, "gemm: split-K needs a slab buffer of splitk * (M*N + M) floats");
-    p.splitk = a->splitk;
-    p.slab_stride = ((long long)a->M * a->N + a->M + 3) / 4 * 4;
-    p.slab_c = a->slab;
-    p.slab_b = a->slab + (long long)a->M * a->N;
+    // the request is checked whether or not the problem is then split: acceptance does not depend on the layout of C
+    MMDEER_CHECK(a->slab != nullptr && ((uintptr_t)a->slab % 16) == 0,
+                 "gemm: split-K needs a 16-byte aligned slab of splitk * (M*N + M) floats");
+    MMDEER_CHECK(a->c_f32 && !a->bias && !a->relu && !a->Y && !a->accumulate && a->drop_site < 0 && a->regen_site < 0,
+                 "gemm: split-K needs an fp32 C and no epilogue");
+    if (batch_may_split(*a)) {
+      p.splitk = a->splitk;
+      p.slab_stride = ((long long)a->M * a->N + a->M + 3) / 4 * 4;
+      p.slab_c = a->slab;
+      p.slab_b = a->slab + (long long)a->M * a->N;
+    }
   }
   g.drop = make_drop(a->dropout_p, a->seed, a->offset, a->offset_dev);
   g.stamps = reinterpret_cast<unsigned long long*>(a->debug);
   GemmTile t = (a->tile >= 0 && a->tile <= 4) ? (GemmTile)a->tile : pick_tile(g);
-  TRY(launch_gemm_group(g, a->compute_f32 ? 1 : 0, t, (hipStream_t)a->stream));
-  if (g.p[0].splitk > 1) {   // fold the K-slices into C (and bias_grad)
+  const int f32 = a->compute_f32 ? 1 : 0;
+  TRY(prepare_gemm_group(g, f32, t));   // every check before the first launch (prepare also clamps splitk to the K-tile count)
+  const int sk = g.p[0].splitk;
+  TRY(launch_gemm_group(g, f32, t, (hipStream_t)a->stream));
+  if (sk > 1) {   // fold the K-slices into C (and bias_grad); batch_may_split: dense C, M*N and M multiples of 4
     ReduceTable rt{};
     rt.nseg = 1;
-    rt.src[0] = p.slab_c; rt.dst[0] = reinterpret_cast<float*>(p.C); rt.nparts[0] = g.p[0].splitk;
+    rt.src[0] = p.slab_c; rt.dst[0] = reinterpret_cast<float*>(p.C); rt.nparts[0] = sk;
     rt.n[0] = a->M * a->N; rt.stride[0] = p.slab_stride;
     if (p.bias_grad) {
       rt.nseg = 2;
-      rt.src[1] = p.slab_b; rt.dst[1] = p.bias_grad; rt.nparts[1] = g.p[0].splitk; rt.n[1] = a->M; rt.stride[1] = p.slab_stride;
+      rt.src[1] = p.slab_b; rt.dst[1] = p.bias_grad; rt.nparts[1] = sk; rt.n[1] = a->M; rt.stride[1] = p.slab_stride;
     }
     TRY(launch_reduce_partials(rt, (hipStream_t)a->stream));
   }
@@ -1300,13 +1319,6 @@ int batch_splitk(int K, int f32, int boost) {
 // -L.  (Round 4 before this: a fixed 16 K-tiles per slice, times a boost that counted 256 x 256 tiles: Stack B's first group of 16
 // matrices ran as 592 workgroups in three rounds + a 17 us fold, 68 us, where 148 unsplit workgroups take one round of ~43 us.)
 // Other kernels: slices of ksteps_target K-tiles, times `boost` when the group would leave most of the chip idle.
-// Whether a problem of mmdeer_gemm_batch may be split: the fold of its slab slices runs over C and bias_grad as dense runs of a
-// multiple of 4 floats with 16-byte vector accesses.  The others (a C with ldc != N, an unaligned output) run their whole reduction
-// in one workgroup per tile, at any K: whether a call is accepted, and what it writes, does not depend on the split policy.
-bool batch_may_split(const mmdeer_gemm_args& q) {
-  return q.ldc == q.N && (long long)q.M * q.N % 4 == 0 && ((uintptr_t)q.C % 16) == 0 &&
-         (!q.bias_grad || (q.M % 4 == 0 && ((uintptr_t)q.bias_grad % 16) == 0));
-}
 int batch_problem_splitk(const mmdeer_gemm_args& q, int f32, int boost) { return batch_may_split(q) ? batch_splitk(q.K, f32, boost) : 1; }
 
 int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {

@@ -60,6 +60,7 @@ enum GemmTile { TILE_64x64 = 0, TILE_128x64 = 1, TILE_128x128 = 2, TILE_256x256 
 // compute_f32 = 1: fp32 operands in LDS, v_mfma_f32_16x16x4_f32 (exact fp32); 0: bf16 operands, v_mfma_f32_16x16x32_bf16.
 // Enqueues on `stream`, never synchronises.  Returns 0 / -1 (message via mmdeer_last_error()).
 // The checks of launch_gemm_group and the source mode of every operand (a_mode / b_mode), without launching anything.
+// (launch_gemm_group also refuses a source-mode pair that no kernel instantiates, for every problem before its first launch.)
 int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile);
 int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile, hipStream_t stream);
 

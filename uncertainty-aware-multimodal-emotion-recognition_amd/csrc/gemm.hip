@@ -27,6 +27,16 @@ int env_nt128() { return opt(OPT_NT128); }
 int env_glds() { return opt(OPT_GLDS); }
 }  // namespace
 
+// the (A mode, B mode) pairs gemm_dispatch_nt / _nx / _tt instantiate (fp32 compute: (F32, F32) only)
+bool gemm_modes_instantiated(int ta, int tb, int compute_f32, int am, int bm) {
+  if (compute_f32) return am == SRC_F32 && bm == SRC_F32;
+  const bool vv = am == SRC_BF16_V16 && bm == SRC_BF16_V16;
+  if (!ta && !tb) return vv || (am == SRC_F32 && (bm == SRC_BF16_V16 || bm == SRC_BF16_V8)) || (am == SRC_BF16_V8 && bm == SRC_BF16_V8);
+  if (!ta && tb) return vv || (am == SRC_BF16_V16 && bm == SRC_BF16_V8);
+  if (ta && tb) return vv || (am == SRC_BF16_V16 && (bm == SRC_F32 || bm == SRC_BF16_V8));
+  return false;
+}
+
 void gemm_problem_defaults(GemmProblem& p) {
   p = GemmProblem{};
   p.batch = 1;
@@ -40,6 +50,7 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   MMDEER_CHECK(g.nprob >= 1 && g.nprob <= GEMM_MAX_PROBLEMS, "gemm: bad problem count %d", g.nprob);
   MMDEER_CHECK((int)tile_req >= 0 && (int)tile_req <= 4, "gemm: bad tile id %d", (int)tile_req);
   const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
+  MMDEER_CHECK(!ta || tb, "gemm: (trans_a=1, trans_b=0) is not instantiated");
   // the whole group can run on the 256x256 weight-gradient kernel (it alone tolerates padded, half-valid row ends)
   // the weight-gradient DMA kernel on 128x128 / 256x128 tiles (option dw_tile)
   const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && env_glds() && opt(OPT_DW_TILE) == 2;
@@ -47,8 +58,10 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   bool pad256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && env_glds();
   for (int i = 0; i < g.nprob && pad256; ++i) {
     const GemmProblem& q = g.p[i];
+    // (the output conditions of the DMA kernel too: a half-valid chunk read by the register-staged fallback would be dropped)
     pad256 = !q.a_f32 && !q.b_f32 && q.K % 32 == 0 && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 &&
-             q.lda % 8 == 0 && q.ldb % 8 == 0 && q.sA % 8 == 0 && q.sB % 8 == 0;
+             q.lda % 8 == 0 && q.ldb % 8 == 0 && q.sA % 8 == 0 && q.sB % 8 == 0 && (uintptr_t)q.C % 16 == 0 && q.sC % 4 == 0 &&
+             (q.splitk <= 1 || ((uintptr_t)q.slab_c % 16 == 0 && q.slab_stride % 4 == 0));
   }
   for (int i = 0; i < g.nprob; ++i) {
     GemmProblem& p = g.p[i];
@@ -60,6 +73,10 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
     MMDEER_CHECK(p.trans_b || p.K % 4 == 0, "gemm[%d]: K=%d must be a multiple of 4 for a k-contiguous B", i, p.K);
     MMDEER_CHECK(!p.trans_a || p.M % 4 == 0, "gemm[%d]: M=%d must be a multiple of 4 for a transposed A", i, p.M);
     MMDEER_CHECK(p.lda % 4 == 0 && p.ldb % 4 == 0 && p.ldc % 4 == 0, "gemm[%d]: leading dims must be multiples of 4", i);
+    MMDEER_CHECK(p.lda >= (p.trans_a ? p.M : p.K), "gemm[%d]: lda=%d is shorter than a row of A (%d)", i, p.lda, p.trans_a ? p.M : p.K);
+    MMDEER_CHECK(p.ldb >= (p.trans_b ? p.N : p.K), "gemm[%d]: ldw=%d is shorter than a row of W (%d)", i, p.ldb, p.trans_b ? p.N : p.K);
+    MMDEER_CHECK(p.ldc >= p.N, "gemm[%d]: ldc=%d is shorter than a row of C (N=%d)", i, p.ldc, p.N);
+    MMDEER_CHECK(!p.Y || p.ldy >= p.N, "gemm[%d]: ldy=%d is shorter than a row of Y (N=%d)", i, p.ldy, p.N);
     MMDEER_CHECK(((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.B % 16 == 0) && ((uintptr_t)p.C % 8 == 0),
                  "gemm[%d]: A and B must be 16-byte aligned, C 8-byte aligned", i);
     MMDEER_CHECK(p.M == 0 || ((long long)p.lda * (p.trans_a ? p.K : p.M) >= 8 && (long long)p.ldb * (p.trans_b ? p.K : p.N) >= 8),
@@ -102,6 +119,10 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
   const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && env_glds();
   // One launch per distinct (A mode, B mode) pair: the kernels are specialised on the pair so that their K loop
   // has no data-dependent control flow.  Most groups are homogeneous (one launch).
+  // every problem's source-mode pair before the first launch of the group: a refused group writes nothing
+  for (int i = 0; i < g.nprob; ++i)
+    MMDEER_CHECK(gemm_modes_instantiated(ta, tb, compute_f32, g.p[i].a_mode, g.p[i].b_mode),
+                 "gemm[%d]: source-mode pair (%d,%d) is not instantiated for trans=(%d,%d)", i, g.p[i].a_mode, g.p[i].b_mode, ta, tb);
   bool done[GEMM_MAX_PROBLEMS] = {};
   for (int i = 0; i < g.nprob; ++i) {
     if (done[i]) continue;
