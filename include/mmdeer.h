@@ -446,6 +446,68 @@ int mmdeer_lstm_cell_t1(const void* gates, int ld_gates, void* out, int ld_out, 
 int mmdeer_lstm_cell_t1_bwd(const void* gates, int ld_gates, const void* dout, int ld_dout, void* dgates, int B, int hidden, int ndir,
                             int act_f32, void* stream);
 
+/* ---- temporal audio encoder (reference src/models/encoders.py:376-389 at T > 1): one bidirectional nn.LSTM layer over all T
+ * steps in ONE launch per pass (no workgroup waits on another; the launch count does not grow with T), and the attention pool
+ * over time.  hidden (H) must be 256 and ndir 2; "act" = fp32 when act_f32 != 0, else bf16.  Every row index below is
+ * t * B + b (time-major).  Pointers that the kernels read or write 16 bytes at a time (the images, the tape, and the rows of
+ * xg / h / dh_out / dgates: pointer 16-byte aligned, leading dimension a multiple of 16 bytes) are refused when misaligned.
+ * B = 0 or T = 0 writes nothing and returns 0.  A refused call (NULL pointer, H != 256, ndir != 2, leading dimension too
+ * small, misalignment) writes nothing, returns -1 and leaves the reason in mmdeer_last_error(); all of that is checked on
+ * the host before any HIP runtime call.
+ *
+ * mmdeer_lstm_seq_pack: the recurrent weights' device images, from the two directions' fp32 weight_hh [4H][H]:
+ * image [2][4H][H] (row-major, act; read by the forward) and, unless image_t is NULL, image_t [2][H][4H] (the transpose, act;
+ * read by the backward).
+ *
+ * mmdeer_lstm_seq_fwd: zero initial h and c, torch gate order i, f, g, o.
+ *   xg      act [T*B][ld_xg >= 8H]: W_ih x_t + b_ih + b_hh, direction d in columns [4H d, 4H (d+1))
+ *   h       act [T*B][ld_h >= 2H]: written, direction d in columns [H d, H (d+1)); the reverse direction reads x_{T-1} .. x_0 and
+ *           its state after consuming x_t is stored at row t
+ *   tape_gates fp32 [T*B][8H] dense: the activated gates sigmoid(i), sigmoid(f), tanh(g), sigmoid(o); tape_c fp32 [T*B][2H]
+ *           dense: the cell state.  Both NULL (inference): no tape is written.
+ * mmdeer_lstm_seq_bwd: backpropagation through time from dh_out act [T*B][ld_dh >= 2H] (the gradient at h), the tape and
+ *   w_hh_t -> dgates act [T*B][ld_dg >= 8H], the gradient at xg.  The caller forms dW_hh = sum_t dgates_t^T h_{t-1} (forward
+ *   direction; h_{t+1} for the reverse), dW_ih, the bias gradients and dx with mmdeer_gemm. */
+typedef struct mmdeer_lstm_seq_args {
+  const void* xg; int32_t ld_xg;
+  const void* w_hh;          /* image of mmdeer_lstm_seq_pack */
+  const void* w_hh_t;        /* image_t of mmdeer_lstm_seq_pack (backward) */
+  void* h; int32_t ld_h;
+  float* tape_gates; float* tape_c;
+  const void* dh_out; int32_t ld_dh;
+  void* dgates; int32_t ld_dg;
+  int32_t T, B, hidden, ndir, act_f32;
+  void* stream;
+} mmdeer_lstm_seq_args;
+int mmdeer_lstm_seq_pack(const float* w_hh_fwd, const float* w_hh_rev, int hidden, void* image, void* image_t, int act_f32, void* stream);
+int mmdeer_lstm_seq_fwd(const mmdeer_lstm_seq_args* a);
+int mmdeer_lstm_seq_bwd(const mmdeer_lstm_seq_args* a);
+
+/* Attention pool over time: s_{b,t} = w2 . tanh(z_{b,t}) + b2[0], a_{b,t} = softmax over t (max-subtracted),
+ * attended_b = sum_t a_{b,t} h_{b,t}.
+ *   h act [T*B][ld_h >= 2H] (the LSTM output), z act [T*B][ld_z >= H] (W1 h + b1, from mmdeer_gemm), w2 fp32 [H], b2 fp32 [1]
+ *   forward writes attended act [B][ld_att >= 2H] and weights fp32 [B][T]
+ *   backward reads weights and dout act [B][ld_dout >= 2H] and writes dh act [T*B][ld_dh >= 2H] = a_t dout (the score path's
+ *   share, dz W1, is the caller's GEMM), dz act [T*B][ld_dz >= H], dw2 fp32 [H] and db2 fp32 [1].  db2 is written as an exact
+ *   zero: b2 shifts every score of a sample equally and the softmax does not see it.  scratch: fp32, at least
+ *   MMDEER_TEMPORAL_POOL_SCRATCH elements (dw2's per-workgroup partials, folded in a fixed order: deterministic). */
+#define MMDEER_TEMPORAL_POOL_SCRATCH (256 * 256)
+typedef struct mmdeer_temporal_pool_args {
+  const void* h; int32_t ld_h;
+  const void* z; int32_t ld_z;
+  const float* w2; const float* b2;
+  void* attended; int32_t ld_att;
+  float* weights;
+  const void* dout; int32_t ld_dout;
+  void* dh; int32_t ld_dh;
+  void* dz; int32_t ld_dz;
+  float* dw2; float* db2; float* scratch;
+  int32_t T, B, hidden, act_f32;
+  void* stream;
+} mmdeer_temporal_pool_args;
+int mmdeer_temporal_pool_fwd(const mmdeer_temporal_pool_args* a);
+int mmdeer_temporal_pool_bwd(const mmdeer_temporal_pool_args* a);
+
 /* ---- streaming evaluation statistics (reference src/utils/metrics.py:59-125) ---------------------------
  * pred / target / unc: [B][3] fp32 (unc may be NULL).  acc: device double[3][8], zeroed by the caller before the first
  * batch; every call adds {n, sum p, sum t, sum p^2, sum t^2, sum pt, sum |p-t|, sum (p-t)^2} per emotion dimension over
@@ -733,7 +795,7 @@ int mmdeer_allgather(const void* send, void* recv, long long send_count, int dty
 
 /* sizeof() of an argument struct of this header by its name without the mmdeer_ prefix ("gemm_args", "chain_args", "chain_seg",
  * "repack_job", "forward_args", "backward_args", "adamw_args", "adamw_flat_args", "stackb_attn_train_args", "stackb_attn_args",
- * "stackb_forward_args", "stackb_weights", "softmax_mix_args"); -1 for an unknown name.  A binding in another language checks its
+ * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args"); -1 for an unknown name.  A binding in another language checks its
  * own layout against it at load time (mmdeer/_lib.py does). */
 long long mmdeer_sizeof(const char* struct_name);
 

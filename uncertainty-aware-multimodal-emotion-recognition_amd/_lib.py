@@ -185,11 +185,32 @@ class RepackJob(C.Structure):
                 ("transpose", c_int), ("layout", c_int), ("ld_dst", c_int), ("dst_col", c_int)]
 
 
+class LstmSeqArgs(C.Structure):
+    """mmdeer_lstm_seq_args (include/mmdeer.h)."""
+    _fields_ = [
+        ("xg", c_void_p), ("ld_xg", c_int), ("w_hh", c_void_p), ("w_hh_t", c_void_p), ("h", c_void_p), ("ld_h", c_int),
+        ("tape_gates", c_void_p), ("tape_c", c_void_p), ("dh_out", c_void_p), ("ld_dh", c_int), ("dgates", c_void_p), ("ld_dg", c_int),
+        ("T", c_int), ("B", c_int), ("hidden", c_int), ("ndir", c_int), ("act_f32", c_int), ("stream", c_void_p),
+    ]
+
+
+class TemporalPoolArgs(C.Structure):
+    """mmdeer_temporal_pool_args (include/mmdeer.h)."""
+    _fields_ = [
+        ("h", c_void_p), ("ld_h", c_int), ("z", c_void_p), ("ld_z", c_int), ("w2", c_void_p), ("b2", c_void_p),
+        ("attended", c_void_p), ("ld_att", c_int), ("weights", c_void_p), ("dout", c_void_p), ("ld_dout", c_int),
+        ("dh", c_void_p), ("ld_dh", c_int), ("dz", c_void_p), ("ld_dz", c_int), ("dw2", c_void_p), ("db2", c_void_p), ("scratch", c_void_p),
+        ("T", c_int), ("B", c_int), ("hidden", c_int), ("act_f32", c_int), ("stream", c_void_p),
+    ]
+
+
+TEMPORAL_POOL_SCRATCH = 256 * 256   # MMDEER_TEMPORAL_POOL_SCRATCH
+
 # ctypes mirror of every argument struct, by the name mmdeer_sizeof() knows it under
 STRUCTS = {"gemm_args": GemmArgs, "chain_args": ChainArgs, "chain_seg": ChainSeg, "repack_job": RepackJob, "forward_args": ForwardArgs,
            "backward_args": BackwardArgs, "adamw_args": AdamWArgs, "adamw_flat_args": AdamWFlatArgs, "stackb_attn_train_args": StackBAttnTrainArgs,
            "stackb_attn_args": StackBAttnArgs, "stackb_forward_args": StackBForwardArgs, "stackb_weights": StackBWeights,
-           "softmax_mix_args": SoftmaxMixArgs}
+           "softmax_mix_args": SoftmaxMixArgs, "lstm_seq_args": LstmSeqArgs, "temporal_pool_args": TemporalPoolArgs}
 
 # every symbol include/mmdeer.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -252,6 +273,11 @@ SYMBOLS = [
     ("mmdeer_stackb_gate_mix_bwd", c_int, [c_void_p, c_int] * 7 + [c_int, c_int, c_int, c_void_p]),
     ("mmdeer_cross_modal_attn_bwd", c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     ("mmdeer_lstm_cell_t1_bwd", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    ("mmdeer_lstm_seq_pack", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    ("mmdeer_lstm_seq_fwd", c_int, [C.POINTER(LstmSeqArgs)]),
+    ("mmdeer_lstm_seq_bwd", c_int, [C.POINTER(LstmSeqArgs)]),
+    ("mmdeer_temporal_pool_fwd", c_int, [C.POINTER(TemporalPoolArgs)]),
+    ("mmdeer_temporal_pool_bwd", c_int, [C.POINTER(TemporalPoolArgs)]),
     ("mmdeer_softmax_mix_fwd", c_int, [C.POINTER(SoftmaxMixArgs)]),
     ("mmdeer_softmax_mix_bwd", c_int, [C.POINTER(SoftmaxMixArgs)]),
     ("mmdeer_outer_fwd", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
