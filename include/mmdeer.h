@@ -714,10 +714,22 @@ int mmdeer_stackb_forward(const mmdeer_stackb_forward_args* a);
  * Weights are read from FRAGMENT-MAJOR images (mmdeer_repack, layout 1) of the [N][K] matrix a segment multiplies by (forward:
  * the nn.Linear weight; dX = dY W: its transpose [K_lin][N_lin], i.e. N = in_features, K = out_features).
  * A layer is one or more segments writing disjoint column ranges of one output panel; the last carries end_layer = 1.
- * Limits: <= MMDEER_CHAIN_MAX_SEGS segments, 8 layers, 16 bias / gamma / beta vectors of 4864 floats in total; N % 64 == 0,
- * K in {64, 128, 256, 384, 512, 768 (16-sample workgroups only)}; <= 4 column tiles per segment, of 128 columns, or of 64 when
- * N % 128 != 0 (then K must be 128 or 256); panel width <= 768 columns (16-sample workgroups) or 512 (32-sample).  Anything else
- * is refused with a message before a launch. */
+ * Limits: <= MMDEER_CHAIN_MAX_SEGS segments (so as many layers at most), 16 bias / gamma / beta vectors of 4864 floats in total;
+ * N % 64 == 0, K in {64, 128, 256, 384, 512, 768 (16-sample workgroups only)}; <= 4 column tiles per segment, of 128 columns, or
+ * of 64 when N % 128 != 0 (then K must be 128 or 256); panel width <= 768 columns (16-sample workgroups) or 512 (32-sample).
+ * Writes, for r < rows, of each layer end: stash[r][0, nout) -- or [0, stash_split) and stash2[r][0, nout - stash_split) --,
+ * xln[r][0, nout), mean[r], rstd[r], lnb_dz[r][0, nout), and lnb_partial[w][0, 2 nout) for w < mmdeer_chain_workgroups(rows,
+ * samples_per_workgroup); nothing else (rows = 0 writes nothing).  Rows of X, mask_y, lnb_y, lnb_mean, lnb_rstd past `rows`, columns
+ * of X past K0 and columns of mask_y outside [mask_col0, mask_col0 + N) are never read into a stored output.  Refuses (-1, writing
+ * nothing, message in mmdeer_last_error()) unless: 1 <= nseg <= MMDEER_CHAIN_MAX_SEGS and the last segment ends its layer;
+ * rows >= 0; samples_per_workgroup 0, 16 or 32; the limits above; X and W 16-byte aligned, ldx % 8 == 0, ldx >= K0; kin_off and
+ * nout_off non-negative multiples of 64 with kin_off + K <= the input panel's width and nout_off + N <= nout; 0 <= drop_shift < 32;
+ * bias 16-byte aligned; mask_y 8-byte aligned, ld_mask and mask_col0 multiples of 4, mask_col0 >= 0, ld_mask >= mask_col0 + N;
+ * stash 16-byte aligned, ld_stash % 8 == 0 and ld_stash >= the widest part it stores; stash_split only on a plain stash (no
+ * LayerNorm), a multiple of 8 in (0, nout), with a 16-byte aligned stash2; a LayerNorm (forward or backward) of width 256 or 512 with
+ * every pointer given and gamma / beta / xln / lnb_y / lnb_dz / lnb_partial 16-byte aligned; residual only where the layer keeps
+ * its input's width; res_add / res_dup only on a segment that is its layer alone (N = nout = 256, nout_off 0), res_add only behind a
+ * layer that wrote the bypass copy (res_dup). */
 #define MMDEER_CHAIN_MAX_SEGS 12
 typedef struct mmdeer_chain_seg {
   const void* W;            /* fragment-major image of the segment's [N][K] bf16 matrix */
@@ -764,7 +776,10 @@ int mmdeer_chain_workgroups(int rows, int samples_per_workgroup);
 /* Derived bf16 images of bf16 matrices, any number of jobs in as few launches as possible (64 jobs each).  Job j restates the
  * matrix S = src[j] ([rows][cols], row stride ld_src, columns >= cols_valid read as zero) or, with transpose, S^T, in layout 0
  * (row-major at dst[j] with row stride ld_dst, starting at column dst_col) or layout 1 (fragment-major, what mmdeer_chain streams:
- * rows of the image % 16 == 0, columns % 64 == 0). */
+ * rows of the image % 16 == 0, columns % 64 == 0).  Writes the images, nothing else.  Every job is checked before the first launch,
+ * so a refused call (-1) writes nothing; refused unless every job has a src, a 16-byte aligned dst, rows, cols > 0,
+ * 0 <= cols_valid <= cols, ld_src >= cols_valid, image columns % 8 == 0, layout 0 or 1, and for layout 0 ld_dst and dst_col
+ * multiples of 8 with dst_col + image columns <= ld_dst. */
 typedef struct mmdeer_repack_job {
   const void* src; void* dst;
   int32_t ld_src, rows, cols, cols_valid, transpose, layout, ld_dst, dst_col;

@@ -82,6 +82,147 @@ def test_layer_chain_operator_validates_its_table_on_the_host():
     assert lib.mmdeer_repack(j, 0, None) == 0
 
 
+def _chain_refusal(mutate):
+    """A one-layer chain table (every pointer a plausible aligned address that the host checks never dereference) changed by
+    `mutate`; returns mmdeer_chain's return code and message."""
+    import ctypes as C
+    lib = _lib.load()
+    A = 1 << 20
+    a = _lib.ChainArgs()
+    a.X, a.ldx, a.K0, a.rows, a.nseg = A, 256, 256, 64, 1
+    s = a.seg[0]
+    s.W, s.N, s.K, s.end_layer, s.nout, s.drop_site, s.mask_scale = A, 256, 256, 1, 256, -1, 1.0
+    mutate(a, A)
+    rc = lib.mmdeer_chain(C.byref(a))
+    return rc, lib.mmdeer_last_error().decode()
+
+
+def _ln(s, A):
+    s.gamma, s.beta, s.xln, s.mean, s.rstd = A, A, A, A, A
+
+
+def _lnb(s, A):
+    s.lnb_gamma, s.lnb_y, s.lnb_mean, s.lnb_rstd, s.lnb_dz, s.lnb_partial = A, A, A, A, A, A
+
+
+def _layers(a, A, n, per_layer):
+    """n single-segment 256-wide layers; per_layer(seg, i) adds vectors / LayerNorms."""
+    a.nseg = n
+    for i in range(n):
+        s = a.seg[i]
+        s.W, s.N, s.K, s.end_layer, s.nout, s.drop_site = A, 256, 256, 1, 256, -1
+        per_layer(s, i)
+
+
+def _segs(a, A, *spec):
+    """Segments (N, K, kin_off, nout_off, end_layer, nout) of one chain."""
+    a.nseg = len(spec)
+    for i, (N, K, kin, nout_off, end, nout) in enumerate(spec):
+        s = a.seg[i]
+        s.W, s.N, s.K, s.kin_off, s.nout_off, s.end_layer, s.nout, s.drop_site = A, N, K, kin, nout_off, end, nout, -1
+
+
+def _wide_ln_layers(a, A):
+    """Three 512-wide Linear + LayerNorm layers (3 x 1536 vector floats) and a 256-wide Linear with a bias: 4864 floats."""
+    _layers(a, A, 4, lambda s, i: None)
+    for i in range(4):
+        s = a.seg[i]
+        s.K, s.bias = 256 if i == 0 else 512, A
+        if i < 3:
+            s.N, s.nout = 512, 512
+            _ln(s, A)
+
+
+CHAIN_REFUSALS = {
+    # name: (mutation, a word of the message)
+    "no_segments": (lambda a, A: setattr(a, "nseg", 0), "segments"),
+    "13_segments": (lambda a, A: setattr(a, "nseg", 13), "segments"),
+    "negative_rows": (lambda a, A: setattr(a, "rows", -1), "rows"),
+    "samples_per_workgroup_24": (lambda a, A: setattr(a, "samples_per_workgroup", 24), "samples_per_workgroup"),
+    "unaligned_X": (lambda a, A: setattr(a, "X", A + 8), "input rows"),
+    "ldx_not_multiple_of_8": (lambda a, A: setattr(a, "ldx", 260), "input rows"),
+    "ldx_below_K0": (lambda a, A: setattr(a, "ldx", 248), "ldx"),
+    "K0_768_on_32_sample_workgroups": (lambda a, A: (setattr(a, "K0", 768), setattr(a, "ldx", 768), setattr(a, "samples_per_workgroup", 32)), "panel"),
+    "unaligned_W": (lambda a, A: setattr(a.seg[0], "W", A + 2), "weights"),
+    "N_96": (lambda a, A: (setattr(a.seg[0], "N", 96), setattr(a.seg[0], "nout", 128)), "unsupported"),
+    "K_320_past_the_panel": (lambda a, A: setattr(a.seg[0], "K", 320), "reads columns"),
+    "K_192_not_instantiated": (lambda a, A: setattr(a.seg[0], "K", 192), "not instantiated"),
+    "K_768_on_32_sample_workgroups": (lambda a, A: (setattr(a, "K0", 512), setattr(a, "ldx", 512), setattr(a, "samples_per_workgroup", 32),
+                                                    setattr(a.seg[0], "K", 768)), "reads columns"),
+    "64_column_tiles_with_K_64": (lambda a, A: (setattr(a.seg[0], "N", 192), setattr(a.seg[0], "K", 64), setattr(a.seg[0], "nout", 192)), "unsupported"),
+    "five_column_tiles": (lambda a, A: (setattr(a.seg[0], "N", 640), setattr(a.seg[0], "nout", 640)), "column tiles"),
+    "negative_kin_off": (lambda a, A: (setattr(a.seg[0], "kin_off", -64), setattr(a.seg[0], "K", 64)), "reads columns"),
+    "kin_off_window_past_the_panel": (lambda a, A: setattr(a.seg[0], "kin_off", 64), "reads columns"),
+    "negative_nout_off": (lambda a, A: setattr(a.seg[0], "nout_off", -64), "output offset"),
+    "nout_off_not_multiple_of_64": (lambda a, A: setattr(a.seg[0], "nout_off", 32), "output offset"),
+    "segment_past_the_layer_width": (lambda a, A: _segs(a, A, (256, 256, 0, 0, 0, 0), (128, 256, 0, 256, 1, 256)), "writes columns"),
+    "nout_past_the_panel": (lambda a, A: (setattr(a.seg[0], "nout_off", 576), setattr(a.seg[0], "nout", 832)), "does not fit"),
+    "drop_shift_32": (lambda a, A: (setattr(a, "dropout_p", 0.1), setattr(a.seg[0], "drop_site", 1), setattr(a.seg[0], "drop_shift", 32)), "drop_shift"),
+    "unaligned_bias": (lambda a, A: setattr(a.seg[0], "bias", A + 4), "bias"),
+    "unaligned_mask": (lambda a, A: (setattr(a.seg[0], "mask_y", A + 2), setattr(a.seg[0], "ld_mask", 256)), "mask"),
+    "mask_col0_not_multiple_of_4": (lambda a, A: (setattr(a.seg[0], "mask_y", A), setattr(a.seg[0], "ld_mask", 512), setattr(a.seg[0], "mask_col0", 2)), "mask"),
+    "ld_mask_below_col0_plus_N": (lambda a, A: (setattr(a.seg[0], "mask_y", A), setattr(a.seg[0], "ld_mask", 256), setattr(a.seg[0], "mask_col0", 4)), "mask columns"),
+    "negative_mask_col0": (lambda a, A: (setattr(a.seg[0], "mask_y", A), setattr(a.seg[0], "ld_mask", 512), setattr(a.seg[0], "mask_col0", -4)), "mask columns"),
+    "unaligned_stash": (lambda a, A: (setattr(a.seg[0], "stash", A + 8), setattr(a.seg[0], "ld_stash", 256)), "stash"),
+    "ld_stash_below_nout": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "ld_stash", 248)), "ld_stash"),
+    "ld_stash_below_the_split_part": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "stash2", A), setattr(a.seg[0], "stash_split", 64),
+                                                    setattr(a.seg[0], "ld_stash", 184)), "ld_stash"),
+    "ld_stash_below_a_LayerNorm_width": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "ld_stash", 128), _ln(a.seg[0], A)), "ld_stash"),
+    "split_without_stash2": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "ld_stash", 256), setattr(a.seg[0], "stash_split", 128)), "split"),
+    "split_not_multiple_of_8": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "stash2", A), setattr(a.seg[0], "ld_stash", 256),
+                                              setattr(a.seg[0], "stash_split", 100)), "split"),
+    "split_at_nout": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "stash2", A), setattr(a.seg[0], "ld_stash", 256),
+                                    setattr(a.seg[0], "stash_split", 256)), "split"),
+    "split_with_a_LayerNorm": (lambda a, A: (setattr(a.seg[0], "stash", A), setattr(a.seg[0], "stash2", A), setattr(a.seg[0], "ld_stash", 256),
+                                             setattr(a.seg[0], "stash_split", 128), _ln(a.seg[0], A)), "stash_split"),
+    "LayerNorm_width_384": (lambda a, A: (_segs(a, A, (384, 256, 0, 0, 1, 384)), _ln(a.seg[0], A)), "LayerNorm width"),
+    "LayerNorm_without_xln": (lambda a, A: (_ln(a.seg[0], A), setattr(a.seg[0], "xln", None)), "LayerNorm"),
+    "LayerNorm_unaligned_gamma": (lambda a, A: (_ln(a.seg[0], A), setattr(a.seg[0], "gamma", A + 4)), "LayerNorm"),
+    "residual_of_another_width": (lambda a, A: (_segs(a, A, (512, 256, 0, 0, 1, 512)), _ln(a.seg[0], A), setattr(a.seg[0], "residual", 1)), "residual"),
+    "LayerNorm_backward_width_384": (lambda a, A: (_segs(a, A, (384, 256, 0, 0, 1, 384)), _lnb(a.seg[0], A)), "LayerNorm backward"),
+    "LayerNorm_backward_without_partial": (lambda a, A: (_lnb(a.seg[0], A), setattr(a.seg[0], "lnb_partial", None)), "LayerNorm backward"),
+    "LayerNorm_backward_unaligned_y": (lambda a, A: (_lnb(a.seg[0], A), setattr(a.seg[0], "lnb_y", A + 8)), "LayerNorm backward"),
+    "res_add_without_a_bypass_copy": (lambda a, A: setattr(a.seg[0], "res_add", 1), "bypass"),
+    "res_dup_on_a_128_wide_segment": (lambda a, A: (_segs(a, A, (128, 256, 0, 0, 1, 128)), setattr(a.seg[0], "res_dup", 1)), "residual epilogue"),
+    "res_dup_in_a_512_wide_layer": (lambda a, A: (_segs(a, A, (256, 256, 0, 0, 1, 512)), setattr(a.seg[0], "res_dup", 1)), "that one segment"),
+    "res_dup_beside_a_second_segment": (lambda a, A: (_segs(a, A, (256, 256, 0, 0, 0, 0), (128, 256, 0, 256, 1, 384)), setattr(a.seg[0], "res_dup", 1)),
+                                        "that one segment"),
+    "res_add_beside_a_second_segment": (lambda a, A: (_segs(a, A, (256, 256, 0, 0, 1, 256), (256, 256, 0, 0, 0, 0), (128, 256, 0, 256, 1, 384)),
+                                                      setattr(a.seg[0], "res_dup", 1), setattr(a.seg[1], "res_add", 1)), "that one segment"),
+    "last_segment_open": (lambda a, A: setattr(a.seg[0], "end_layer", 0), "last segment"),
+    "17_vectors": (lambda a, A: _layers(a, A, 6, lambda s, i: (setattr(s, "bias", A), _ln(s, A) if i < 5 else _lnb(s, A))), "vectors"),
+    "vector_floats_past_4864": (lambda a, A: (_wide_ln_layers(a, A), setattr(a.seg[3], "N", 512), setattr(a.seg[3], "nout", 512)), "floats"),
+}
+
+
+@pytest.mark.parametrize("name", list(CHAIN_REFUSALS))
+def test_layer_chain_refuses_with_a_message(name):
+    """Every documented limit of mmdeer_chain (include/mmdeer.h) is checked on the host before a launch: the call returns -1 and the
+    message names what is wrong.  Every table here is refused by those checks, so no call reaches a device (the pointers are fake);
+    tables at the limits that must be accepted run with real buffers in test_gpu_chain_routes.py."""
+    mutate, word = CHAIN_REFUSALS[name]
+    rc, msg = _chain_refusal(mutate)
+    assert rc == -1 and word in msg, (name, rc, msg)
+
+
+def test_repack_checks_every_job_before_it_launches():
+    """mmdeer_repack splits more than 64 jobs over several launches; a bad job in a later launch is refused before the first launch
+    (no GPU here: had the first 64 jobs launched, the message would be the launch's)."""
+    lib = _lib.load()
+    A = 1 << 20
+    j = (_lib.RepackJob * 70)()
+    for i in range(70):
+        j[i].src, j[i].dst, j[i].ld_src, j[i].rows, j[i].cols, j[i].cols_valid, j[i].layout = A, A, 64, 16, 64, 64, 1
+    j[66].rows = 8
+    assert lib.mmdeer_repack(j, 70, None) == -1 and b"jobs 64" in lib.mmdeer_last_error()
+    j[66].rows = 16
+    for field, bad, word in (("ld_src", 32, b"ld_src"), ("cols_valid", -8, b"ld_src"), ("dst_col", 8, b"does not fit")):
+        j[66].layout, j[66].ld_dst = 0, 64
+        setattr(j[66], field, bad)
+        assert lib.mmdeer_repack(j, 70, None) == -1 and word in lib.mmdeer_last_error(), field
+        j[66].ld_src, j[66].cols_valid, j[66].dst_col, j[66].layout, j[66].ld_dst = 64, 64, 0, 1, 0
+
+
 def test_frag_images_job_table_on_the_host():
     """mmdeer/chainops.py: FragImages lays its images out in one buffer and describes them to mmdeer_repack -- offsets, shapes, sub-images
     and the refusals are host logic (no launch here)."""

@@ -1669,18 +1669,28 @@ int mmdeer_chain_workgroups(int rows, int samples_per_workgroup) {
 
 int mmdeer_repack(const mmdeer_repack_job* jobs, int n, void* stream) {
   MMDEER_CHECK(n >= 0 && (n == 0 || jobs), "mmdeer_repack: jobs");
-  for (int base = 0; base < n; base += REPACK_MAX) {
-    RepackTable t{};
-    for (int j = base; j < n && j < base + REPACK_MAX; ++j) {
-      const mmdeer_repack_job& s = jobs[j];
-      RepackJob& J = t.job[t.njobs++];
-      J.src = reinterpret_cast<const bf16_t*>(s.src); J.dst = reinterpret_cast<bf16_t*>(s.dst);
-      J.ld_src = s.ld_src; J.rows = s.rows; J.cols = s.cols; J.cols_valid = s.cols_valid; J.transpose = s.transpose;
-      MMDEER_CHECK(s.layout == 0 || s.layout == 1, "mmdeer_repack: job %d layout", j);
-      J.layout = s.layout; J.ld_dst = s.ld_dst; J.dst_col = s.dst_col;
-    }
-    TRY(launch_repack(t, (hipStream_t)stream));
+  // REPACK_MAX jobs per launch; every job is checked before the first launch, so that a refused call writes nothing
+  std::vector<RepackTable> tabs((n + REPACK_MAX - 1) / REPACK_MAX);
+  for (int j = 0; j < n; ++j) {
+    const mmdeer_repack_job& s = jobs[j];
+    RepackTable& t = tabs[j / REPACK_MAX];
+    RepackJob& J = t.job[t.njobs++];
+    J.src = reinterpret_cast<const bf16_t*>(s.src); J.dst = reinterpret_cast<bf16_t*>(s.dst);
+    J.ld_src = s.ld_src; J.rows = s.rows; J.cols = s.cols; J.cols_valid = s.cols_valid; J.transpose = s.transpose;
+    MMDEER_CHECK(s.layout == 0 || s.layout == 1, "mmdeer_repack: job %d layout", j);
+    MMDEER_CHECK(s.cols_valid >= 0 && s.ld_src >= s.cols_valid, "mmdeer_repack: job %d: ld_src = %d is shorter than cols_valid = %d", j, s.ld_src, s.cols_valid);
+    MMDEER_CHECK(s.layout == 1 || (s.dst_col >= 0 && s.ld_dst >= s.dst_col + (s.transpose ? s.rows : s.cols)),
+                 "mmdeer_repack: job %d: a row-major image at column %d does not fit ld_dst = %d", j, s.dst_col, s.ld_dst);
+    J.layout = s.layout; J.ld_dst = s.ld_dst; J.dst_col = s.dst_col;
   }
+  for (size_t b = 0; b < tabs.size(); ++b) {
+    if (check_repack(tabs[b]) < 0) {
+      char msg[512];
+      snprintf(msg, sizeof msg, "%s", mmdeer_last_error());
+      MMDEER_CHECK(false, "mmdeer_repack: jobs %d..: %s", (int)b * REPACK_MAX, msg);
+    }
+  }
+  for (RepackTable& t : tabs) TRY(launch_repack(t, (hipStream_t)stream));
   return 0;
 }
 

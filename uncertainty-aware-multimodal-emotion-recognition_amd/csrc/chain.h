@@ -7,9 +7,7 @@
 
 namespace mmdeer {
 
-constexpr int CHAIN_MAX_SEGS = 12;
-constexpr int CHAIN_MAX_TILES = 24;      // output-column tiles of all segments
-constexpr int CHAIN_MAX_ENDS = 8;        // layers
+constexpr int CHAIN_MAX_SEGS = 12;       // segments, and so layers (the weight stream has no limit of its own on tiles or layers)
 constexpr int CHAIN_MAX_VECS = 16;       // bias / gamma / beta vectors
 constexpr int CHAIN_VEC_FLOATS = 4864;   // LDS floats for every bias / gamma / beta of a chain
 
@@ -151,6 +149,7 @@ struct RepackJob {
 };
 constexpr int REPACK_MAX = 64;
 struct RepackTable { int njobs; int pad_; RepackJob job[REPACK_MAX]; };
+int check_repack(RepackTable& t);      // validates the jobs and places them on the grid: granules of the launch, or -1
 int launch_repack(RepackTable& t, hipStream_t s);
 
 void chain_seg_defaults(ChainSeg& s);

@@ -1077,9 +1077,8 @@ __global__ __launch_bounds__(256) void repack_kernel(const RepackTable t) {
 }
 }  // namespace
 
-int launch_repack(RepackTable& t, hipStream_t s) {
+int check_repack(RepackTable& t) {
   MMDEER_CHECK(t.njobs >= 0 && t.njobs <= REPACK_MAX, "repack: too many jobs (%d)", t.njobs);
-  if (t.njobs == 0) return 0;
   int g = 0;
   for (int m = 0; m < t.njobs; ++m) {
     RepackJob& J = t.job[m];
@@ -1091,6 +1090,12 @@ int launch_repack(RepackTable& t, hipStream_t s) {
     J.gstart = g;
     g += (R * (Cn >> 3) + 255) / 256 * 256;        // every job starts a block
   }
+  return g;
+}
+
+int launch_repack(RepackTable& t, hipStream_t s) {
+  const int g = check_repack(t);
+  if (g <= 0) return g;
   hipLaunchKernelGGL(repack_kernel, dim3((g + 255) / 256), dim3(256), 0, s, t);
   MMDEER_HIP(hipGetLastError());
   return 0;
@@ -1112,6 +1117,7 @@ int launch_chain(const ChainArgs& a, hipStream_t stream) {
                  "chain: NIG head: pointers must be 16-byte aligned");
   } else {
     MMDEER_CHECK(a.X && ((uintptr_t)a.X % 16) == 0 && a.ldx % 8 == 0, "chain: input rows must be 16-byte aligned");
+    MMDEER_CHECK(a.ldx >= a.K0, "chain: ldx = %d is shorter than the input width K0 = %d", a.ldx, a.K0);
   }
   MMDEER_CHECK(a.B > 0, "chain: empty batch");
   MMDEER_CHECK(a.groups == 1 || a.groups == 2, "chain: groups must be 1 or 2");
@@ -1150,15 +1156,17 @@ int launch_chain(const ChainArgs& a, hipStream_t stream) {
     MMDEER_CHECK(s.N > 0 && s.N % 64 == 0 && s.K > 0 && s.K % 64 == 0 && (s.N % 128 == 0 || s.K % 128 == 0),
                  "chain: segment %d has unsupported N = %d, K = %d", i, s.N, s.K);
     MMDEER_CHECK(!s.in_aux || a.aux_video, "chain: segment %d reads a second input panel the chain does not have", i);
-    MMDEER_CHECK(s.kin_off % 64 == 0 && s.kin_off + s.K <= (s.in_aux ? 384 : width_in), "chain: segment %d reads columns [%d, %d) of a %d-wide panel", i,
+    MMDEER_CHECK(s.kin_off >= 0 && s.kin_off % 64 == 0 && s.kin_off + s.K <= (s.in_aux ? 384 : width_in), "chain: segment %d reads columns [%d, %d) of a %d-wide panel", i,
                  s.kin_off, s.kin_off + s.K, s.in_aux ? 384 : width_in);
     MMDEER_CHECK(s.row_group == 0 || (s.row_group == 1 && s.fold_groups == 0 && blocks_in == ts), "chain: segment %d row group", i);
-    MMDEER_CHECK(s.nout_off % 64 == 0, "chain: segment %d output offset", i);
+    MMDEER_CHECK(s.nout_off >= 0 && s.nout_off % 64 == 0, "chain: segment %d output offset", i);
+    MMDEER_CHECK(s.drop_shift >= 0 && s.drop_shift < 32, "chain: segment %d drop_shift = %d", i, s.drop_shift);
     MMDEER_CHECK(!s.bias || ((uintptr_t)s.bias % 16) == 0, "chain: segment %d bias alignment", i);
     const int mblocks = s.in_aux ? ts : s.mblocks ? s.mblocks : blocks_in;
     layer_has_group1 = layer_has_group1 || s.row_group == 1;
     MMDEER_CHECK(mblocks <= blocks_in && (mblocks == ts || mblocks == 2 * ts), "chain: segment %d m-blocks", i);
-    MMDEER_CHECK(nvec + 3 <= CHAIN_MAX_VECS, "chain: too many bias / gamma / beta vectors");
+    const int seg_vecs = (s.bias ? 1 : 0) + (!s.end_layer ? 0 : s.lnb_gamma ? 1 : s.gamma ? 2 : 0);
+    MMDEER_CHECK(nvec + seg_vecs <= CHAIN_MAX_VECS, "chain: more than %d bias / gamma / beta vectors", CHAIN_MAX_VECS);
     const int vec_off = s.bias ? add_vec(s.bias, s.N) : 0;
     const int kb = s.N % 128 != 0, ntl = kb ? s.N / 64 : s.N / 128, nkt = s.K / 64;
     MMDEER_CHECK(ntl <= 4, "chain: segment %d has too many column tiles", i);
@@ -1178,6 +1186,8 @@ int launch_chain(const ChainArgs& a, hipStream_t stream) {
     td.has_bias = s.bias != nullptr;
     td.mask_y = s.mask_y; td.ld_mask = s.ld_mask; td.mask_col0 = s.mask_col0; td.mask_scale = s.mask_scale;
     MMDEER_CHECK(!s.mask_y || (((uintptr_t)s.mask_y % 8) == 0 && s.ld_mask % 4 == 0 && s.mask_col0 % 4 == 0), "chain: segment %d mask alignment", i);
+    MMDEER_CHECK(!s.mask_y || (s.mask_col0 >= 0 && s.ld_mask >= s.mask_col0 + s.N), "chain: segment %d reads mask columns [%d, %d) of rows of ld_mask = %d",
+                 i, s.mask_col0, s.mask_col0 + s.N, s.ld_mask);
     if (s.end_layer) {
       const int blocks_out = s.fold_groups == 1 ? blocks_in / 2 : (s.fold_groups == 2 || layer_has_group1) ? blocks_in * 2 : blocks_in;
       layer_has_group1 = false;
@@ -1185,7 +1195,20 @@ int launch_chain(const ChainArgs& a, hipStream_t stream) {
       MMDEER_CHECK(s.fold_groups != 2 || (blocks_in == ts && s.nout_off == 0 && s.N == 2 * s.nout && s.nout % 64 == 0),
                    "chain: segment %d unfolds: one row group, N = 2 x the panel width", i);
       MMDEER_CHECK(s.nout % 64 == 0 && s.nout * blocks_out <= pan_cols * ts, "chain: layer ending at segment %d does not fit the panel", i);
+      for (int t = layer_first_seg; t <= i; ++t)     // (folded segments place their columns by a rule of their own)
+        MMDEER_CHECK(a.seg[t].fold_groups != 0 || a.seg[t].nout_off + a.seg[t].N <= s.nout, "chain: segment %d writes columns [%d, %d) of a %d-wide panel",
+                     t, a.seg[t].nout_off, a.seg[t].nout_off + a.seg[t].N, s.nout);
+      // a residual epilogue owns its layer: the bypass copy of res_dup is columns [256, 512) of the output panel, and the next layer
+      // takes width_in_dup from this (the last) segment
+      for (int t = layer_first_seg; t <= i; ++t)
+        MMDEER_CHECK(!(a.seg[t].res_add || a.seg[t].res_dup) || (layer_first_seg == i && s.nout == 256),
+                     "chain: segment %d: a residual epilogue needs a 256-wide layer of that one segment", t);
       MMDEER_CHECK(!s.stash || (((uintptr_t)s.stash % 16) == 0 && s.ld_stash % 8 == 0), "chain: segment %d stash alignment", i);
+      MMDEER_CHECK(!s.stash_split || (s.stash && !s.gamma && !s.lnb_gamma), "chain: segment %d: stash_split needs a plain stash (no LayerNorm)", i);
+      {
+        const int hi = s.nout - s.stash_split, stored = s.stash_split > 0 ? (s.stash_split > hi ? s.stash_split : hi) : s.nout;
+        MMDEER_CHECK(!s.stash || s.ld_stash >= stored, "chain: segment %d: ld_stash = %d is shorter than the %d stored columns", i, s.ld_stash, stored);
+      }
       ChainEndK& e = k.rec[i].end;
       e.stash = s.stash; e.ld_stash = s.ld_stash; e.nout = s.nout;
       if (s.lnb_gamma) {
