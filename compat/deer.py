@@ -1,5 +1,7 @@
 """`from deer import test_deer_implementation` (run_multimodal_deer.py:76; src/models/deer.py).  DEERLoss here is the
-reference's loss variant 1 (deer.py:111-195); the DEER head itself is part of mmdeer.model.MultimodalDEER."""
+reference's loss variant 1 (deer.py:111-195); DEERLayer and MultiDimensionalDEER are the head as modules of its own
+(mmdeer/head.py), and the same head is part of mmdeer.model.MultimodalDEER."""
+from mmdeer.head import DEERLayer, MultiDimensionalDEER  # noqa: F401
 from mmdeer.losses import DEERLossV1 as DEERLoss  # noqa: F401
 from mmdeer.side import CrossModalAttention, ModalityEncoders  # noqa: F401
 

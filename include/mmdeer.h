@@ -508,6 +508,47 @@ typedef struct mmdeer_temporal_pool_args {
 int mmdeer_temporal_pool_fwd(const mmdeer_temporal_pool_args* a);
 int mmdeer_temporal_pool_bwd(const mmdeer_temporal_pool_args* a);
 
+/* ---- the evidence tail as an operator of its own (reference src/models/deer.py:55, 86-98): the last Linear(K -> 4 O) of an
+ * evidence net, the NIG activations and the three uncertainties in ONE launch for G nets side by side, and its backward.
+ * "act" = fp32 when act_f32 != 0, else bf16.  Net g reads columns [g K, (g + 1) K) of x; output column g O + o.
+ *   x        act [B][ld_x]: the activations below the last layer (after ReLU / dropout)
+ *   w        act [G][4 O][K]: row 4 o + c of net g is the reference's weight row 4 o + c (c = 0..3: mu, nu^, alpha^, beta^)
+ *   b        fp32 [G][4 O]
+ *   evid     fp32 [B][G O][4]: the raw evidence x W^T + b, written by the forward and read by the backward
+ *   nig_out  fp32 [7][B][G O]: mu = e0, nu = softplus(e1) + 1e-6, alpha = softplus(e2) + 1, beta = softplus(e3) + 1e-6,
+ *            aleatoric = beta / (alpha - 1), epistemic = beta / (nu (alpha - 1)), total = aleatoric + epistemic; alpha - 1 is
+ *            formed from the rounded fp32 alpha, so it is 0 and the uncertainties inf where e2 < about -17, as in torch
+ *   g_out    backward: the upstream gradients of the seven planes, fp32 [B][G O] each.  A NULL plane is an output the loss does not
+ *            use: its terms are dropped, not multiplied by zero, so a loss on mu, nu, alpha, beta alone has finite gradients
+ *            where alpha - 1 = 0.  Where a given uncertainty plane meets alpha - 1 = 0 the result is inf / nan (no clamping).
+ *   devid    fp32 [B][G O][4], optional: d evidence
+ *   dx       act [B][ld_dx], optional: (devid . W) * ((x > 0) * mask_scale); mask_scale <= 0: no mask factor.  Must not alias x.
+ *   dw, db   fp32 [G][4 O][K], [G][4 O]: overwritten.  Per-part partials folded in index order: no float atomics, two runs give
+ *            identical bits.
+ *   scratch  fp32, at least mmdeer_evidence_tail_scratch(B, G, K, O) elements, 16-byte aligned (backward only)
+ * Accepted: 1 <= G <= 8, 1 <= O <= 8, K a multiple of 8 in [8, 512], ld_x and ld_dx >= G K and multiples of 8 (bf16) / 4 (fp32),
+ * x, w, b, evid, devid, dx, scratch 16-byte aligned, B >= 0.  B = 0 launches nothing; the backward then zero-fills dw and db.
+ * Anything else writes nothing, returns -1 and names the argument in mmdeer_last_error(); all of it is checked on the host
+ * before any HIP runtime call.  mmdeer_evidence_tail_scratch returns -1 for a refused shape. */
+typedef struct mmdeer_evidence_tail_args {
+  const void* x; int32_t ld_x;
+  const void* w;
+  const float* b;
+  float* evid;
+  float* nig_out;
+  const float* g_out[7];
+  float* devid;
+  void* dx; int32_t ld_dx;
+  float* dw; float* db;
+  float* scratch;
+  float mask_scale;
+  int32_t B, G, K, O, act_f32;
+  void* stream;
+} mmdeer_evidence_tail_args;
+long long mmdeer_evidence_tail_scratch(int B, int G, int K, int O);
+int mmdeer_evidence_tail_fwd(const mmdeer_evidence_tail_args* a);
+int mmdeer_evidence_tail_bwd(const mmdeer_evidence_tail_args* a);
+
 /* ---- streaming evaluation statistics (reference src/utils/metrics.py:59-125) ---------------------------
  * pred / target / unc: [B][3] fp32 (unc may be NULL).  acc: device double[3][8], zeroed by the caller before the first
  * batch; every call adds {n, sum p, sum t, sum p^2, sum t^2, sum pt, sum |p-t|, sum (p-t)^2} per emotion dimension over
@@ -810,7 +851,7 @@ int mmdeer_allgather(const void* send, void* recv, long long send_count, int dty
 
 /* sizeof() of an argument struct of this header by its name without the mmdeer_ prefix ("gemm_args", "chain_args", "chain_seg",
  * "repack_job", "forward_args", "backward_args", "adamw_args", "adamw_flat_args", "stackb_attn_train_args", "stackb_attn_args",
- * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args"); -1 for an unknown name.  A binding in another language checks its
+ * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args", "evidence_tail_args"); -1 for an unknown name.  A binding in another language checks its
  * own layout against it at load time (mmdeer/_lib.py does). */
 long long mmdeer_sizeof(const char* struct_name);
 

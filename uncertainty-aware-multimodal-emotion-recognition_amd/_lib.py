@@ -204,13 +204,24 @@ class TemporalPoolArgs(C.Structure):
     ]
 
 
+class EvidenceTailArgs(C.Structure):
+    """mmdeer_evidence_tail_args (include/mmdeer.h)."""
+    _fields_ = [
+        ("x", c_void_p), ("ld_x", c_int), ("w", c_void_p), ("b", c_void_p), ("evid", c_void_p), ("nig_out", c_void_p),
+        ("g_out", c_void_p * 7), ("devid", c_void_p), ("dx", c_void_p), ("ld_dx", c_int), ("dw", c_void_p), ("db", c_void_p),
+        ("scratch", c_void_p), ("mask_scale", C.c_float), ("B", c_int), ("G", c_int), ("K", c_int), ("O", c_int), ("act_f32", c_int),
+        ("stream", c_void_p),
+    ]
+
+
 TEMPORAL_POOL_SCRATCH = 256 * 256   # MMDEER_TEMPORAL_POOL_SCRATCH
 
 # ctypes mirror of every argument struct, by the name mmdeer_sizeof() knows it under
 STRUCTS = {"gemm_args": GemmArgs, "chain_args": ChainArgs, "chain_seg": ChainSeg, "repack_job": RepackJob, "forward_args": ForwardArgs,
            "backward_args": BackwardArgs, "adamw_args": AdamWArgs, "adamw_flat_args": AdamWFlatArgs, "stackb_attn_train_args": StackBAttnTrainArgs,
            "stackb_attn_args": StackBAttnArgs, "stackb_forward_args": StackBForwardArgs, "stackb_weights": StackBWeights,
-           "softmax_mix_args": SoftmaxMixArgs, "lstm_seq_args": LstmSeqArgs, "temporal_pool_args": TemporalPoolArgs}
+           "softmax_mix_args": SoftmaxMixArgs, "lstm_seq_args": LstmSeqArgs, "temporal_pool_args": TemporalPoolArgs,
+           "evidence_tail_args": EvidenceTailArgs}
 
 # every symbol include/mmdeer.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -278,6 +289,9 @@ SYMBOLS = [
     ("mmdeer_lstm_seq_bwd", c_int, [C.POINTER(LstmSeqArgs)]),
     ("mmdeer_temporal_pool_fwd", c_int, [C.POINTER(TemporalPoolArgs)]),
     ("mmdeer_temporal_pool_bwd", c_int, [C.POINTER(TemporalPoolArgs)]),
+    ("mmdeer_evidence_tail_scratch", C.c_longlong, [c_int, c_int, c_int, c_int]),
+    ("mmdeer_evidence_tail_fwd", c_int, [C.POINTER(EvidenceTailArgs)]),
+    ("mmdeer_evidence_tail_bwd", c_int, [C.POINTER(EvidenceTailArgs)]),
     ("mmdeer_softmax_mix_fwd", c_int, [C.POINTER(SoftmaxMixArgs)]),
     ("mmdeer_softmax_mix_bwd", c_int, [C.POINTER(SoftmaxMixArgs)]),
     ("mmdeer_outer_fwd", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
