@@ -72,7 +72,7 @@ size_t mmdeer_workspace_bytes(int batch, int compute_f32);
  * by the workspaces of every batch size; written by mmdeer_forward(repack = 1), mmdeer_pack_weights and mmdeer_adamw_step. */
 size_t mmdeer_weights_bytes(int compute_f32);
 
-/* Launch-plan options (csrc/options.h): integer switches that select between kernel plans with IDENTICAL results up to
+/* Launch-plan options (csrc/options.inc): integer switches that select between kernel plans with IDENTICAL results up to
  * rounding (A/B measurements, debugging); read at every call, so a process may change them between calls.
  *   fused_attn (1)     0: unfused in_proj GEMM + attention kernels also in bf16 mode
  *   qkv_recompute (1)  0: the fused forward stores q|k|v for the backward instead of recomputing the head tiles
@@ -108,14 +108,18 @@ const char* mmdeer_trace_label(int i);
 
 /* Byte offset of a named buffer inside the workspace of (batch, compute_f32), -1 for an unknown name: lets a test read the
  * activations and activation-gradients a step left behind (tests/test_gpu_bf16_layers.py checks every kernel of the bench
- * configuration on its own stored inputs).  Names (csrc/api.hip Layout; act dtype unless noted): audio_pad [B,128] bf16,
+ * configuration on its own stored inputs).  Names: every workspace field of csrc/layout.inc, the one list the layout is made of
+ * (act dtype unless noted): audio_pad [B,128] bf16,
  * avin avv [2B,256], cat [B,512], y_a2 av [B,256], xtok [2B,512], qkv [2B,1536], obar pool y_t3 tri y_o1 fused [B,512],
- * h1 h2 [B,256], e1 [B,384], e2 [B,192], probs [B,8,4] f32, evid [B,3,4] f32, mean_* rstd_* [B] f32, and the gradients
- * dz2 de1 dh2 dh1 dfused dz_o1 dtri dz_t3 dpool dobar dqkv dxtok dav dz_a2 dcats davv davin of the same shapes. */
+ * h1 h2 [B,256], e1 [B,384], e2 [B,192], probs [B,8,4] f32, evid [B,3,4] f32, stats f32, mean_* rstd_* [B] f32, the gradients
+ * dz2 de1 dh2 dh1 dfused dz_o1 dtri dz_t3 dpool dobar dqkv dxtok dav dz_a2 dcats davv davin of the same shapes, the fp32 partial
+ * slabs part_ln_o1 part_ln_t3 part_ln_a2 part_w3 part_b3 and the split-K slab. */
 long long mmdeer_workspace_offset(int batch, int compute_f32, const char* name);
 /* The same for the packed-parameter buffer (`weights`): wpack / wtpack (compute-dtype matrices and their transposes at the
  * flat element offsets of mmdeer_param_offset), vpack (fp32 vectors, same offsets), wa_pad ([256][128] bf16 audio weight),
- * wqkv_hm (head-major in_proj image of the fused kernels).  bench.py launches the roofline kernel on the step's operands. */
+ * wqkv_hm (head-major in_proj image of the fused kernels), wscratch (the optimiser step's partials) and, empty with compute_f32,
+ * wfpack / wtfpack (fragment-major images of W / W^T at the flat offsets) and wa_frag (that of wa_pad): every weights field of
+ * csrc/layout.inc.  bench.py launches the roofline kernel on the step's operands. */
 long long mmdeer_weights_offset(int compute_f32, const char* name);
 
 typedef struct mmdeer_loss_cfg {

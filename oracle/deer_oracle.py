@@ -533,7 +533,7 @@ def to_params(state: Dict[str, "torch.Tensor"], dtype=torch.float32, requires_gr
 #   * tri_fused.hip: q, k rounded to bf16 for the score products only (the backward multiplies by the unrounded
 #     accumulators); v stays fp32; the token-pooled context obar and dqkv are stored bf16; probabilities fp32;
 #   * nig.hip: the evidence (64 -> 4 layer output) and everything after it fp32; dz2 bf16;
-#   * api.hip pack: every weight MATRIX bf16 (gradients of the fp32 master parameters are NOT rounded: the weight-gradient
+#   * stackc.hip pack: every weight MATRIX bf16 (gradients of the fp32 master parameters are NOT rounded: the weight-gradient
 #     GEMMs accumulate bf16 operands in fp32 slabs); biases and LayerNorm vectors fp32.
 def _bf16_round(x):
     return x.to(torch.bfloat16).to(x.dtype)
@@ -603,7 +603,7 @@ def _drop_k(x, mask, p):
 
 def model_forward_bf16(P, audio, video, text, masks=None, p=0.3, heads=8):
     """model_forward with the bf16 storage points of the HIP path (see the block comment above); fp32 tensors in, fp32 out.
-    Follows the launch plan of csrc/api.hip:mmdeer_forward (F1 .. F18), e.g. the token mean BEFORE the attention out_proj."""
+    Follows the launch plan of csrc/stackc.hip:mmdeer_forward (F1 .. F18), e.g. the token mean BEFORE the attention out_proj."""
     masks = masks or {}
     W = lambda name: _qf(P[name])
     lin = lambda x, pre: x @ W(pre + ".weight").t() + P[pre + ".bias"]
@@ -671,7 +671,7 @@ def model_forward_bf16(P, audio, video, text, masks=None, p=0.3, heads=8):
 
 
 # --------------------------------------------------------------------------- kernel-level restatements (bf16 path)
-# One function per launch of csrc/api.hip's plan, each taking the tensors THAT launch reads (as fp32 tensors holding
+# One function per launch of csrc/stackc.hip's plan, each taking the tensors THAT launch reads (as fp32 tensors holding
 # bf16-representable values where the kernel reads bf16) and returning what it stores.  tests/test_gpu_bf16_layers.py feeds
 # every launch of a full-size step its own stored inputs ("teacher forcing"), so the chaotic growth of rounding differences
 # through the chain (see model_forward_bf16's callers) cannot hide an error inside one kernel.

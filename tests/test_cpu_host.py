@@ -280,6 +280,41 @@ def test_workspace_bytes_grow_with_batch():
     assert w2 < 1 << 30
 
 
+def test_layout_lookups_answer_every_field_of_the_one_list():
+    """csrc/layout.inc is the one list struct Layout, make_layout() and both name look-ups are made of: every field is answered, on a
+    256-byte boundary, in list order (equal offsets only behind an empty field: wfpack, wtfpack and wa_frag with compute_f32, at the
+    end of the buffer), inside the buffer; a name of the other buffer, or no field's name, is refused."""
+    import re
+    lib = _lib.load()
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uncertainty-aware-multimodal-emotion-recognition_amd", "csrc")
+    text = open(os.path.join(root, "layout.inc")).read()
+    rows = re.findall(r"\bX\(([WS]),\s*(ACT|BF16|F32),\s*(\w+),\s*[^(),]+,\s*([01])\)", text)
+    assert len(rows) == len(re.findall(r"\bX\([WS],", text)) and len({n for _, _, n, _ in rows}) == len(rows) >= 50
+    for f32 in (0, 1):
+        for batch in (0, 1, 7, 512, 4096, 4097, 8192, 16384):
+            for buf in "WS":
+                if buf == "W":
+                    total, look = lib.mmdeer_weights_bytes(f32), lambda n: lib.mmdeer_weights_offset(f32, n.encode())
+                else:
+                    total, look = lib.mmdeer_workspace_bytes(batch, f32), lambda n: lib.mmdeer_workspace_offset(batch, f32, n.encode())
+                prev, prev_empty = -1, False
+                for b, _, name, bf16_only in rows:
+                    if b != buf:
+                        assert look(name) == -1, name
+                        continue
+                    off = look(name)
+                    assert off >= 0 and off % 256 == 0 and off <= total, (name, off)
+                    assert off > prev or (off == prev and prev_empty), (name, off, prev)
+                    prev, prev_empty = off, bool(f32 and bf16_only == "1")
+                    assert prev_empty or off < total, name
+                assert look("no_such_field") == -1
+    assert lib.mmdeer_workspace_offset(-1, 0, b"slab") == -1
+    # the figures of the layout before the list existed
+    assert (lib.mmdeer_weights_bytes(0), lib.mmdeer_weights_bytes(1)) == (36593664, 36528128)
+    assert (lib.mmdeer_workspace_bytes(4096, 0), lib.mmdeer_workspace_bytes(4096, 1)) == (267252736, 436073472)
+    assert (lib.mmdeer_workspace_offset(4096, 0, b"slab"), lib.mmdeer_workspace_offset(4096, 1, b"slab")) == (174216192, 343036928)
+
+
 def test_state_dict_names_follow_the_reference(golden_dir):
     m = MultimodalDEER(ModelConfig())
     sd = m.state_dict()
@@ -512,14 +547,23 @@ def test_compat_modules_resolve_by_bare_name():
 
 
 def test_option_table_matches_the_enum_order():
-    """csrc/options.h (enum OptId) and the name table of csrc/api.hip are two lists that must stay in the same order: an option
-    looked up by id would otherwise read its neighbour's value (it happened once: dw_tile read chain_max)."""
+    """enum OptId and the table of names, defaults and ranges are generated from ONE list, csrc/options.inc, so their order cannot part
+    (it happened once with two lists: dw_tile read chain_max).  What is left to hold: every row's name is its id without OPT_, in
+    lower case, and the library enumerates exactly the rows of that list, in order, with NULL past the end."""
     import os
     import re
+    from mmdeer import _lib
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uncertainty-aware-multimodal-emotion-recognition_amd", "csrc")
-    enum = [e.lower() for e in re.findall(r"^\s+OPT_([A-Z0-9_]+)\b", open(os.path.join(root, "options.h")).read(), re.M) if e != "COUNT"]
-    table = re.findall(r'\{"([a-z0-9_]+)",\s*-?\d+,', open(os.path.join(root, "api.hip")).read())
-    assert enum == table and len(enum) >= 15
+    text = open(os.path.join(root, "options.inc")).read()
+    rows = re.findall(r'^X\(OPT_([A-Z0-9_]+),\s*"([a-z0-9_]+)",\s*(-?\d+),', text, re.M)
+    assert len(rows) == len(re.findall(r"^X\(", text, re.M)) >= 15          # every row is of that form
+    assert [i.lower() for i, _, _ in rows] == [n for _, n, _ in rows]
+    lib = _lib.load()
+    assert [lib.mmdeer_option_name(i) for i in range(len(rows))] == [n.encode() for _, n, _ in rows]
+    assert lib.mmdeer_option_name(len(rows)) is None and lib.mmdeer_option_name(-1) is None
+    for text_of in ("options.h", "options.hip"):                              # no second list of ids or names anywhere
+        src = open(os.path.join(root, text_of)).read()
+        assert '#include "options.inc"' in src and not re.search(r"\bOPT_(?!COUNT\b)[A-Z0-9_]+\s*[,=]", src)
 
 
 def test_set_option_refuses_values_outside_the_range():

@@ -1,6 +1,6 @@
 """mmdeer_gemm on every kernel route behind it, called through the C ABI (include/mmdeer.h).
 
-One call selects one of about a dozen kernels (csrc/gemm.hip: launch_gemm_group, pick_tile in api.hip, the gemm_dispatch_*
+One call selects one of about a dozen kernels (csrc/gemm.hip: launch_gemm_group, pick_tile in gemm.hip, the gemm_dispatch_*
 functions).  ROUTES below names each route with the arguments and launch-plan options that select it, and shapes that land
 on it with ragged M and N, a ragged last K-tile and padded leading dimensions.  Every result is compared element-wise with a
 float64 product of the operands as the kernel sees them, under an error bound derived from the accumulation (C_BOUND).

@@ -9,16 +9,16 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "uncertainty-aware-multimodal-emotion-recognition_amd", "csrc", "chain.hip")
+sys.path.insert(0, ROOT)
+from mmdeer import build  # noqa: E402  (the flags the shipped library is compiled with)
 LIMITS = {"chain_kernel_s16": 224, "chain_kernel_s32": 240, "chain_kernel_s16_d2": 240, "chain_kernel_s16_d8": 192}
 
 
 def device_asm() -> str:
-    hipcc = "/opt/rocm/bin/hipcc"
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "chain.s")
-        subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-kernarg-preload-count=16", "-S",
-                        "--cuda-device-only", "-o", out, SRC], check=True, capture_output=True)
+        subprocess.run([build._hipcc(), *build.FLAGS, "-S", "--cuda-device-only", "-o", out, os.path.join(build.CSRC, "chain.hip")],
+                       check=True, capture_output=True)
         return open(out).read()
 
 

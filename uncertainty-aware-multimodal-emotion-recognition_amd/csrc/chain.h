@@ -98,7 +98,7 @@ struct ChainNigF {
   float* wstats;           // [ceil(B / 16)][3][NIG_NSTAT], written iff targets
 };
 
-// Host-side description of a chain (api.hip fills it; launch_chain() validates it and derives the kernel's tables).
+// Host-side description of a chain (stackc.hip, stackb.hip and mmdeer_chain fill it; launch_chain() validates it and derives the kernel's tables).
 struct ChainArgs {
   const bf16_t* X;         // chain input [rows][ldx]
   int ldx, K0;             // leading dimension, width (<= 512, multiple of 64)

@@ -34,7 +34,7 @@
 // 39-44 through an LDS-DMA ring) --; for 256-wide layers the layer ends: decode of the next table record ~1.0k cycles, barrier skew
 // between the two waves of a SIMD ~1.5k, LayerNorm ~1.9k, and the restart of the 4-deep ring behind every layer end (eight stages in
 // 4.5k cycles instead of 2.6k).  One workgroup per 16 rows also means the launch only pays while the chip holds all workgroups at
-// once: api.hip uses 16-sample workgroups for B <= 4096, 32-sample workgroups up to 8192 and the separate launches above.
+// once: stackc.hip uses 16-sample workgroups for B <= 4096, 32-sample workgroups up to 8192 and the separate launches above.
 // Measured dead ends (rounds 3-4): the LDS-DMA weight ring (36-45 B/clk) and a seventh slot of it; re-reading the activation fragments
 // from LDS at every stage while the weights also went through LDS; two stages per barrier; the segment tables from the kernel
 // arguments by dependent scalar loads record after record (~1000 cycles each); weights into registers from the ROW-MAJOR copy

@@ -73,6 +73,8 @@ struct DropCtx {
   float scale;                // 1 / (1 - p)
   const unsigned long long* offset_dev;   // optional device-resident counter added to `offset` (HIP-graph replays)
 };
+// host side: the context of dropout probability p (api.hip)
+DropCtx make_drop(float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev = nullptr);
 
 __host__ __device__ __forceinline__ unsigned drop_key(const DropCtx& d, int site) {
   unsigned long long off = d.offset;
@@ -159,5 +161,6 @@ void set_error(const char* fmt, ...);
       return -1;                                                                   \
     }                                                                              \
   } while (0)
+#define TRY(x) do { if ((x) != 0) return -1; } while (0)   // pass a failed launcher's -1 on (its message is set)
 
 }  // namespace mmdeer

@@ -71,8 +71,10 @@ void gemm_problem_defaults(GemmProblem& p);
 int launch_gemm_ln(GemmGroup& g, const void* Y, const float* gamma, const float* beta, void* xln, float* out32, float* mean,
                    float* rstd, hipStream_t s);
 
-// tile policy of the executors (api.hip): the MMDEER_TILE override, else by tile count and operand layout
+// tile policy of the executors (gemm.hip): option "tile" when set, else by tile count and operand layout
 GemmTile pick_tile(const GemmGroup& g);
+// target number of K-tiles per split-K slice of a weight-gradient problem (gemm.hip)
+int ksteps_target(int compute_f32);
 
 // K-tile count of a problem for the given compute dtype (64 bf16 / 32 fp32 elements of K per tile)
 inline int gemm_ktiles(int K, int compute_f32) { const int kt = compute_f32 ? 32 : 64; return (K + kt - 1) / kt; }

@@ -17,15 +17,53 @@ int gemm_dispatch_tt256x128(const GemmGroup& g, int total, hipStream_t s);
 int gemm_dispatch_tt128k2(const GemmGroup& g, int total, hipStream_t s);
 int gemm_dispatch_nt256(const GemmGroup& g, int total, int bn, hipStream_t s);
 
-namespace {
-// launch-plan options (options.h): "xcd" = 0 no XCD renumbering; "nt192" = 0 the forward 256-row kernel keeps 256-column
-// tiles; "nt128" = 0 never trade two 128x64 workgroups per CU for one 8-wave 128x128 workgroup; "glds" = 0 forces the
-// register-staged kernel for NT problems (A/B comparison, debugging)
-int env_xcd() { return opt(OPT_XCD); }
-int env_nt192() { return opt(OPT_NT192); }
-int env_nt128() { return opt(OPT_NT128); }
-int env_glds() { return opt(OPT_GLDS); }
-}  // namespace
+// target number of K-tiles per split-K slice of a weight-gradient problem (option "ksteps" overrides)
+// in units of 64 batch rows.  Defaults: bf16 (256x256 LDS-DMA kernel) 16 = 1024 rows per slice -- the slab
+// traffic, 4 B per parameter per slice written and read back, is what limits the slice count; fp32 8.
+int ksteps_target(int f32) {
+  const int v = opt(OPT_KSTEPS);
+  if (v > 0) return v;
+  if (!f32 && opt(OPT_DW_TILE) == 4) return 32;   // 256x128: two K-slices at 4096 rows
+  return f32 ? 8 : 16;
+}
+
+// smallest tile that still gives the chip >= ~2 workgroups per CU; otherwise the largest tile count wins
+// (the Stack C and Stack B executors and mmdeer_gemm / mmdeer_gemm_batch share this policy)
+GemmTile pick_tile(const GemmGroup& g) {
+  const int ft = opt(OPT_TILE);
+  if (ft >= 0 && ft <= 4) return (GemmTile)ft;
+  static const int bm[3] = {64, 128, 128}, bn[3] = {64, 64, 128};
+  long long tiles[3];
+  for (int t = 0; t < 3; ++t) {
+    tiles[t] = 0;
+    for (int i = 0; i < g.nprob; ++i) {
+      const GemmProblem& p = g.p[i];
+      tiles[t] += (long long)((p.M + bm[t] - 1) / bm[t]) * ((p.N + bn[t] - 1) / bn[t]) * p.batch;
+    }
+  }
+  // weight-gradient groups (both operands transposed): the strided loads and the packing LDS store cost the same per
+  // K-tile whatever the tile size, so the largest tile wins; split-K supplies the parallelism
+  if (g.p[0].trans_a) { const int t = opt(OPT_DW_TILE); return (GemmTile)(t < 2 ? 2 : t > 4 ? 4 : t); }   // 256x256 (falls back to 128x128 per sub-group where the kernel does not apply)
+  // bf16: 128x64 and 64x64 run on the LDS-DMA kernel, 128x128 only on the register-staged one (measured on the
+  // trimodal in_proj, 768 tiles of 128x128: 28.5 us against 17 us as 1536 tiles of 128x64)
+  const bool f32 = g.p[0].a_f32 && g.p[0].b_f32;
+  if (f32 && tiles[2] >= 512) return TILE_128x128;
+  if (!f32) {   // big forward problems: 256x256 tiles when they fill most of the chip in one round (in_proj: 192)
+    long long t256 = 0;
+    bool plain = true;
+    for (int i = 0; i < g.nprob; ++i) {
+      const GemmProblem& p = g.p[i];
+      t256 += (long long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.batch;
+      plain = plain && !p.Y && !p.trans_b;
+    }
+    if (plain && t256 >= 160 && t256 <= 256) return TILE_256x256;
+  }
+  // ~one 128x64 tile per CU: the 8-wave 128x64 kernel (launcher) moves 25 % fewer operand bytes than two 64x64
+  // workgroups per CU, and the K loop of those is bound by the CU's vector-memory path
+  if (!f32 && !g.p[0].trans_a && !g.p[0].trans_b && tiles[1] >= 200 && tiles[1] <= 320) return TILE_128x64;
+  if (tiles[1] >= opt(OPT_T128)) return TILE_128x64;   // option "t128": smallest 128x64 tile count that selects that kernel
+  return TILE_64x64;
+}
 
 // the (A mode, B mode) pairs gemm_dispatch_nt / _nx / _tt instantiate (fp32 compute: (F32, F32) only)
 bool gemm_modes_instantiated(int ta, int tb, int compute_f32, int am, int bm) {
@@ -53,9 +91,9 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   MMDEER_CHECK(!ta || tb, "gemm: (trans_a=1, trans_b=0) is not instantiated");
   // the whole group can run on the 256x256 weight-gradient kernel (it alone tolerates padded, half-valid row ends)
   // the weight-gradient DMA kernel on 128x128 / 256x128 tiles (option dw_tile)
-  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && env_glds() && opt(OPT_DW_TILE) == 2;
-  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && env_glds();
-  bool pad256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && env_glds();
+  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && opt(OPT_GLDS) && opt(OPT_DW_TILE) == 2;
+  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && opt(OPT_GLDS);
+  bool pad256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && opt(OPT_GLDS);
   for (int i = 0; i < g.nprob && pad256; ++i) {
     const GemmProblem& q = g.p[i];
     // (the output conditions of the DMA kernel too: a half-valid chunk read by the register-staged fallback would be dropped)
@@ -113,10 +151,10 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
 int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream) {
   static const int bm_of[5] = {64, 128, 128, 256, 256}, bn_of[5] = {64, 64, 128, 256, 128};
   if (prepare_gemm_group(g, compute_f32, tile_req) != 0) return -1;
-  g.xcd_remap = env_xcd();
+  g.xcd_remap = opt(OPT_XCD);
   const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
-  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && env_glds() && opt(OPT_DW_TILE) == 2;
-  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && env_glds();
+  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && opt(OPT_GLDS) && opt(OPT_DW_TILE) == 2;
+  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && opt(OPT_GLDS);
   // One launch per distinct (A mode, B mode) pair: the kernels are specialised on the pair so that their K loop
   // has no data-dependent control flow.  Most groups are homogeneous (one launch).
   // every problem's source-mode pair before the first launch of the group: a refused group writes nothing
@@ -138,7 +176,7 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
     }
     // 256x256 tiles exist only as the LDS-DMA weight-gradient kernel; anything else of such a group runs 128x128
     bool tt256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 &&
-                 env_glds();
+                 opt(OPT_GLDS);
     for (int j = 0; j < sub.nprob && tt256; ++j) {
       const GemmProblem& q = sub.p[j];
       tt256 = q.K % 32 == 0 && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 &&
@@ -146,7 +184,7 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
     }
     // ... and as the LDS-DMA forward kernel (bias / ReLU / dropout epilogue, no mask, no split-K)
     bool nt256 = tile_req == TILE_256x256 && !ta && !tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 &&
-                 env_glds();
+                 opt(OPT_GLDS);
     for (int j = 0; j < sub.nprob && nt256; ++j) {
       const GemmProblem& q = sub.p[j];
       nt256 = q.K % 32 == 0 && q.splitk == 1 && !q.bias_grad && !q.Y && (uintptr_t)q.C % 16 == 0 && q.sC % 8 == 0 &&
@@ -156,14 +194,14 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
     GemmTile tile = (tt256 && dw128) ? TILE_128x128 : (tt256 && dw256x128) ? TILE_256x128 : (tt256 || nt256) ? TILE_256x256 :
                     ((tile_req == TILE_256x256 || tile_req == TILE_256x128) ? (ta ? TILE_128x128 : TILE_128x64) : tile_req);
     // LDS-DMA fast path: bf16 NT problems whose operands are 16-byte aligned, row-contiguous and K % 64 == 0
-    bool glds_ok = !ta && !tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 && env_glds();
+    bool glds_ok = !ta && !tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 && opt(OPT_GLDS);
     for (int j = 0; j < sub.nprob && glds_ok; ++j)
       glds_ok = sub.p[j].K % 64 == 0 && sub.p[j].splitk == 1 && !sub.p[j].bias_grad;
     // These launches are bound by the bytes a CU pulls through its vector-memory path (~40 B/clk of LDS-DMA): when 128x64
     // tiles need two workgroups per CU (in_proj dX: 512 tiles x 576 KB) and 128x128 tiles cover the problems with about one
     // 8-wave workgroup per CU (256 x 768 KB), the square tile moves a third fewer bytes per CU
     bool glds128 = false;
-    if (glds_ok && tile == TILE_128x64 && env_nt128()) {
+    if (glds_ok && tile == TILE_128x64 && opt(OPT_NT128)) {
       long long t64 = 0, t128 = 0;
       bool ok = true;
       for (int j = 0; j < sub.nprob; ++j) {
@@ -176,7 +214,7 @@ int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStrea
       if (glds128) tile = TILE_128x128;
     }
     int BM = bm_of[tile], BN = bn_of[tile];
-    if (nt256 && env_nt192()) {   // 256x192 tiles when they fill the chip in one round and 256x256 tiles do not
+    if (nt256 && opt(OPT_NT192)) {   // 256x192 tiles when they fill the chip in one round and 256x256 tiles do not
       long long t256 = 0, t192 = 0;
       bool ok = true;
       for (int j = 0; j < sub.nprob; ++j) {

@@ -45,8 +45,6 @@ namespace {
 #define KWGSTAMP(which) do {} while (0)
 #endif
 
-int env_nt8() { return opt(OPT_NT8); }   // option "nt8" = 0: never use the 8-wave 128x64 form
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -244,7 +242,7 @@ int gemm_dispatch_nt_glds(const GemmGroup& g, int total, GemmTile tile, hipStrea
     case TILE_64x64: return launch_glds<64, 64, 4, 4>(g, total, s);
     case TILE_128x64:
       // up to ~one workgroup per CU: the 8-wave form (96 KiB ring, one per CU); more tiles: 4 waves, 72 KiB ring, two per CU
-      if (total <= 320 && env_nt8()) return launch_glds<128, 64, 4, 8>(g, total, s);
+      if (total <= 320 && opt(OPT_NT8)) return launch_glds<128, 64, 4, 8>(g, total, s);
       return launch_glds<128, 64, 3, 4>(g, total, s);
     default: return launch_glds<128, 128, 4, 8>(g, total, s);   // one 8-wave workgroup per CU (128 KiB ring), 32x64 per wave
   }

@@ -3,9 +3,11 @@
 #pragma once
 #include "common.h"
 
+struct mmdeer_loss_cfg;   // include/mmdeer.h
+
 namespace mmdeer {
 
-constexpr int NIG_NSTAT = 35;      // per (block, dim): 5 sums + 10 bins x {sum conf, sum err, count}
+constexpr int NIG_NSTAT = 35;     // per (block, dim): 5 sums + 10 bins x {sum conf, sum err, count}
 constexpr int NIG_GLOBAL_STATS = 3 * NIG_NSTAT + 1;   // summed block partials of the three dims + the batch size (exact-global loss)
 constexpr int NIG_LOSS_OUT = 20;   // per dim {total, nll, reg, kl, ece} x 3, cross, total, mean nll, mean reg, mean kl
 
@@ -13,6 +15,7 @@ struct LossCfg {
   float reg_w, kl_w, ece_w, cross_w;   // losses.py:52-53, 239   (0.1, 0.01, 0.05, 0.05)
   float task_w[3];                     // losses.py:256-259      (1, 1, 1)
 };
+LossCfg loss_cfg(const mmdeer_loss_cfg& c);   // the public struct as the kernels take it (api.hip)
 
 constexpr int NIG_ROWS = 64;       // samples per workgroup of the head kernels (4 lanes per sample)
 inline int nig_nblocks(int B) { return B > 0 ? (B + NIG_ROWS - 1) / NIG_ROWS : 1; }

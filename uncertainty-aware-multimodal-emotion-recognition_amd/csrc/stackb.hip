@@ -304,8 +304,6 @@ int run1(const GemmProblem& p, int f32, hipStream_t s) {
   return run(g, f32, s);
 }
 
-#define TRY(x) do { if ((x) != 0) return -1; } while (0)
-
 int stackb_forward(const mmdeer_stackb_forward_args* a) {
   const mmdeer_stackb_weights& w = *a->weights;
   const int B = a->batch, f32 = a->compute_f32 ? 1 : 0, L = w.encoder_layers;
