@@ -575,6 +575,51 @@ int mmdeer_eval_quantile_select(const float* err, const float* unc, long long n,
 int mmdeer_eval_ece_bins(const float* err, const float* unc, long long n, const double* edges, int n_bins, double* bins,
                          void* stream);
 
+/* ---- evaluator statistics (reference src/training/evaluation.py:135-355, 492-530, 578-682; csrc/evalstats.hip) ----------
+ * pred / target / unc: [N][D] fp32 device arrays, 1 <= D <= 3, 1 <= N < 2^31.  Every reduction below has a fixed partition
+ * and a fixed-order fold and uses no floating-point atomics: two calls on the same inputs give bit-identical outputs.
+ *
+ * mmdeer_bootstrap_moments: R <= 4096 bootstrap replicates.  Draw i < N of replicate r reads row
+ *     j = ((splitmix64(key(seed, r) + i) >> 32) * N) >> 32,   key(seed, r) = splitmix64(seed + r * 0xD1B54A32D192ED03)
+ *   (mmdeer/synth.py: bootstrap_indices restates it in numpy).  One index per (r, i) serves all D dimensions: the reference
+ *   draws per dimension, but each interval is a marginal statistic, so its distribution is the same.
+ *   mom[R][D][6] (fp64) = {n, sum p, sum t, sum p^2, sum t^2, sum pt} over the drawn rows where neither value is NaN;
+ *   flags[R][D]: bit 0 the drawn valid p are all equal (min == max: pearsonr's exact test), bit 1 the same for t, bit 2
+ *   both and the two constants are equal.  scratch: mmdeer_bootstrap_scratch(N, R) bytes, 16-byte aligned (a repacked
+ *   32-byte row per sample and the per-workgroup partial sums).
+ * mmdeer_bootstrap_ci: metric 0 = CCC (evaluation.py:656-682: 0.0 below two valid pairs or for a zero denominator, NaN
+ *   for a constant sample), 1 = Pearson (NaN for a constant sample or when a NaN row was drawn).  NaN replicates are
+ *   dropped, the rest sorted; ci[D][2] (fp64) = np.percentile (linear) at the levels q_lo, q_hi in [0, 1]; nkept[D] = the
+ *   number of replicates kept ({0.0, 0.0} when none is). */
+long long mmdeer_bootstrap_scratch(long long N, int R);
+int mmdeer_bootstrap_moments(const float* pred, const float* target, long long N, int D, int R, unsigned long long seed,
+                             double* mom, int* flags, void* scratch, long long scratch_bytes, void* stream);
+int mmdeer_bootstrap_ci(const double* mom, const int* flags, long long N, int D, int R, int metric, double q_lo, double q_hi,
+                        double* ci, int* nkept, void* stream);
+
+/* Stable ascending sort of n <= 2^20 fp32 keys (keys[i * stride]) by the total order (key, index): order[n] (int32) is
+ * exactly np.argsort(kind='stable') -- -0.0 == +0.0, NaN last.  A larger n is refused.  scratch:
+ * mmdeer_sort_pairs_scratch(n) bytes, 8-byte aligned; after the call it holds the sorted (key image, index) pairs that
+ * mmdeer_average_ranks reads: ranks[n] (fp64, original positions) = the tie-averaged 1-based ranks of
+ * scipy.stats.rankdata (NaN keys rank as one run of ties at the end).
+ * mmdeer_rank_moments: out[3] = {sum a'^2, sum b'^2, sum a'b'} of two rank arrays centred by (n + 1) / 2 (Spearman). */
+long long mmdeer_sort_pairs_scratch(long long n);
+int mmdeer_sort_pairs(const float* keys, long long stride, long long n, int* order, void* scratch, long long scratch_bytes,
+                      void* stream);
+int mmdeer_average_ranks(const void* sorted, long long n, double* ranks, void* stream);
+int mmdeer_rank_moments(const double* ranks_a, const double* ranks_b, long long n, double* out, void* stream);
+
+/* Bin tables of CalibrationAnalyzer.compute_ece (evaluation.py:492-530) per dimension.  Confidence 1 - u / (max u + 1e-8)
+ * and the threshold np.median(|p - t|) are formed in float32 as numpy forms them; edges: DEVICE array of n_bins + 1
+ * doubles (np.linspace(0, 1, n_bins + 1)), n_bins <= 32.  bins[D][2][n_bins][3] (fp64) = {count, sum confidence,
+ * sum (|p - t| <= threshold)} under rule 0 ([lo, hi), last bin closed: the reference's weights) and rule 1 ((lo, hi],
+ * first bin closed: sklearn's calibration_curve).  stats[D][4] = {max u, threshold, 1 if an uncertainty is not finite or
+ * a confidence lies outside [0, 1] (the reference then returns 0.0), 1 if the threshold is NaN}.
+ * scratch: mmdeer_calibration_bins_scratch(D) bytes. */
+long long mmdeer_calibration_bins_scratch(int D);
+int mmdeer_calibration_bins(const float* pred, const float* target, const float* unc, long long N, int D, const double* edges,
+                            int n_bins, double* stats, double* bins, void* scratch, void* stream);
+
 /* ---- Stack B: complete_project.CompleteDEERModel, eval forward -----------------------------------------
  * Every Linear(+ReLU) of the model runs on mmdeer_gemm; with a single key the reference's MultiHeadAttention
  * (complete_project.py:120-184) is output_proj(value_proj(value)) exactly, i.e. two more GEMMs.  The four single

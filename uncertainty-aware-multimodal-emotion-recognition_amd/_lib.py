@@ -275,6 +275,15 @@ SYMBOLS = [
     ("mmdeer_eval_accumulate", c_int, [c_void_p] * 6 + [c_int, c_void_p]),
     ("mmdeer_eval_quantile_select", c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("mmdeer_eval_ece_bins", c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p]),
+    ("mmdeer_bootstrap_scratch", c_ll, [c_ll, c_int]),
+    ("mmdeer_bootstrap_moments", c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_u64, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    ("mmdeer_bootstrap_ci", c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p]),
+    ("mmdeer_sort_pairs_scratch", c_ll, [c_ll]),
+    ("mmdeer_sort_pairs", c_int, [c_void_p, c_ll, c_ll, c_void_p, c_void_p, c_ll, c_void_p]),
+    ("mmdeer_average_ranks", c_int, [c_void_p, c_ll, c_void_p, c_void_p]),
+    ("mmdeer_rank_moments", c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_void_p]),
+    ("mmdeer_calibration_bins_scratch", c_ll, [c_int]),
+    ("mmdeer_calibration_bins", c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("mmdeer_stackb_residual_ln", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("mmdeer_stackb_attn_mix", c_int, [C.POINTER(StackBAttnArgs)]),
     ("mmdeer_stackb_gate_mix", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -53,6 +53,18 @@ def uniform01(stream: int, n: int, offset: int = 0) -> np.ndarray:
     return (bits >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
+def bootstrap_indices(seed: int, replicate: int, n: int) -> np.ndarray:
+    """The n rows replicate ``replicate`` of ``mmdeer_bootstrap_moments`` draws (csrc/evalstats.hip: boot_index), bit for bit:
+    row_i = ((splitmix64(key + i) >> 32) * n) >> 32 with key = splitmix64(seed + replicate * 0xD1B54A32D192ED03).
+    Integer-only; the product stays inside uint64 for n < 2**32.  Returns int64."""
+    if not 1 <= n < 1 << 32:
+        raise ValueError("bootstrap_indices: need 1 <= n < 2**32")
+    key = _splitmix64(np.array([(int(seed) + int(replicate) * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))[0]
+    with np.errstate(over="ignore"):
+        bits = _splitmix64((np.arange(n, dtype=np.uint64) + key) & _M64)
+    return (((bits >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
 def normal(stream: int, n: int, offset: int = 0) -> np.ndarray:
     """n N(0,1) doubles by Box-Muller over two decorrelated counter streams."""
     u1 = uniform01(stream * 2 + 0, n, offset)
