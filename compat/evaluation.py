@@ -9,4 +9,5 @@ from mmdeer.evaluation import (  # noqa: F401
     DEERModelEvaluator,
     EvaluationResults,
     StatisticalValidator,
+    UncertaintyAnalyzer,
 )

@@ -620,6 +620,27 @@ long long mmdeer_calibration_bins_scratch(int D);
 int mmdeer_calibration_bins(const float* pred, const float* target, const float* unc, long long N, int D, const double* edges,
                             int n_bins, double* stats, double* bins, void* scratch, void* stream);
 
+/* The table UncertaintyAnalyzer (evaluation.py:358-482) is computed from, per dimension d of u = unc[:, d] and
+ * e = |pred - target|[:, d] (the float32 subtraction, as numpy forms it); 2 <= N <= 2^20 (the sort's limit).
+ * table[D][MMDEER_UNC_TABLE] (fp64, device):
+ *    0 N | 1 sum u | 2 sum e | 3 sum (u - mean u)^2 | 4 sum (e - mean e)^2 | 5 sum (u - mean u)(e - mean e) | 6 mean u
+ *    7 population variance of u | 8 min u | 9 max u | 10 min e | 11 max e   (NaN with a NaN in the column, as np.min / np.max)
+ *   12 flags: 1 = a NaN in u, 2 = a NaN in e | 13-15 zero
+ *   16 + k, k < n_cuts <= 16: the sum of e over the n_keep[k] least uncertain samples -- the first n_keep[k] positions of the
+ *        stable ascending order of u (ties in index order, NaN last: mmdeer_sort_pairs' order); 0 for n_keep[k] = 0, NaN
+ *        with a NaN error in the prefix.  n_keep: HOST array, ascending, each in [0, N]; the sparsification curve's
+ *        int(frac * N) is the caller's arithmetic, not recomputed here.
+ *   32 + k, k < n_q <= 8: np.percentile(u, 100 * levels[k]), method 'linear', in fp64; NaN with a NaN in u.  levels: HOST
+ *        array, each in [0, 1].
+ * Unused entries are zero.  All D columns are sorted by the same launches (the launch count of one mmdeer_sort_pairs plus
+ * four); sums are fp64 with a partition that depends on N alone and a fixed-order fold: two calls give bit-identical tables.
+ * scratch: mmdeer_uncertainty_table_scratch(N, D) bytes (0 for an N or D out of range), 8-byte aligned. */
+#define MMDEER_UNC_TABLE 40
+long long mmdeer_uncertainty_table_scratch(long long N, int D);
+int mmdeer_uncertainty_table(const float* pred, const float* target, const float* unc, long long N, int D, const long long* n_keep,
+                             int n_cuts, const double* levels, int n_q, double* table, void* scratch, long long scratch_bytes,
+                             void* stream);
+
 /* ---- Stack B: complete_project.CompleteDEERModel, eval forward -----------------------------------------
  * Every Linear(+ReLU) of the model runs on mmdeer_gemm; with a single key the reference's MultiHeadAttention
  * (complete_project.py:120-184) is output_proj(value_proj(value)) exactly, i.e. two more GEMMs.  The four single

@@ -284,6 +284,9 @@ SYMBOLS = [
     ("mmdeer_rank_moments", c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_void_p]),
     ("mmdeer_calibration_bins_scratch", c_ll, [c_int]),
     ("mmdeer_calibration_bins", c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("mmdeer_uncertainty_table_scratch", c_ll, [c_ll, c_int]),
+    ("mmdeer_uncertainty_table", c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, C.POINTER(c_ll), c_int, C.POINTER(C.c_double), c_int,
+                                         c_void_p, c_void_p, c_ll, c_void_p]),
     ("mmdeer_stackb_residual_ln", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     ("mmdeer_stackb_attn_mix", c_int, [C.POINTER(StackBAttnArgs)]),
     ("mmdeer_stackb_gate_mix", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -1,6 +1,6 @@
 // mmdeer -- on-device statistics of the DEER evaluator (reference src/training/evaluation.py:135-355, 492-530, 578-682):
-// bootstrap moments and percentile intervals, a stable sort with tie-averaged ranks (Spearman), and the bin tables of the
-// evaluator's calibration error.  The (N, D) prediction / target / uncertainty arrays stay in HBM; what reaches the host is
+// bootstrap moments and percentile intervals, a stable sort with tie-averaged ranks (Spearman), the bin tables of the
+// evaluator's calibration error, and the table UncertaintyAnalyzer (:358-482) is computed from.  The (N, D) prediction / target / uncertainty arrays stay in HBM; what reaches the host is
 // ci[D][2], a few moment sums and the bin tables.  Every reduction has a fixed partition and a fixed-order fold and uses no
 // floating-point atomics: two launches on the same inputs give bit-identical results.
 #include "common.h"
@@ -180,6 +180,27 @@ __device__ double np_percentile_sorted(const double* v, int n, double q) {
   const int hi = lo + 1 < n ? lo + 1 : n - 1;
   return np_lerp(v[lo], v[hi], __dsub_rn(virt, (double)lo));
 }
+// The same two steps for a caller that fetches the two order statistics itself, with contraction switched off: the _rn
+// intrinsics above are plain operators to this compiler, which may fuse a product into the sum that follows, and
+// fma(10, 0.95, -9) is 0.49999999999999956 where numpy has 0.5.  Results equal to np.percentile bit for bit need every
+// product rounded first.
+__device__ __forceinline__ double np_percentile_position(int n, double q, int* lo_out, int* hi_out) {
+#pragma clang fp contract(off)
+  const double virt = (double)(n - 1) * q;
+  int lo = (int)floor(virt);
+  if (lo > n - 1) lo = n - 1;
+  if (lo < 0) lo = 0;
+  *lo_out = lo;
+  *hi_out = lo + 1 < n ? lo + 1 : n - 1;
+  return virt - (double)lo;
+}
+__device__ __forceinline__ double np_lerp_strict(double a, double b, double t) {
+#pragma clang fp contract(off)
+  const double d = b - a;
+  double r = a + d * t;
+  if (t >= 0.5) r = b - d * (1.0 - t);
+  return d == 0.0 ? a : r;
+}
 
 // one workgroup per dimension: R <= 4096 replicate values in LDS, NaN replaced by +inf (sorted to the end and not counted),
 // bitonic sort, the two percentiles over the nkept values that remain
@@ -240,8 +261,11 @@ __device__ __forceinline__ unsigned sort_image(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(256) void sort_init_kernel(const float* keys, long long stride, long long n, long long P,
+// blockIdx.y = column c: keys + c * col_step -> a + c * P (mmdeer_sort_pairs has one column; the network kernels alike)
+__global__ __launch_bounds__(256) void sort_init_kernel(const float* keys, long long stride, long long col_step, long long n, long long P,
                                                         unsigned long long* a) {
+  keys += (long long)blockIdx.y * col_step;
+  a += (long long)blockIdx.y * P;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256)
     a[i] = i < n ? (((unsigned long long)sort_image(keys[i * stride]) << 32) | (unsigned long long)i) : ~0ull;
 }
@@ -250,6 +274,7 @@ __global__ __launch_bounds__(256) void sort_init_kernel(const float* keys, long 
 __global__ __launch_bounds__(256) void sort_tile_kernel(unsigned long long* a, long long P, long long k_first, long long k_last) {
   __shared__ unsigned long long t[SORT_TILE];
   const int tid = threadIdx.x;
+  a += (long long)blockIdx.y * P;
   const long long base = (long long)blockIdx.x * SORT_TILE;
   const int len = (int)(P < SORT_TILE ? P : SORT_TILE);
   for (int i = tid; i < len; i += 256) t[i] = a[base + i];
@@ -273,6 +298,7 @@ __global__ __launch_bounds__(256) void sort_tile_kernel(unsigned long long* a, l
 
 // one step (k, j) with j >= SORT_TILE in global memory
 __global__ __launch_bounds__(256) void sort_step_kernel(unsigned long long* a, long long P, long long k, long long j) {
+  a += (long long)blockIdx.y * P;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) {
     const long long l = i ^ j;
     if (l > i) {
@@ -448,9 +474,232 @@ __global__ __launch_bounds__(256) void cal_bins_kernel(const float* pred, const 
   }
 }
 
+// ---- uncertainty table of UncertaintyAnalyzer (evaluation.py:358-482) --------------------------------------------------------
+// Per dimension, of u = unc[:, d] and e = |pred - target|[:, d] (the float32 subtraction): moments, the sums of e over the
+// n_keep[k] least uncertain samples (stable ascending order of u, NaN last) and np.percentile of u.  table[d][UNC_TABLE]:
+//   0 n | 1 sum u | 2 sum e | 3 sum (u - mean u)^2 | 4 sum (e - mean e)^2 | 5 sum (u - mean u)(e - mean e) | 6 mean u
+//   7 population variance of u | 8 min u | 9 max u | 10 min e | 11 max e | 12 flags (1: a NaN in u, 2: a NaN in e) | 13-15 zero
+//   16 + k: sum of e over the first n_keep[k] sorted positions | 32 + k: np.percentile(u, 100 levels[k]), NaN with a NaN in u
+// The centred sums take a second pass over the column: with u = 1e-3 + 1e-6 x the raw sums would cancel seven digits.
+constexpr int UNC_MAX_CUTS = 16;
+constexpr int UNC_MAX_Q = 8;
+constexpr int UNC_TABLE = 40;
+constexpr int UNC_CHUNK = 2048;      // sorted positions per workgroup of the prefix gather: the partition depends on N alone
+constexpr int UNC_P1 = 7;            // per workgroup of the first pass: sum u, sum e, min u, max u, min e, max e, flags
+struct UncCuts {
+  long long keep[UNC_MAX_CUTS];
+  double q[UNC_MAX_Q];
+  int n_cuts, n_q;
+};
+__host__ __forceinline__ int unc_chunks(long long N) { return (int)((N + UNC_CHUNK - 1) / UNC_CHUNK); }
+
+// fixed-order LDS tree over 256 lanes; the sum is in sm[0] afterwards
+__device__ __forceinline__ void tree_sum_256(double* sm, int tid) {
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) sm[tid] += sm[tid + off];
+    __syncthreads();
+  }
+}
+
+// workgroup (s, d): rows [s * per, (s + 1) * per), row i on lane (i - first) % 256.  Minima and maxima skip NaN (fminf would
+// drop it silently); the flag carries it and the last kernel writes NaN, as np.min / np.max do.
+__global__ __launch_bounds__(256) void unc_sums_kernel(const float* pred, const float* target, const float* unc, int N, int D, int S,
+                                                       double* part1) {
+  __shared__ double sm[2][256];
+  __shared__ float sf[4][256];
+  __shared__ unsigned s_flags;
+  const int tid = threadIdx.x, s = blockIdx.x, d = blockIdx.y;
+  const int per = (N + S - 1) / S;
+  const int i0 = s * per, i1 = i0 + per < N ? i0 + per : N;
+  double su = 0.0, se = 0.0;
+  float umin = __builtin_inff(), umax = -__builtin_inff(), emin = __builtin_inff(), emax = -__builtin_inff();
+  unsigned flags = 0u;
+  if (tid == 0) s_flags = 0u;
+  for (int i = i0 + tid; i < i1; i += 256) {
+    const float u = unc[(size_t)i * D + d];
+    const float e = fabsf(pred[(size_t)i * D + d] - target[(size_t)i * D + d]);
+    su += (double)u; se += (double)e;
+    if (u != u) flags |= 1u; else { umin = fminf(umin, u); umax = fmaxf(umax, u); }
+    if (e != e) flags |= 2u; else { emin = fminf(emin, e); emax = fmaxf(emax, e); }
+  }
+  sm[0][tid] = su; sm[1][tid] = se;
+  sf[0][tid] = umin; sf[1][tid] = umax; sf[2][tid] = emin; sf[3][tid] = emax;
+  __syncthreads();
+  if (flags) atomicOr(&s_flags, flags);
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      sm[0][tid] += sm[0][tid + off]; sm[1][tid] += sm[1][tid + off];
+      sf[0][tid] = fminf(sf[0][tid], sf[0][tid + off]); sf[1][tid] = fmaxf(sf[1][tid], sf[1][tid + off]);
+      sf[2][tid] = fminf(sf[2][tid], sf[2][tid + off]); sf[3][tid] = fmaxf(sf[3][tid], sf[3][tid + off]);
+    }
+    __syncthreads();
+  }
+  double* out = part1 + ((size_t)d * S + s) * UNC_P1;
+  if (tid < 2) out[tid] = sm[tid][0];
+  else if (tid < 6) out[tid] = (double)sf[tid - 2][0];
+  else if (tid == 6) out[6] = (double)s_flags;
+}
+
+// the S <= 64 first-pass partials of dimension d into LDS, one lane each; folded from there in order s = 0, 1, ... by one
+// lane (a fold straight from HBM would wait for one load after the other)
+__device__ __forceinline__ void unc_stage_part1(const double* part1, int S, int d, int tid, double (*sp)[UNC_P1]) {
+  for (int i = tid; i < S * UNC_P1; i += blockDim.x) sp[i / UNC_P1][i % UNC_P1] = part1[(size_t)d * S * UNC_P1 + i];
+}
+__device__ __forceinline__ double unc_fold(const double (*sp)[UNC_P1], int S, int k) {
+  double v = 0.0;
+  for (int s = 0; s < S; ++s) v += sp[s][k];
+  return v;
+}
+
+// second pass, same partition: part2[d][s][3] = sums of (u - mean u)^2, (e - mean e)^2 and their product
+__global__ __launch_bounds__(256) void unc_centred_kernel(const float* pred, const float* target, const float* unc, int N, int D, int S,
+                                                          const double* part1, double* part2) {
+  __shared__ double sm[3][256];
+  __shared__ double sp[BOOT_MAX_SPLIT][UNC_P1];
+  __shared__ double s_mean[2];
+  const int tid = threadIdx.x, s = blockIdx.x, d = blockIdx.y;
+  unc_stage_part1(part1, S, d, tid, sp);
+  __syncthreads();
+  if (tid < 2) s_mean[tid] = unc_fold(sp, S, tid) / (double)N;
+  __syncthreads();
+  const double mu = s_mean[0], me = s_mean[1];
+  const int per = (N + S - 1) / S;
+  const int i0 = s * per, i1 = i0 + per < N ? i0 + per : N;
+  double a[3] = {0.0, 0.0, 0.0};
+  for (int i = i0 + tid; i < i1; i += 256) {
+    const double du = (double)unc[(size_t)i * D + d] - mu;
+    const double de = (double)fabsf(pred[(size_t)i * D + d] - target[(size_t)i * D + d]) - me;
+    a[0] += du * du; a[1] += de * de; a[2] += du * de;
+  }
+  for (int k = 0; k < 3; ++k) sm[k][tid] = a[k];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+      for (int k = 0; k < 3; ++k) sm[k][tid] += sm[k][tid + off];
+    __syncthreads();
+  }
+  if (tid < 3) part2[((size_t)d * S + s) * 3 + tid] = sm[tid][0];
+}
+
+// workgroup (c, d): sorted positions [c * UNC_CHUNK, (c + 1) * UNC_CHUNK) of column d, cut by the n_keep into segments
+// [n_keep[k - 1], n_keep[k]); seg[d][c][k] = the sum of e over segment k inside this chunk, e gathered through the sorted
+// index.  Position pos goes to lane (pos - first of the segment here) % 256; fixed LDS tree.  A NaN error stays a NaN sum.
+__global__ __launch_bounds__(256) void unc_prefix_kernel(const unsigned long long* a, long long P, const float* pred, const float* target,
+                                                         int N, int D, int C, UncCuts cuts, double* seg) {
+  __shared__ double sm[256];
+  const int tid = threadIdx.x, c = blockIdx.x, d = blockIdx.y;
+  const unsigned long long* ad = a + (long long)d * P;
+  const long long pos0 = (long long)c * UNC_CHUNK;
+  const long long pos1 = pos0 + UNC_CHUNK < N ? pos0 + UNC_CHUNK : N;
+  long long lo = 0;
+  for (int k = 0; k < cuts.n_cuts; ++k) {
+    const long long hi = cuts.keep[k];
+    const long long b0 = lo > pos0 ? lo : pos0, b1 = hi < pos1 ? hi : pos1;
+    double total = 0.0;
+    if (b0 < b1) {                                  // the same for every lane
+      double v = 0.0;
+      for (long long pos = b0 + tid; pos < b1; pos += 256) {
+        const size_t row = (size_t)(unsigned)(ad[pos] & 0xFFFFFFFFull);       // < N: the padding sorts behind position N - 1
+        v += (double)fabsf(pred[row * D + d] - target[row * D + d]);
+      }
+      sm[tid] = v;
+      tree_sum_256(sm, tid);
+      total = sm[0];
+      __syncthreads();
+    }
+    if (tid == 0) seg[((size_t)d * C + c) * UNC_MAX_CUTS + k] = total;
+    lo = hi;
+  }
+}
+
+// one workgroup per dimension folds everything in a fixed order and writes table[d].  Segment sums: lane (part, k) adds
+// column k over the part-th sixteenth of the chunks, lane k the sixteen parts in order, then the running sum over k.
+__global__ __launch_bounds__(256) void unc_final_kernel(const unsigned long long* a, long long P, const float* unc, int N, int D, int S, int C,
+                                                        UncCuts cuts, const double* part1, const double* part2, const double* seg,
+                                                        double* table) {
+  __shared__ double sp[BOOT_MAX_SPLIT][UNC_P1];
+  __shared__ double sq[BOOT_MAX_SPLIT][3];
+  __shared__ double sg[16][UNC_MAX_CUTS];
+  __shared__ double st[UNC_MAX_CUTS];
+  const int tid = threadIdx.x, d = blockIdx.x;
+  const unsigned long long* ad = a + (long long)d * P;
+  double* out = table + (size_t)d * UNC_TABLE;
+  const double nan = __builtin_nan("");
+  unc_stage_part1(part1, S, d, tid, sp);
+  for (int i = tid; i < S * 3; i += 256) sq[i / 3][i % 3] = part2[(size_t)d * S * 3 + i];
+  {
+    const int k = tid % UNC_MAX_CUTS, part = tid / UNC_MAX_CUTS, per = (C + 15) / 16;
+    const int c1 = (part + 1) * per < C ? (part + 1) * per : C;
+    double v = 0.0;
+    for (int c = part * per; c < c1; ++c) v += seg[((size_t)d * C + c) * UNC_MAX_CUTS + k];
+    sg[part][k] = k < cuts.n_cuts ? v : 0.0;          // entries past n_cuts were never written
+  }
+  __syncthreads();
+  if (tid < UNC_MAX_CUTS) {
+    double v = 0.0;
+    for (int part = 0; part < 16; ++part) v += sg[part][tid];
+    st[tid] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double su = unc_fold(sp, S, 0), se = unc_fold(sp, S, 1);
+    double umin = __builtin_inf(), umax = -__builtin_inf(), emin = __builtin_inf(), emax = -__builtin_inf();
+    unsigned flags = 0u;
+    for (int s = 0; s < S; ++s) {
+      umin = fmin(umin, sp[s][2]); umax = fmax(umax, sp[s][3]); emin = fmin(emin, sp[s][4]); emax = fmax(emax, sp[s][5]);
+      flags |= (unsigned)sp[s][6];
+    }
+    out[0] = (double)N; out[1] = su; out[2] = se; out[6] = su / (double)N;
+    out[8] = (flags & 1u) ? nan : umin; out[9] = (flags & 1u) ? nan : umax;
+    out[10] = (flags & 2u) ? nan : emin; out[11] = (flags & 2u) ? nan : emax;
+    out[12] = (double)flags; out[13] = 0.0; out[14] = 0.0; out[15] = 0.0;
+  } else if (tid < 4) {
+    double v = 0.0;
+    for (int s = 0; s < S; ++s) v += sq[s][tid - 1];
+    out[2 + tid] = v;
+    if (tid == 1) out[7] = v / (double)N;
+  } else if (tid >= 64 && tid < 64 + UNC_MAX_CUTS) {
+    const int k = tid - 64;
+    double v = 0.0;
+    for (int j = 0; j <= k; ++j) v += st[j];
+    out[16 + k] = k < cuts.n_cuts ? v : 0.0;
+  } else if (tid >= 128 && tid < 128 + UNC_MAX_Q) {
+    const int k = tid - 128;
+    double q = -1.0;
+    for (int j = 0; j < cuts.n_q; ++j)
+      if (j == k) q = cuts.q[j];
+    double v = 0.0;
+    if (q >= 0.0) {
+      const bool has_nan = (unsigned)(ad[N - 1] >> 32) == 0xFFFFFFFFu;       // NaN sorts last
+      int lo, hi;
+      const double t = np_percentile_position(N, q, &lo, &hi);
+      const double x = (double)unc[(size_t)(unsigned)(ad[lo] & 0xFFFFFFFFull) * D + d];
+      const double y = (double)unc[(size_t)(unsigned)(ad[hi] & 0xFFFFFFFFull) * D + d];
+      v = has_nan ? nan : np_lerp_strict(x, y, t);
+    }
+    out[32 + k] = v;
+  }
+}
+
 inline unsigned grid_for(long long n, long long cap = 4096) {
   long long b = (n + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// composite keys of `columns` key columns into a[columns][P] and the bitonic network over all of them: one launch per step
+// whatever the number of columns
+inline void launch_sort(const float* keys, long long stride, long long col_step, long long n, long long P, unsigned columns,
+                        unsigned long long* a, hipStream_t st) {
+  hipLaunchKernelGGL(sort_init_kernel, dim3(grid_for(P), columns), dim3(256), 0, st, keys, stride, col_step, n, P, a);
+  const unsigned tiles = (unsigned)(P <= SORT_TILE ? 1 : P / SORT_TILE);
+  // k <= SORT_TILE: every step stays inside a tile
+  hipLaunchKernelGGL(sort_tile_kernel, dim3(tiles, columns), dim3(256), 0, st, a, P, 2ll, P < SORT_TILE ? P : (long long)SORT_TILE);
+  for (long long k = 2ll * SORT_TILE; k <= P; k <<= 1) {
+    for (long long j = k >> 1; j >= SORT_TILE; j >>= 1)
+      hipLaunchKernelGGL(sort_step_kernel, dim3(grid_for(P), columns), dim3(256), 0, st, a, P, k, j);
+    hipLaunchKernelGGL(sort_tile_kernel, dim3(tiles, columns), dim3(256), 0, st, a, P, k, k);
+  }
 }
 
 }  // namespace
@@ -520,15 +769,7 @@ int mmdeer_sort_pairs(const float* keys, long long stride, long long n, int* ord
   while (P < n) P <<= 1;
   unsigned long long* a = (unsigned long long*)scratch;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sort_init_kernel, dim3(grid_for(P)), dim3(256), 0, st, keys, stride, n, P, a);
-  const unsigned tiles = (unsigned)(P <= SORT_TILE ? 1 : P / SORT_TILE);
-  // k <= SORT_TILE: every step stays inside a tile
-  hipLaunchKernelGGL(sort_tile_kernel, dim3(tiles), dim3(256), 0, st, a, P, 2ll, P < SORT_TILE ? P : (long long)SORT_TILE);
-  for (long long k = 2ll * SORT_TILE; k <= P; k <<= 1) {
-    for (long long j = k >> 1; j >= SORT_TILE; j >>= 1)
-      hipLaunchKernelGGL(sort_step_kernel, dim3(grid_for(P)), dim3(256), 0, st, a, P, k, j);
-    hipLaunchKernelGGL(sort_tile_kernel, dim3(tiles), dim3(256), 0, st, a, P, k, k);
-  }
+  launch_sort(keys, stride, 0, n, P, 1, a, st);
   hipLaunchKernelGGL(sort_order_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const unsigned long long*)a, n, order);
   MMDEER_HIP(hipGetLastError());
   return 0;
@@ -562,6 +803,57 @@ int mmdeer_calibration_bins(const float* pred, const float* target, const float*
   hipLaunchKernelGGL(cal_select_kernel, dim3(D, 3), dim3(256), 0, st, pred, target, unc, N, D, (float*)scratch);
   hipLaunchKernelGGL(cal_bins_kernel, dim3(D, 2 * n_bins), dim3(256), 0, st, pred, target, unc, N, D, edges, n_bins, (const float*)scratch,
                      stats, bins);
+  MMDEER_HIP(hipGetLastError());
+  return 0;
+}
+
+long long mmdeer_uncertainty_table_scratch(long long N, int D) {
+  if (N < 2 || N > SORT_MAX_N || D < 1 || D > 3) return 0;
+  long long P = 1;
+  while (P < N) P <<= 1;
+  // sorted pairs [D][P] | first-pass partials [D][S][7] | centred partials [D][S][3] | segment sums [D][C][16]: all doubles wide
+  return (long long)D * 8 * (P + (long long)boot_split(N) * (UNC_P1 + 3) + (long long)unc_chunks(N) * UNC_MAX_CUTS);
+}
+
+int mmdeer_uncertainty_table(const float* pred, const float* target, const float* unc, long long N, int D, const long long* n_keep,
+                             int n_cuts, const double* levels, int n_q, double* table, void* scratch, long long scratch_bytes,
+                             void* stream) {
+  MMDEER_CHECK(pred && target && unc && table && scratch, "uncertainty_table: NULL argument");
+  MMDEER_CHECK(N >= 2, "uncertainty_table: need N >= 2 (got %lld)", N);
+  MMDEER_CHECK(N <= SORT_MAX_N, "uncertainty_table: N = %lld is above the limit of %lld samples (the device sort)", N, SORT_MAX_N);
+  MMDEER_CHECK(D >= 1 && D <= 3, "uncertainty_table: need 1 <= D <= 3 (got %d)", D);
+  MMDEER_CHECK(n_cuts >= 0 && n_cuts <= UNC_MAX_CUTS, "uncertainty_table: need 0 <= n_cuts <= %d (got %d)", UNC_MAX_CUTS, n_cuts);
+  MMDEER_CHECK(n_q >= 0 && n_q <= UNC_MAX_Q, "uncertainty_table: need 0 <= n_q <= %d (got %d)", UNC_MAX_Q, n_q);
+  MMDEER_CHECK((n_cuts == 0 || n_keep) && (n_q == 0 || levels), "uncertainty_table: NULL argument");
+  UncCuts cuts = {};
+  cuts.n_cuts = n_cuts; cuts.n_q = n_q;
+  for (int k = 0; k < n_cuts; ++k) {
+    MMDEER_CHECK(n_keep[k] >= 0 && n_keep[k] <= N, "uncertainty_table: n_keep[%d] = %lld lies outside [0, N = %lld]", k, n_keep[k], N);
+    MMDEER_CHECK(k == 0 || n_keep[k] >= n_keep[k - 1], "uncertainty_table: n_keep must be ascending (n_keep[%d] = %lld after %lld)", k,
+                 n_keep[k], n_keep[k - 1]);
+    cuts.keep[k] = n_keep[k];
+  }
+  for (int k = 0; k < n_q; ++k) {
+    MMDEER_CHECK(levels[k] >= 0.0 && levels[k] <= 1.0, "uncertainty_table: quantile levels must lie in [0, 1] (levels[%d])", k);
+    cuts.q[k] = levels[k];
+  }
+  MMDEER_CHECK(scratch_bytes >= mmdeer_uncertainty_table_scratch(N, D), "uncertainty_table: scratch of %lld bytes, %lld needed",
+               scratch_bytes, mmdeer_uncertainty_table_scratch(N, D));
+  MMDEER_CHECK(((uintptr_t)scratch & 7) == 0, "uncertainty_table: scratch must be 8-byte aligned");
+  long long P = 1;
+  while (P < N) P <<= 1;
+  const int S = boot_split(N), C = unc_chunks(N);
+  unsigned long long* a = (unsigned long long*)scratch;
+  double* part1 = (double*)(a + (size_t)D * P);
+  double* part2 = part1 + (size_t)D * S * UNC_P1;
+  double* seg = part2 + (size_t)D * S * 3;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(unc_sums_kernel, dim3(S, D), dim3(256), 0, st, pred, target, unc, (int)N, D, S, part1);
+  hipLaunchKernelGGL(unc_centred_kernel, dim3(S, D), dim3(256), 0, st, pred, target, unc, (int)N, D, S, (const double*)part1, part2);
+  launch_sort(unc, (long long)D, 1, N, P, (unsigned)D, a, st);      // the D columns by the same launches
+  hipLaunchKernelGGL(unc_prefix_kernel, dim3(C, D), dim3(256), 0, st, (const unsigned long long*)a, P, pred, target, (int)N, D, C, cuts, seg);
+  hipLaunchKernelGGL(unc_final_kernel, dim3(D), dim3(256), 0, st, (const unsigned long long*)a, P, unc, (int)N, D, S, C, cuts,
+                     (const double*)part1, (const double*)part2, (const double*)seg, table);
   MMDEER_HIP(hipGetLastError());
   return 0;
 }

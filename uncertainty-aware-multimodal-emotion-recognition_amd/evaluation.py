@@ -16,6 +16,10 @@ Differences from the reference, all deliberate:
   dimension.  Each interval is a marginal statistic of one dimension, so its distribution is the same.  The draws are a
   counter hash of ``seed`` (``synth.bootstrap_indices``), not numpy's global generator: a call is reproducible.
 * Spearman sorts on the device, at most 2**20 samples; a larger N is refused with a message.
+* ``UncertaintyAnalyzer`` orders the samples by uncertainty with the device's STABLE sort (ties in index order, NaN last).
+  The reference calls ``np.argsort`` with its default kind, whose order among equal uncertainties is unspecified (and
+  differs from the stable one in practice).  The sparsification results agree whenever no run of equal uncertainties
+  straddles a cut point ``int(frac * N)``; where one does, the stable order is the definition here.  2 <= N <= 2**20.
 """
 from __future__ import annotations
 
@@ -237,6 +241,43 @@ def calibration_bins(p: torch.Tensor, t: torch.Tensor, u: torch.Tensor, n_bins: 
     return stats.cpu().numpy(), bins.cpu().numpy()
 
 
+SPARSIFICATION_FRACTIONS = np.linspace(0.1, 1.0, 10)
+UNC_TABLE = 40                         # MMDEER_UNC_TABLE
+UNC_LEVELS = (0.5, 0.95)               # np.median, np.percentile(., 95)
+
+
+def sparsification_cuts(n: int) -> List[int]:
+    """The reference's own expression (evaluation.py:445-449), in Python floats: int(0.30000000000000004 * n) is the contract."""
+    return [int(float(frac) * n) for frac in SPARSIFICATION_FRACTIONS]
+
+
+def ause_from_means(errors, fractions=SPARSIFICATION_FRACTIONS) -> float:
+    """np.trapz(errors, fractions), written out (the name left numpy 2)."""
+    e, f = np.asarray(errors, dtype=np.float64), np.asarray(fractions, dtype=np.float64)
+    return float(np.sum((f[1:] - f[:-1]) * (e[1:] + e[:-1]) / 2.0))
+
+
+def uncertainty_table_device(p: torch.Tensor, t: torch.Tensor, u: torch.Tensor, n_keep, levels=UNC_LEVELS) -> torch.Tensor:
+    """table (D, 40) float64 device tensor of mmdeer_uncertainty_table: include/mmdeer.h has the layout.  ``n_keep`` are
+    ascending cut points in [0, N], ``levels`` quantile levels in [0, 1].  Enqueues only."""
+    import ctypes as C
+    lib = _lib.load()
+    N, D = p.shape
+    table = torch.empty(D, UNC_TABLE, dtype=torch.float64, device=p.device)
+    nbytes = int(lib.mmdeer_uncertainty_table_scratch(N, D))
+    scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=p.device)
+    keep = (C.c_longlong * max(len(n_keep), 1))(*[int(k) for k in n_keep])
+    lev = (C.c_double * max(len(levels), 1))(*[float(q) for q in levels])
+    _lib.check(lib.mmdeer_uncertainty_table(p.data_ptr(), t.data_ptr(), u.data_ptr(), N, D, keep, len(n_keep), lev, len(levels),
+                                            table.data_ptr(), scratch.data_ptr(), nbytes, _lib.current_stream()))
+    return table
+
+
+def uncertainty_table(p: torch.Tensor, t: torch.Tensor, u: torch.Tensor, n_keep, levels=UNC_LEVELS) -> np.ndarray:
+    """``uncertainty_table_device`` copied to the host (D x 320 bytes)."""
+    return uncertainty_table_device(p, t, u, n_keep, levels).cpu().numpy()
+
+
 def ece_from_bins(weight_bins, curve_bins, n: int) -> float:
     """The reference's sum (evaluation.py:511-524) from the two bin tables [n_bins][3] = {count, sum conf, sum acc}.
 
@@ -300,7 +341,7 @@ class EvaluationResults:
 
 
 class CalibrationAnalyzer:
-    """evaluation.py:485-530 (``compute_ece``; the curve lists of ``analyze_calibration`` are not built)."""
+    """evaluation.py:485-563: ``compute_ece`` and ``analyze_calibration``."""
 
     def compute_ece(self, predictions, targets, uncertainties, n_bins: int = 15) -> float:
         """ECE of 1-D GPU tensors as the reference computes it, quirks included (see ``ece_from_bins``): confidence
@@ -315,6 +356,102 @@ class CalibrationAnalyzer:
     def _ece_all(self, p, t, u, n_bins: int) -> List[float]:
         stats, bins = calibration_bins(p, t, u, n_bins)
         return [0.0 if stats[d, 2] != 0 else ece_from_bins(bins[d, 0], bins[d, 1], p.shape[0]) for d in range(p.shape[1])]
+
+    def analyze_calibration(self, predictions, targets, uncertainties, n_bins: int = 15) -> Dict[str, Any]:
+        """``{dim}_ece`` and ``{dim}_calibration_curve`` {'mean_predicted_value', 'fraction_of_positives'} per dimension of
+        (N, D) GPU tensors: sklearn's non-empty bins ((lo, hi], rule 1 of ``calibration_bins``).  Where calibration_curve
+        would raise (a confidence outside [0, 1] or a non-finite uncertainty) the reference logs a warning and leaves the
+        curve key out, and its ECE is 0.0; so here."""
+        p, t = _pair(predictions, targets)
+        u = _gpu2d(uncertainties, "uncertainties")
+        if u.shape != p.shape:
+            raise ValueError("mmdeer.evaluation: uncertainties and predictions differ in shape")
+        stats, bins = calibration_bins(p, t, u, n_bins)
+        out: Dict[str, Any] = {}
+        for d, dim in enumerate(EMOTION_DIMS[: p.shape[1]]):
+            if stats[d, 2] != 0:
+                out[f"{dim}_ece"] = 0.0
+                continue
+            out[f"{dim}_ece"] = ece_from_bins(bins[d, 0], bins[d, 1], p.shape[0])
+            curve = bins[d, 1][bins[d, 1][:, 0] != 0]
+            out[f"{dim}_calibration_curve"] = {"mean_predicted_value": (curve[:, 1] / curve[:, 0]).tolist(),
+                                               "fraction_of_positives": (curve[:, 2] / curve[:, 0]).tolist()}
+        return out
+
+
+class UncertaintyAnalyzer:
+    """evaluation.py:358-482.  One call of mmdeer_uncertainty_table serves the correlation, sparsification and
+    distribution sections; the calibration section is ``CalibrationAnalyzer.analyze_calibration``.  What reaches the host
+    is that table (D x 40 doubles) and the bin tables.
+
+    The three private methods keep the reference's names and arguments, on (N, D) GPU tensors; ``errors`` are absolute
+    errors (they enter as |errors - 0|).  ``table`` lets ``analyze_uncertainty_quality`` compute the table once."""
+
+    def __init__(self):
+        self.calibration_analyzer = CalibrationAnalyzer()
+
+    def analyze_uncertainty_quality(self, predictions, targets, uncertainties) -> Dict[str, Any]:
+        p, t = _pair(predictions, targets)
+        u = _gpu2d(uncertainties, "uncertainties")
+        if u.shape != p.shape:
+            raise ValueError("mmdeer.evaluation: uncertainties and predictions differ in shape")
+        table = uncertainty_table(p, t, u, sparsification_cuts(p.shape[0]))
+        return {
+            "uncertainty_error_correlation": self._compute_uncertainty_error_correlation(u, None, table),
+            "calibration_analysis": self.calibration_analyzer.analyze_calibration(p, t, u),
+            "sparsification_analysis": self._compute_sparsification_analysis(u, None, table),
+            "uncertainty_distribution": self._analyze_uncertainty_distribution(u, table),
+        }
+
+    @staticmethod
+    def _table(uncertainties, errors, table) -> np.ndarray:
+        if table is not None:
+            return table
+        u = _gpu2d(uncertainties, "uncertainties")
+        e = u if errors is None else _gpu2d(errors, "errors")
+        if e.shape != u.shape:
+            raise ValueError("mmdeer.evaluation: uncertainties and errors differ in shape")
+        return uncertainty_table(e, torch.zeros_like(e), u, sparsification_cuts(u.shape[0]))
+
+    def _compute_uncertainty_error_correlation(self, uncertainties, errors, table=None) -> Dict[str, float]:
+        """Pearson correlation of (u, |error|) per dimension with scipy's p-value; NaN for a column with a NaN or a constant
+        column (exactly: min == max), as pearsonr."""
+        tb = self._table(uncertainties, errors, table)
+        out: Dict[str, float] = {}
+        for d, dim in enumerate(EMOTION_DIMS[: tb.shape[0]]):
+            n, suu, see, sue = int(tb[d, 0]), float(tb[d, 3]), float(tb[d, 4]), float(tb[d, 5])
+            if tb[d, 12] != 0 or tb[d, 8] == tb[d, 9] or tb[d, 10] == tb[d, 11] or not (suu > 0 and see > 0):
+                corr = NAN
+            else:
+                corr = max(-1.0, min(1.0, sue / math.sqrt(suu * see)))
+            out[f"{dim}_correlation"] = corr
+            out[f"{dim}_p_value"] = pearson_p_value(corr, n)
+        out["average_correlation"] = float(np.mean([out[f"{dim}_correlation"] for dim in EMOTION_DIMS[: tb.shape[0]]]))
+        return out
+
+    def _compute_sparsification_analysis(self, uncertainties, errors, table=None) -> Dict[str, Any]:
+        """Mean error of the int(frac * N) least uncertain samples for frac = 0.1 .. 1.0 (0.0 where that count is 0) and
+        the area under those ten means (AUSE, trapezoid rule)."""
+        tb = self._table(uncertainties, errors, table)
+        keep = sparsification_cuts(int(tb[0, 0]))
+        out: Dict[str, Any] = {}
+        for d, dim in enumerate(EMOTION_DIMS[: tb.shape[0]]):
+            means = [float(tb[d, 16 + k]) / n_keep if n_keep > 0 else 0.0 for k, n_keep in enumerate(keep)]
+            out[f"{dim}_ause"] = ause_from_means(means)
+            out[f"{dim}_sparsification_curve"] = {"fractions": SPARSIFICATION_FRACTIONS.tolist(), "errors": means}
+        return out
+
+    def _analyze_uncertainty_distribution(self, uncertainties, table=None) -> Dict[str, float]:
+        tb = self._table(uncertainties, None, table)
+        out: Dict[str, float] = {}
+        for d, dim in enumerate(EMOTION_DIMS[: tb.shape[0]]):
+            out[f"{dim}_mean"] = float(tb[d, 6])
+            out[f"{dim}_std"] = math.sqrt(tb[d, 7]) if tb[d, 7] >= 0 else NAN
+            out[f"{dim}_min"] = float(tb[d, 8])
+            out[f"{dim}_max"] = float(tb[d, 9])
+            out[f"{dim}_median"] = float(tb[d, 32])
+            out[f"{dim}_percentile_95"] = float(tb[d, 33])
+        return out
 
 
 class StatisticalValidator:
@@ -381,6 +518,7 @@ class DEERModelEvaluator:
         self.emotion_dims = list(emotion_dims) if emotion_dims is not None else list(EMOTION_DIMS)
         self.confidence_level = confidence_level
         self.n_bootstrap = n_bootstrap
+        self.uncertainty_analyzer = UncertaintyAnalyzer()
         self.calibration_analyzer = CalibrationAnalyzer()
         self.statistical_validator = StatisticalValidator(confidence_level)
 
