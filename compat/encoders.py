@@ -1,6 +1,9 @@
 """`from encoders import AudioEncoder, VideoEncoder, TextEncoder` (run_multimodal_deer.py:77).  The raw-signal front ends
-(librosa / cv2 / BERT) are out of scope; the pre-extracted-feature branch of EnhancedAudioEncoder (row a14) is real."""
+(librosa / cv2 / BERT) are out of scope; the pre-extracted-feature branch of EnhancedAudioEncoder (row a14) is real,
+and EnhancedTextEncoder is the reference's no-BERT configuration on token ids and a mask (mmdeer.text; its
+``forward_embeddings`` takes the caller's own contextual embeddings in place of BERT's last_hidden_state)."""
 from mmdeer.side import EnhancedAudioEncoder  # noqa: F401
+from mmdeer.text import TemporalTextEncoder as EnhancedTextEncoder  # noqa: F401
 
 
 def _out_of_scope(name):

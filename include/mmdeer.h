@@ -512,6 +512,86 @@ typedef struct mmdeer_temporal_pool_args {
 int mmdeer_temporal_pool_fwd(const mmdeer_temporal_pool_args* a);
 int mmdeer_temporal_pool_bwd(const mmdeer_temporal_pool_args* a);
 
+/* ---- temporal text encoder (reference src/models/encoders.py:648-746; csrc/token_pool.hip).  Rows are batch-major: row
+ * b * L + t.  The widths are fixed: E = 768 (`width`) and A = 384 (`att_width`); others are refused.  L is arbitrary.  Every
+ * refusal (NULL or misaligned pointers, leading dimensions too small or misaligned, widths, negative B / L) is decided on the
+ * host before any HIP call; B == 0 or L == 0 writes nothing and returns 0.  Activation rows ("act") need 16-byte alignment:
+ * pointer % 16 == 0 and ld % (4 fp32 | 8 bf16) == 0.  mask is fp32 [B][L] and is taken as BINARY: m = 1 where it is nonzero.
+ *
+ * mmdeer_token_embed_fwd: the gather.  Either the tables (ids int64 [B][L], emb fp32 [V][768], pos fp32 [P][768], V < 2^24)
+ *   or src fp32 [B*L][ld_src >= 768] (precomputed embeddings) with the tables NULL.
+ *     tables: x = (emb[clamp(id, 0, V-1)] + pos[min(t, P-1)]) * m     and ids32 int32 [B*L] = the clamped ids
+ *     src:    x = src * m
+ *   x is act [B*L][ld_x >= 768].
+ * mmdeer_token_embed_bwd: from dx act [B*L][ld_dx >= 768] and the mask, either d_src fp32 [B*L][ld_dsrc >= 768] = dx * m, or
+ *   both table gradients in fp32, dense: d_pos [P][768] and d_emb [V][768] (all of it is written: rows that no valid token names,
+ *   and row 0, the padding row, are exact zeros).  No floating-point atomics: d_pos sums over the samples in a fixed order, and
+ *   d_emb groups the rows by id with mmdeer_sort_pairs (stable) and sums every run in row order, so two calls give the same
+ *   bits.  B * L <= 2^20 (the sort's limit; more is refused).  ids32 is the forward's.  scratch: 16-byte aligned,
+ *   mmdeer_token_embed_bwd_scratch(B * L) bytes. */
+typedef struct mmdeer_token_embed_args {
+  const int64_t* ids;
+  const float* mask;
+  const float* emb; const float* pos; int32_t V, P;
+  const float* src; int32_t ld_src;
+  void* x; int32_t ld_x;
+  int32_t* ids32;
+  const void* dx; int32_t ld_dx;
+  float* d_src; int32_t ld_dsrc;
+  float* d_emb; float* d_pos;
+  void* scratch; long long scratch_bytes;
+  int32_t B, L, width, act_f32;
+  void* stream;
+} mmdeer_token_embed_args;
+long long mmdeer_token_embed_bwd_scratch(long long rows);
+int mmdeer_token_embed_fwd(const mmdeer_token_embed_args* a);
+int mmdeer_token_embed_bwd(const mmdeer_token_embed_args* a);
+
+/* Masked attention pool over tokens (encoders.py:733-746).  x act [B*L][ld_x >= 768] is ALREADY masked (x_t = 0 where m_t = 0),
+ * z act [B*L][ld_z >= 384] = W1 x + b1 (from mmdeer_gemm), w2 fp32 [384], b2 fp32 [1]:
+ *     s_t = w2 . tanh(z_t) + b2      p = softmax(s) over ALL L positions (max-subtracted; padded positions take part)
+ *     S = sum_t p_t m_t              a_t = p_t m_t / (S + 1e-10)            attended = sum_t a_t x_t
+ *   forward writes attended act [B][ld_att >= 768], weights fp32 [B][L] (= a) and, when probs is not NULL, probs fp32 [B][L]
+ *   (= p, which the backward reads).  A fully masked sample gives a = 0 and attended = 0 exactly.
+ *   backward reads dout act [B][ld_dout >= 768], x, z, weights, probs and writes dx act [B*L][ld_dx >= 768] = a_t dout (the
+ *   direct term only; the score path's share dz W1 is the caller's GEMM, and the caller multiplies the sum by m),
+ *   dz act [B*L][ld_dz >= 384], dw2 fp32 [384] and db2 fp32 [1] = an exact zero (b2 shifts every score of a sample equally).
+ *   With da_t = dout . x_t and c = sum_u a_u da_u:  ds_t = p_t (m_t (da_t - c) - c 1e-10) / (S + 1e-10).
+ *   scratch: fp32, 16-byte aligned, at least MMDEER_TOKEN_POOL_SCRATCH elements (dw2's per-workgroup partials, folded in a
+ *   fixed order: deterministic). */
+#define MMDEER_TOKEN_POOL_SCRATCH (1024 * 384)
+typedef struct mmdeer_token_pool_args {
+  const void* x; int32_t ld_x;
+  const void* z; int32_t ld_z;
+  const float* mask;
+  const float* w2; const float* b2;
+  void* attended; int32_t ld_att;
+  float* weights; float* probs;
+  const void* dout; int32_t ld_dout;
+  void* dx; int32_t ld_dx;
+  void* dz; int32_t ld_dz;
+  float* dw2; float* db2; float* scratch;
+  int32_t B, L, width, att_width, act_f32;
+  void* stream;
+} mmdeer_token_pool_args;
+int mmdeer_token_pool_fwd(const mmdeer_token_pool_args* a);
+int mmdeer_token_pool_bwd(const mmdeer_token_pool_args* a);
+
+/* Per-sample token statistics (encoders.py:648-699, "linguistic features") without the reference's host loop.
+ * ids int32 [B][L], mask fp32 [B][L] -> out fp32 [B][ld_out >= 16].  With n valid tokens, u distinct valid ids, c_max the
+ * largest multiplicity and id_max the largest valid id: out[b] = { n / max_length, u / max(n, 1), n / (id_max + 1), c_max,
+ * #{999 <= id <= 1030} / max(n, 1), #{100 <= id <= 999} / max(n, 1), 0 x 10 } (columns 10 .. 15 pad K to a multiple of 4
+ * for the GEMM that follows).  n = 0: all zeros.  L <= 2048 (a sample's ids are held in LDS; more is refused).  Negative valid
+ * ids are undefined input (the reference's bincount raises on them). */
+typedef struct mmdeer_token_stats_args {
+  const int32_t* ids;
+  const float* mask;
+  float* out; int32_t ld_out;
+  int32_t B, L, max_length;
+  void* stream;
+} mmdeer_token_stats_args;
+int mmdeer_token_stats(const mmdeer_token_stats_args* a);
+
 /* ---- the evidence tail as an operator of its own (reference src/models/deer.py:55, 86-98): the last Linear(K -> 4 O) of an
  * evidence net, the NIG activations and the three uncertainties in ONE launch for G nets side by side, and its backward.
  * "act" = fp32 when act_f32 != 0, else bf16.  Net g reads columns [g K, (g + 1) K) of x; output column g O + o.
@@ -921,7 +1001,8 @@ int mmdeer_allgather(const void* send, void* recv, long long send_count, int dty
 
 /* sizeof() of an argument struct of this header by its name without the mmdeer_ prefix ("gemm_args", "chain_args", "chain_seg",
  * "repack_job", "forward_args", "backward_args", "adamw_args", "adamw_flat_args", "stackb_attn_train_args", "stackb_attn_args",
- * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args", "evidence_tail_args"); -1 for an unknown name.  A binding in another language checks its
+ * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args", "evidence_tail_args",
+ * "token_embed_args", "token_pool_args", "token_stats_args"); -1 for an unknown name.  A binding in another language checks its
  * own layout against it at load time (mmdeer/_lib.py does). */
 long long mmdeer_sizeof(const char* struct_name);
 

@@ -214,14 +214,43 @@ class EvidenceTailArgs(C.Structure):
     ]
 
 
+class TokenEmbedArgs(C.Structure):
+    """mmdeer_token_embed_args (include/mmdeer.h)."""
+    _fields_ = [
+        ("ids", c_void_p), ("mask", c_void_p), ("emb", c_void_p), ("pos", c_void_p), ("V", c_int), ("P", c_int),
+        ("src", c_void_p), ("ld_src", c_int), ("x", c_void_p), ("ld_x", c_int), ("ids32", c_void_p),
+        ("dx", c_void_p), ("ld_dx", c_int), ("d_src", c_void_p), ("ld_dsrc", c_int), ("d_emb", c_void_p), ("d_pos", c_void_p),
+        ("scratch", c_void_p), ("scratch_bytes", c_ll),
+        ("B", c_int), ("L", c_int), ("width", c_int), ("act_f32", c_int), ("stream", c_void_p),
+    ]
+
+
+class TokenPoolArgs(C.Structure):
+    """mmdeer_token_pool_args (include/mmdeer.h)."""
+    _fields_ = [
+        ("x", c_void_p), ("ld_x", c_int), ("z", c_void_p), ("ld_z", c_int), ("mask", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
+        ("attended", c_void_p), ("ld_att", c_int), ("weights", c_void_p), ("probs", c_void_p), ("dout", c_void_p), ("ld_dout", c_int),
+        ("dx", c_void_p), ("ld_dx", c_int), ("dz", c_void_p), ("ld_dz", c_int), ("dw2", c_void_p), ("db2", c_void_p), ("scratch", c_void_p),
+        ("B", c_int), ("L", c_int), ("width", c_int), ("att_width", c_int), ("act_f32", c_int), ("stream", c_void_p),
+    ]
+
+
+class TokenStatsArgs(C.Structure):
+    """mmdeer_token_stats_args (include/mmdeer.h)."""
+    _fields_ = [("ids", c_void_p), ("mask", c_void_p), ("out", c_void_p), ("ld_out", c_int),
+                ("B", c_int), ("L", c_int), ("max_length", c_int), ("stream", c_void_p)]
+
+
 TEMPORAL_POOL_SCRATCH = 256 * 256   # MMDEER_TEMPORAL_POOL_SCRATCH
+TOKEN_POOL_SCRATCH = 1024 * 384     # MMDEER_TOKEN_POOL_SCRATCH
 
 # ctypes mirror of every argument struct, by the name mmdeer_sizeof() knows it under
 STRUCTS = {"gemm_args": GemmArgs, "chain_args": ChainArgs, "chain_seg": ChainSeg, "repack_job": RepackJob, "forward_args": ForwardArgs,
            "backward_args": BackwardArgs, "adamw_args": AdamWArgs, "adamw_flat_args": AdamWFlatArgs, "stackb_attn_train_args": StackBAttnTrainArgs,
            "stackb_attn_args": StackBAttnArgs, "stackb_forward_args": StackBForwardArgs, "stackb_weights": StackBWeights,
            "softmax_mix_args": SoftmaxMixArgs, "lstm_seq_args": LstmSeqArgs, "temporal_pool_args": TemporalPoolArgs,
-           "evidence_tail_args": EvidenceTailArgs}
+           "evidence_tail_args": EvidenceTailArgs, "token_embed_args": TokenEmbedArgs, "token_pool_args": TokenPoolArgs,
+           "token_stats_args": TokenStatsArgs}
 
 # every symbol include/mmdeer.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -301,6 +330,12 @@ SYMBOLS = [
     ("mmdeer_lstm_seq_bwd", c_int, [C.POINTER(LstmSeqArgs)]),
     ("mmdeer_temporal_pool_fwd", c_int, [C.POINTER(TemporalPoolArgs)]),
     ("mmdeer_temporal_pool_bwd", c_int, [C.POINTER(TemporalPoolArgs)]),
+    ("mmdeer_token_embed_bwd_scratch", c_ll, [c_ll]),
+    ("mmdeer_token_embed_fwd", c_int, [C.POINTER(TokenEmbedArgs)]),
+    ("mmdeer_token_embed_bwd", c_int, [C.POINTER(TokenEmbedArgs)]),
+    ("mmdeer_token_pool_fwd", c_int, [C.POINTER(TokenPoolArgs)]),
+    ("mmdeer_token_pool_bwd", c_int, [C.POINTER(TokenPoolArgs)]),
+    ("mmdeer_token_stats", c_int, [C.POINTER(TokenStatsArgs)]),
     ("mmdeer_evidence_tail_scratch", C.c_longlong, [c_int, c_int, c_int, c_int]),
     ("mmdeer_evidence_tail_fwd", c_int, [C.POINTER(EvidenceTailArgs)]),
     ("mmdeer_evidence_tail_bwd", c_int, [C.POINTER(EvidenceTailArgs)]),

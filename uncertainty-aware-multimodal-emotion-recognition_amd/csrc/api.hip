@@ -513,7 +513,7 @@ long long mmdeer_sizeof(const char* n) {
 #define SZ(name) if (strcmp(n, #name) == 0) return (long long)sizeof(mmdeer_##name);
   SZ(gemm_args) SZ(chain_args) SZ(chain_seg) SZ(repack_job) SZ(forward_args) SZ(backward_args) SZ(adamw_args) SZ(adamw_flat_args)
   SZ(stackb_attn_train_args) SZ(stackb_attn_args) SZ(stackb_forward_args) SZ(stackb_weights) SZ(softmax_mix_args)
-  SZ(lstm_seq_args) SZ(temporal_pool_args) SZ(evidence_tail_args)
+  SZ(lstm_seq_args) SZ(temporal_pool_args) SZ(evidence_tail_args) SZ(token_embed_args) SZ(token_pool_args) SZ(token_stats_args)
 #undef SZ
   return -1;
 }
