@@ -250,6 +250,71 @@ def test_rank_moments_against_the_restatement():
     np.testing.assert_allclose(out.cpu().numpy(), E.rank_moments(E.average_ranks(x), E.average_ranks(y)), rtol=1e-12)
 
 
+# ---- 4b. the shared order-statistic selection, through both entry points -------------------------------------------------------------
+def select_keys(n, stream):
+    """Heavy ties (about nine distinct values), negatives, +-0.0, denormals and +-3e38; finite, no NaN."""
+    k = np.round(synth.normal(stream, n) * 2).astype(np.float32) / 2
+    special = np.array([0.0, -0.0, 1e-45, -1e-45, 1e-40, 3e38, -3e38, -0.0, 0.0], dtype=np.float32)
+    if n > len(special):
+        k[(np.arange(len(special)) * 37) % n] = special
+    elif n == 2:
+        k = np.array([-0.0, -3e38], dtype=np.float32)
+    return k
+
+
+def quantile_select(err, unc, nq):
+    vals = torch.full((nq, 2), -1.0, dtype=torch.float32, device=DEV)
+    frac = torch.full((nq,), -1.0, dtype=torch.float64, device=DEV)
+    nv = torch.full((1,), -1, dtype=torch.int64, device=DEV)
+    E_, U_ = dev(err), dev(unc)
+    _lib.check(_lib.load().mmdeer_eval_quantile_select(E_.data_ptr(), U_.data_ptr(), len(err), nq, vals.data_ptr(), frac.data_ptr(),
+                                                       nv.data_ptr(), _lib.current_stream()))
+    return vals.cpu().numpy(), frac.cpu().numpy(), int(nv.item())
+
+
+@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 1000])
+def test_radix_selection_is_the_sorted_order_statistic_through_both_entry_points(n):
+    """Integer-exact: the selected 32-bit image is that of the k-th smallest key, so every comparison is == (-0.0 == 0.0)."""
+    i = np.arange(n)
+    # quantile path: a sample counts when its error is not NaN and its uncertainty is finite
+    unc = select_keys(n, 610 + n % 89)
+    err = np.abs(select_keys(n, 611 + n % 89))
+    err[i % 7 == 3] = np.nan
+    unc[i % 11 == 5] = np.inf
+    unc[i % 13 == 6] = -np.inf
+    unc[i % 17 == 8] = np.nan
+    valid = ~np.isnan(err) & np.isfinite(unc)
+    s = np.sort(unc[valid])
+    nv = len(s)
+    assert nv >= 1 and (nv < n or n <= 3)
+    for nq in (2, 11):
+        vals, frac, nvalid = quantile_select(err, unc, nq)
+        q = np.linspace(0, 1, nq)
+        virt = q * (nv - 1)
+        lo = np.floor(virt).astype(np.int64)
+        hi = np.minimum(lo + 1, nv - 1)
+        assert nvalid == nv, (nq, nvalid, nv)
+        assert np.array_equal(vals[:, 0], s[lo]) and np.array_equal(vals[:, 1], s[hi]), (nq, vals.tolist(), s[lo].tolist(), s[hi].tolist())
+        assert np.array_equal(frac, virt - lo), (nq, frac.tolist(), (virt - lo).tolist())
+        vals, frac, nvalid = quantile_select(np.full(n, np.nan, dtype=np.float32), unc, nq)
+        assert nvalid == 0 and not vals.any() and not frac.any()
+    vals, frac, nvalid = quantile_select(err, np.full(n, -np.inf, dtype=np.float32), 11)
+    assert nvalid == 0 and not vals.any() and not frac.any()
+    # calibration path: stats[d, 1] is np.median of the float32 |p - t| (odd n: the middle one, even n: the float32 mean of two)
+    p = np.stack([select_keys(n, 620 + n % 89), select_keys(n, 621 + n % 89)], axis=1)
+    t = np.stack([np.zeros(n, dtype=np.float32), np.round(synth.normal(622 + n % 89, n)).astype(np.float32)], axis=1)
+    u = (0.5 + np.abs(synth.normal(623 + n % 89, 2 * n)).reshape(n, 2)).astype(np.float32)
+    e = np.abs(p - t)
+    assert e.dtype == np.float32 and not np.isnan(e).any()
+    stats, _ = M.calibration_bins(dev(p), dev(t), dev(u), 10)
+    want = np.median(e, axis=0)
+    assert want.dtype == np.float32 and np.array_equal(stats[:, 1], want.astype(np.float64)), (stats[:, 1].tolist(), want.tolist())
+    assert not stats[:, 3].any()
+    p[n // 3, 0] = np.nan
+    stats, _ = M.calibration_bins(dev(p), dev(t), dev(u), 10)
+    assert math.isnan(stats[0, 1]) and stats[0, 3] == 1.0 and stats[1, 1] == float(want[1]) and stats[1, 3] == 0.0
+
+
 # ---- 5. evaluate_model end to end ----------------------------------------------------------------------------------------------
 def loader(n, bs, seed, as_dict):
     b = synth.make_batch(n, seed=seed)

@@ -15,6 +15,8 @@ namespace {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
+// These two stay next to elem.h's ld8 / st8 on purpose: with load8 written on ld8 the compiler gives the bf16
+// tri_attn_bwd_kernel another register assignment and instruction order, and this file runs inside the benchmarked step.
 struct V8 { float v[8]; };
 
 template <bool F32>
@@ -164,9 +166,7 @@ int launch_tri_attn_fwd(const void* qkv, void* obar, float* probs, float* attn_w
                         int train, const DropCtx& dc, hipStream_t s) {
   if (B == 0) return 0;
   const int grid = (B + 3) / 4;
-  if (act_f32) hipLaunchKernelGGL(tri_attn_fwd_kernel<true>, dim3(grid), dim3(256), 0, s, qkv, obar, probs, attn_w, av_w, B, train, dc);
-  else hipLaunchKernelGGL(tri_attn_fwd_kernel<false>, dim3(grid), dim3(256), 0, s, qkv, obar, probs, attn_w, av_w, B, train, dc);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(tri_attn_fwd_kernel, act_f32, dim3(grid), dim3(256), s, qkv, obar, probs, attn_w, av_w, B, train, dc);
   return 0;
 }
 
@@ -174,9 +174,7 @@ int launch_tri_attn_bwd(const void* qkv, const void* dobar, const float* probs, 
                         int train, const DropCtx& dc, hipStream_t s) {
   if (B == 0) return 0;
   const int grid = (B + 3) / 4;
-  if (act_f32) hipLaunchKernelGGL(tri_attn_bwd_kernel<true>, dim3(grid), dim3(256), 0, s, qkv, dobar, probs, dqkv, B, train, dc);
-  else hipLaunchKernelGGL(tri_attn_bwd_kernel<false>, dim3(grid), dim3(256), 0, s, qkv, dobar, probs, dqkv, B, train, dc);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(tri_attn_bwd_kernel, act_f32, dim3(grid), dim3(256), s, qkv, dobar, probs, dqkv, B, train, dc);
   return 0;
 }
 

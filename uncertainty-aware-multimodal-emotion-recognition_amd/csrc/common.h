@@ -163,4 +163,19 @@ void set_error(const char* fmt, ...);
   } while (0)
 #define TRY(x) do { if ((x) != 0) return -1; } while (0)   // pass a failed launcher's -1 on (its message is set)
 
+// kernel<true> for fp32 activations, kernel<false> for bf16, then the launch's error check; _LDS: with dynamic LDS bytes
+#define MMDEER_LAUNCH_ACT_LDS(kernel, act_f32, grid, block, lds, stream, ...)                     \
+  do {                                                                                            \
+    if (act_f32) hipLaunchKernelGGL(kernel<true>, grid, block, lds, stream, __VA_ARGS__);         \
+    else hipLaunchKernelGGL(kernel<false>, grid, block, lds, stream, __VA_ARGS__);                \
+    MMDEER_HIP(hipGetLastError());                                                                \
+  } while (0)
+#define MMDEER_LAUNCH_ACT(kernel, act_f32, grid, block, stream, ...) \
+  MMDEER_LAUNCH_ACT_LDS(kernel, act_f32, grid, block, 0, stream, __VA_ARGS__)
+
+// pointer alignment for the argument checks (a NULL pointer is aligned: optional arguments pass)
+inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+inline bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace mmdeer

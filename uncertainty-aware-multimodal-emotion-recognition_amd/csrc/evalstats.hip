@@ -1,12 +1,190 @@
 // mmdeer -- on-device statistics of the DEER evaluator (reference src/training/evaluation.py:135-355, 492-530, 578-682):
-// bootstrap moments and percentile intervals, a stable sort with tie-averaged ranks (Spearman), the bin tables of the
-// evaluator's calibration error, and the table UncertaintyAnalyzer (:358-482) is computed from.  The (N, D) prediction / target / uncertainty arrays stay in HBM; what reaches the host is
-// ci[D][2], a few moment sums and the bin tables.  Every reduction has a fixed partition and a fixed-order fold and uses no
-// floating-point atomics: two launches on the same inputs give bit-identical results.
+// the streaming CCC / Pearson / MAE / RMSE sums and the quantile-binned calibration error of the validation loop, bootstrap
+// moments and percentile intervals, a stable sort with tie-averaged ranks (Spearman), the bin tables of the evaluator's
+// calibration error, and the table UncertaintyAnalyzer (:358-482) is computed from.  The (N, D) prediction / target /
+// uncertainty arrays stay in HBM; what reaches the host is ci[D][2], a few moment sums and the bin tables.  Every reduction
+// has a fixed partition and a fixed-order fold and uses no floating-point atomics: two launches on the same inputs give
+// bit-identical results.
 #include "common.h"
 
 namespace mmdeer {
 namespace {
+
+// ---- shared by the kernels below: block fold, float image, order-statistic selection -------------------------------------------
+// Fixed-order LDS tree over the 256 lanes of a workgroup, `rows` rows in the same steps: lane tid adds lane tid + off for
+// off = 128, 64, ..., 1, so a sum has the same bits whatever else is folded next to it.  Row k's sum is in sm[k][0] afterwards.
+// Opens with a barrier (the callers' writes need none of their own) and ends behind one.
+__device__ __forceinline__ void tree_sum_256(double (*sm)[256], int rows, int tid) {
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off)
+      for (int k = 0; k < rows; ++k) sm[k][tid] += sm[k][tid + off];
+    __syncthreads();
+  }
+}
+// The row count at compile time (unrolled).  NM > 0: the NM rows of float extrema in sf, which the caller must then pass, are
+// folded in the same steps -- even rows as minima, odd rows as maxima, so they come in (min, max) pairs.
+template <int NS, int NM = 0>
+__device__ __forceinline__ void tree_sum_256(double (*sm)[256], int tid, float (*sf)[256] = nullptr) {
+  static_assert(NS >= 1 && NM >= 0 && NM % 2 == 0, "rows of sums, and (min, max) pairs of extrema");
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) sm[k][tid] += sm[k][tid + off];
+#pragma unroll
+      for (int k = 0; k < NM; ++k) sf[k][tid] = (k & 1) ? fmaxf(sf[k][tid], sf[k][tid + off]) : fminf(sf[k][tid], sf[k][tid + off]);
+    }
+    __syncthreads();
+  }
+}
+
+// order-preserving image of a float in the unsigned integers (-inf < ... < -0.0 < +0.0 < ... < +inf; NaN by its bits), and back
+__device__ __forceinline__ unsigned float_image(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float image_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+// The k-th smallest (k from 0) of the 32-bit keys of elements [0, n), by a workgroup of 256 lanes: 4 passes of 8 bits over integer
+// histograms -- exact and deterministic.  key(i, out) writes element i's key and returns true, or returns false to skip i; k must
+// be below the number of elements it keeps.  Every lane returns the selected key.
+struct RadixScratch {
+  unsigned hist[256];
+  unsigned digit;
+  long long k;
+};
+template <typename KeyFn>
+__device__ __forceinline__ unsigned radix_select_256(long long n, long long k, RadixScratch& rs, int tid, KeyFn key) {
+  unsigned prefix = 0u, mask = 0u;
+  for (int pass = 3; pass >= 0; --pass) {
+    const int shift = 8 * pass;
+    rs.hist[tid] = 0u;
+    __syncthreads();
+    for (long long i = tid; i < n; i += 256) {
+      unsigned x;
+      if (!key(i, x)) continue;
+      if ((x & mask) == prefix) atomicAdd(&rs.hist[(x >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      long long cum = 0;
+      unsigned d = 0;
+      for (; d < 255u; ++d) {
+        if (k < cum + (long long)rs.hist[d]) break;
+        cum += rs.hist[d];
+      }
+      rs.digit = d; rs.k = k - cum;
+    }
+    __syncthreads();
+    prefix |= rs.digit << shift; mask |= 255u << shift; k = rs.k;
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// ---- streaming evaluation statistics (reference src/utils/metrics.py:59-125, src/training/training.py:
+//      316-353): per emotion dimension the sufficient statistics of CCC / Pearson / MAE / RMSE, accumulated in fp64
+//      across validation batches, so the (N, 3) prediction arrays never travel to the host.
+//      acc[d][8] += {n, sum p, sum t, sum p^2, sum t^2, sum p t, sum |p - t|, sum (p - t)^2} over the rows where neither
+//      value is NaN (the reference masks them).  Block 3 writes the per-sample mean |error| and mean uncertainty that
+//      the quantile-binned calibration error needs (2 floats per sample instead of 9).
+__global__ __launch_bounds__(256) void eval_accumulate_kernel(const float* pred, const float* target, const float* unc,
+                                                              double* acc, float* sample_err, float* sample_unc, int B) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 3) {
+    if (!sample_err && !sample_unc) return;
+    for (int b = tid; b < B; b += 256) {
+      float e = 0.f, u = 0.f;
+      for (int d = 0; d < 3; ++d) {
+        e += fabsf(pred[b * 3 + d] - target[b * 3 + d]);
+        if (unc) u += unc[b * 3 + d];
+      }
+      if (sample_err) sample_err[b] = e / 3.f;
+      if (sample_unc) sample_unc[b] = u / 3.f;
+    }
+    return;
+  }
+  __shared__ double sm[8][256];
+  const int d = blockIdx.x;
+  double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = tid; b < B; b += 256) {
+    const float pf = pred[b * 3 + d], tf = target[b * 3 + d];
+    if (pf != pf || tf != tf) continue;
+    const double p = pf, t = tf, e = p - t;
+    s[0] += 1.0; s[1] += p; s[2] += t; s[3] += p * p; s[4] += t * t; s[5] += p * t; s[6] += fabs(e); s[7] += e * e;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) sm[k][tid] = s[k];
+  tree_sum_256<8>(sm, tid);
+  if (tid < 8) acc[d * 8 + tid] += sm[tid][0];   // calls on one stream are ordered: a plain read-modify-write
+}
+
+// ---- quantile-binned calibration error (reference src/utils/metrics.py:214-279) on per-sample device arrays --------------
+// The reference bins the per-sample mean uncertainty by its own quantiles (np.quantile, linear interpolation) and compares,
+// per bin, mean(1 - uncertainty) with mean(1 - error).  Two launches keep it on the device: an exact order-statistic
+// selection for the 2 (nq) ranks np.quantile interpolates between, and the bin sums against the edges the host derives from
+// those 2 nq values.  A sample counts when its error and uncertainty are not NaN and the uncertainty is finite (:243).
+__device__ __forceinline__ bool ece_valid(float e, float u) { return e == e && u == u && fabsf(u) != __builtin_inff(); }
+
+// block b: quantile r = b >> 1 (q_r = linspace(0, 1, nq)[r]), neighbour (b & 1): the floor(q (n - 1))-th smallest valid
+// uncertainty or the one after it, by a 4-pass radix selection (8 bits per pass, integer histograms: exact, deterministic)
+__global__ __launch_bounds__(256) void eval_quantile_select_kernel(const float* err, const float* unc, long long n, int nq,
+                                                                   float* vals, double* frac, long long* nvalid) {
+  __shared__ RadixScratch rs;
+  __shared__ unsigned long long s_cnt;
+  const int tid = threadIdx.x, r = blockIdx.x >> 1, which = blockIdx.x & 1;
+  if (tid == 0) s_cnt = 0ull;
+  __syncthreads();
+  unsigned long long c = 0;
+  for (long long i = tid; i < n; i += 256) c += ece_valid(err[i], unc[i]) ? 1ull : 0ull;
+  atomicAdd(&s_cnt, c);
+  __syncthreads();
+  const long long nv = (long long)s_cnt;
+  if (nv == 0) {
+    if (tid == 0) { vals[2 * r + which] = 0.f; if (!which) { frac[r] = 0.0; if (r == 0) *nvalid = 0; } }
+    return;
+  }
+  const double q = (r == nq - 1) ? 1.0 : (double)r * (1.0 / (double)(nq - 1));      // np.linspace(0, 1, nq)[r]
+  const double virt = q * (double)(nv - 1);                                        // np.quantile, method 'linear'
+  const long long lo = (long long)floor(virt);
+  const long long k = which ? (lo + 1 < nv ? lo + 1 : nv - 1) : lo;
+  const unsigned sel = radix_select_256(n, k, rs, tid, [&](long long i, unsigned& key) {
+    const float u = unc[i];
+    key = float_image(u);
+    return ece_valid(err[i], u);
+  });
+  if (tid == 0) {
+    vals[2 * r + which] = image_float(sel);
+    if (!which) { frac[r] = virt - (double)lo; if (r == 0) *nvalid = nv; }
+  }
+}
+
+// bins[i] = {count, sum (1 - u), sum (1 - e)} over the valid samples with edges[i] <= u < edges[i + 1] (nb <= 16).  One
+// workgroup, per-thread accumulators in LDS, fixed-order tree reduction: deterministic.
+constexpr int ECE_MAX_BINS = 16;
+__global__ __launch_bounds__(256) void eval_ece_bins_kernel(const float* err, const float* unc, long long n, const double* edges,
+                                                            int nb, double* bins) {
+  __shared__ double sm[ECE_MAX_BINS * 3][256];
+  __shared__ double ed[ECE_MAX_BINS + 1];
+  const int tid = threadIdx.x;
+  if (tid <= nb) ed[tid] = edges[tid];
+  for (int j = 0; j < nb * 3; ++j) sm[j][tid] = 0.0;
+  __syncthreads();
+  for (long long i = tid; i < n; i += 256) {
+    const float e = err[i], uf = unc[i];
+    if (!ece_valid(e, uf)) continue;
+    const double u = (double)uf;
+    for (int b = 0; b < nb; ++b) {
+      if (u >= ed[b] && u < ed[b + 1]) {
+        sm[3 * b][tid] += 1.0; sm[3 * b + 1][tid] += 1.0 - u; sm[3 * b + 2][tid] += 1.0 - (double)e;
+        break;
+      }
+    }
+  }
+  tree_sum_256(sm, nb * 3, tid);
+  if (tid < nb * 3) bins[tid] = sm[tid][0];
+}
 
 // ---- bootstrap draws: integer-only, restated bit for bit in mmdeer/synth.py (bootstrap_indices) --------------------------
 __host__ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
@@ -100,17 +278,7 @@ __global__ __launch_bounds__(256) void boot_partial_kernel(const float4* __restr
     for (int k = 0; k < 6; ++k) sm[d * 6 + k][tid] = a[d].s[k];
     sf[d * 4][tid] = a[d].pmin; sf[d * 4 + 1][tid] = a[d].pmax; sf[d * 4 + 2][tid] = a[d].tmin; sf[d * 4 + 3][tid] = a[d].tmax;
   }
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-#pragma unroll
-      for (int k = 0; k < 18; ++k) sm[k][tid] += sm[k][tid + off];
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        sf[k][tid] = (k & 1) ? fmaxf(sf[k][tid], sf[k][tid + off]) : fminf(sf[k][tid], sf[k][tid + off]);
-    }
-    __syncthreads();
-  }
+  tree_sum_256<18, 12>(sm, tid, sf);
   const size_t base = (size_t)r * S + s;
   if (tid < 18) part[base * 18 + tid] = sm[tid][0];
   if (tid >= 64 && tid < 76) mm[base * 12 + (tid - 64)] = sf[tid - 64][0];
@@ -256,9 +424,7 @@ constexpr int SORT_TILE = 2048;        // elements one workgroup sorts / merges 
 
 __device__ __forceinline__ unsigned sort_image(float f) {
   if (f != f) return 0xFFFFFFFFu;
-  unsigned u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return float_image(__float_as_uint(f) == 0x80000000u ? 0.f : f);
 }
 
 // blockIdx.y = column c: keys + c * col_step -> a + c * P (mmdeer_sort_pairs has one column; the network kernels alike)
@@ -346,12 +512,7 @@ __global__ __launch_bounds__(256) void rank_moments_kernel(const double* ra, con
     s[0] += x * x; s[1] += y * y; s[2] += x * y;
   }
   for (int k = 0; k < 3; ++k) sm[k][tid] = s[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off)
-      for (int k = 0; k < 3; ++k) sm[k][tid] += sm[k][tid + off];
-    __syncthreads();
-  }
+  tree_sum_256<3>(sm, tid);
   if (tid < 3) out[tid] = sm[tid][0];
 }
 
@@ -359,18 +520,13 @@ __global__ __launch_bounds__(256) void rank_moments_kernel(const double* ra, con
 constexpr int CAL_MAX_BINS = 32;
 constexpr int CAL_STATS = 4;   // per dimension: {max uncertainty, error threshold, bad flag, threshold is NaN}
 
-__device__ __forceinline__ unsigned cal_key(float f) {     // non-negative, non-NaN floats order like their bits
-  return __float_as_uint(f);
-}
-
 // workgroup (d, which): which = 0, 1 -> the two middle order statistics of |p - t| by a 4-pass radix selection (8 bits per
 // pass, integer histograms: exact); which = 2 -> max of unc and the "non-finite uncertainty" flag.  sel[d][4] (floats)
 __global__ __launch_bounds__(256) void cal_select_kernel(const float* pred, const float* target, const float* unc, long long n, int D,
                                                          float* sel) {
-  __shared__ unsigned hist[256];
+  __shared__ RadixScratch rs;
   __shared__ float fm[256];
-  __shared__ unsigned s_digit, s_bad;
-  __shared__ long long s_k;
+  __shared__ unsigned s_bad;
   const int tid = threadIdx.x, d = blockIdx.x, which = blockIdx.y;
   if (which == 2) {
     float m = -__builtin_inff();
@@ -404,31 +560,11 @@ __global__ __launch_bounds__(256) void cal_select_kernel(const float* pred, cons
     if (tid == 0) sel[d * 4 + which] = __builtin_nanf("");
     return;
   }
-  long long k = which ? n / 2 : (n - 1) / 2;
-  unsigned prefix = 0u, mask = 0u;
-  for (int pass = 3; pass >= 0; --pass) {
-    const int shift = 8 * pass;
-    hist[tid] = 0u;
-    __syncthreads();
-    for (long long i = tid; i < n; i += 256) {
-      const unsigned key = cal_key(fabsf(pred[i * D + d] - target[i * D + d]));
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      long long cum = 0;
-      unsigned dg = 0;
-      for (; dg < 255u; ++dg) {
-        if (k < cum + (long long)hist[dg]) break;
-        cum += hist[dg];
-      }
-      s_digit = dg; s_k = k - cum;
-    }
-    __syncthreads();
-    prefix |= s_digit << shift; mask |= 255u << shift; k = s_k;
-    __syncthreads();
-  }
-  if (tid == 0) sel[d * 4 + which] = __uint_as_float(prefix);
+  const unsigned sel_key = radix_select_256(n, which ? n / 2 : (n - 1) / 2, rs, tid, [&](long long i, unsigned& key) {
+    key = float_image(fabsf(pred[i * D + d] - target[i * D + d]));
+    return true;
+  });
+  if (tid == 0) sel[d * 4 + which] = image_float(sel_key);
 }
 
 // workgroup (d, rule * nb + b): {count, sum conf, sum acc} of bin b under rule 0 ([lo, hi), last bin closed: the reference's
@@ -459,12 +595,7 @@ __global__ __launch_bounds__(256) void cal_bins_kernel(const float* pred, const 
   }
   if (out) atomicOr(&s_out, 1u);
   for (int k = 0; k < 3; ++k) sm[k][tid] = s[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off)
-      for (int k = 0; k < 3; ++k) sm[k][tid] += sm[k][tid + off];
-    __syncthreads();
-  }
+  tree_sum_256<3>(sm, tid);
   if (tid < 3) bins[(((size_t)d * 2 + rule) * nb + b) * 3 + tid] = sm[tid][0];
   if (blockIdx.y == 0 && tid == 0) {
     stats[d * CAL_STATS] = (double)sel[d * 4 + 2];
@@ -493,15 +624,6 @@ struct UncCuts {
 };
 __host__ __forceinline__ int unc_chunks(long long N) { return (int)((N + UNC_CHUNK - 1) / UNC_CHUNK); }
 
-// fixed-order LDS tree over 256 lanes; the sum is in sm[0] afterwards
-__device__ __forceinline__ void tree_sum_256(double* sm, int tid) {
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) sm[tid] += sm[tid + off];
-    __syncthreads();
-  }
-}
-
 // workgroup (s, d): rows [s * per, (s + 1) * per), row i on lane (i - first) % 256.  Minima and maxima skip NaN (fminf would
 // drop it silently); the flag carries it and the last kernel writes NaN, as np.min / np.max do.
 __global__ __launch_bounds__(256) void unc_sums_kernel(const float* pred, const float* target, const float* unc, int N, int D, int S,
@@ -525,16 +647,9 @@ __global__ __launch_bounds__(256) void unc_sums_kernel(const float* pred, const 
   }
   sm[0][tid] = su; sm[1][tid] = se;
   sf[0][tid] = umin; sf[1][tid] = umax; sf[2][tid] = emin; sf[3][tid] = emax;
-  __syncthreads();
+  __syncthreads();                                   // s_flags is zero for everyone
   if (flags) atomicOr(&s_flags, flags);
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-      sm[0][tid] += sm[0][tid + off]; sm[1][tid] += sm[1][tid + off];
-      sf[0][tid] = fminf(sf[0][tid], sf[0][tid + off]); sf[1][tid] = fmaxf(sf[1][tid], sf[1][tid + off]);
-      sf[2][tid] = fminf(sf[2][tid], sf[2][tid + off]); sf[3][tid] = fmaxf(sf[3][tid], sf[3][tid + off]);
-    }
-    __syncthreads();
-  }
+  tree_sum_256<2, 4>(sm, tid, sf);
   double* out = part1 + ((size_t)d * S + s) * UNC_P1;
   if (tid < 2) out[tid] = sm[tid][0];
   else if (tid < 6) out[tid] = (double)sf[tid - 2][0];
@@ -573,12 +688,7 @@ __global__ __launch_bounds__(256) void unc_centred_kernel(const float* pred, con
     a[0] += du * du; a[1] += de * de; a[2] += du * de;
   }
   for (int k = 0; k < 3; ++k) sm[k][tid] = a[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off)
-      for (int k = 0; k < 3; ++k) sm[k][tid] += sm[k][tid + off];
-    __syncthreads();
-  }
+  tree_sum_256<3>(sm, tid);
   if (tid < 3) part2[((size_t)d * S + s) * 3 + tid] = sm[tid][0];
 }
 
@@ -587,7 +697,7 @@ __global__ __launch_bounds__(256) void unc_centred_kernel(const float* pred, con
 // index.  Position pos goes to lane (pos - first of the segment here) % 256; fixed LDS tree.  A NaN error stays a NaN sum.
 __global__ __launch_bounds__(256) void unc_prefix_kernel(const unsigned long long* a, long long P, const float* pred, const float* target,
                                                          int N, int D, int C, UncCuts cuts, double* seg) {
-  __shared__ double sm[256];
+  __shared__ double sm[1][256];
   const int tid = threadIdx.x, c = blockIdx.x, d = blockIdx.y;
   const unsigned long long* ad = a + (long long)d * P;
   const long long pos0 = (long long)c * UNC_CHUNK;
@@ -603,9 +713,9 @@ __global__ __launch_bounds__(256) void unc_prefix_kernel(const unsigned long lon
         const size_t row = (size_t)(unsigned)(ad[pos] & 0xFFFFFFFFull);       // < N: the padding sorts behind position N - 1
         v += (double)fabsf(pred[row * D + d] - target[row * D + d]);
       }
-      sm[tid] = v;
-      tree_sum_256(sm, tid);
-      total = sm[0];
+      sm[0][tid] = v;
+      tree_sum_256<1>(sm, tid);
+      total = sm[0][0];
       __syncthreads();
     }
     if (tid == 0) seg[((size_t)d * C + c) * UNC_MAX_CUTS + k] = total;
@@ -708,6 +818,35 @@ inline void launch_sort(const float* keys, long long stride, long long col_step,
 using namespace mmdeer;
 
 extern "C" {
+
+int mmdeer_eval_accumulate(const float* pred, const float* target, const float* unc, double* acc, float* sample_err,
+                           float* sample_unc, int B, void* stream) {
+  MMDEER_CHECK(B >= 0, "eval_accumulate: batch must be >= 0 (got %d)", B);
+  if (B == 0) return 0;
+  MMDEER_CHECK(pred && target && acc, "eval_accumulate: pred / target / acc must be non-NULL");
+  MMDEER_CHECK(!sample_unc || unc, "eval_accumulate: sample_unc needs unc");
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(4), dim3(256), 0, (hipStream_t)stream, pred, target, unc, acc, sample_err, sample_unc, B);
+  MMDEER_HIP(hipGetLastError());
+  return 0;
+}
+
+int mmdeer_eval_quantile_select(const float* err, const float* unc, long long n, int nq, float* vals, double* frac,
+                                long long* nvalid, void* stream) {
+  MMDEER_CHECK(err && unc && vals && frac && nvalid, "eval_quantile_select: NULL argument");
+  MMDEER_CHECK(n > 0 && nq >= 2 && nq <= 64, "eval_quantile_select: need n > 0 and 2 <= nq <= 64 (got n = %lld, nq = %d)", n, nq);
+  hipLaunchKernelGGL(eval_quantile_select_kernel, dim3(2 * nq), dim3(256), 0, (hipStream_t)stream, err, unc, n, nq, vals, frac, nvalid);
+  MMDEER_HIP(hipGetLastError());
+  return 0;
+}
+
+int mmdeer_eval_ece_bins(const float* err, const float* unc, long long n, const double* edges, int n_bins, double* bins,
+                         void* stream) {
+  MMDEER_CHECK(err && unc && edges && bins, "eval_ece_bins: NULL argument");
+  MMDEER_CHECK(n > 0 && n_bins >= 1 && n_bins <= ECE_MAX_BINS, "eval_ece_bins: need n > 0 and 1 <= n_bins <= %d (got %d)", ECE_MAX_BINS, n_bins);
+  hipLaunchKernelGGL(eval_ece_bins_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, err, unc, n, edges, n_bins, bins);
+  MMDEER_HIP(hipGetLastError());
+  return 0;
+}
 
 long long mmdeer_bootstrap_scratch(long long N, int R) {
   if (N <= 0 || R <= 0) return 0;

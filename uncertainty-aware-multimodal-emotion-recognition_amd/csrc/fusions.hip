@@ -6,39 +6,13 @@
 //                              the weight read as [out][I J], and the two contractions of its backward
 // The Linear layers of these modules run on mmdeer_gemm (mmdeer/fusions.py sequences them).  fp32 or bf16 storage, fp32
 // arithmetic; per-sample results only (batch reductions are dW-shaped GEMMs), so every result is deterministic.
-#include "common.h"
+#include "elem.h"
 
 #include "../../include/mmdeer.h"
 
 namespace mmdeer {
 namespace {
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <bool F32>
-__device__ __forceinline__ f32x4 fld4(const void* base, long long idx) {
-  if constexpr (F32) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-  } else {
-    const u32x2 a = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    return f32x4{__uint_as_float(a.x << 16), __uint_as_float(a.x & 0xFFFF0000u), __uint_as_float(a.y << 16), __uint_as_float(a.y & 0xFFFF0000u)};
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void fst4(void* base, long long idx, f32x4 v) {
-  if constexpr (F32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx) = v;
-  else *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(base) + idx) = u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
-}
-template <bool F32>
-__device__ __forceinline__ float fld1(const void* base, long long idx) {
-  if constexpr (F32) return reinterpret_cast<const float*>(base)[idx];
-  else return bf2f(reinterpret_cast<const bf16_t*>(base)[idx]);
-}
-template <bool F32>
-__device__ __forceinline__ void fst1(void* base, long long idx, float v) {
-  if constexpr (F32) reinterpret_cast<float*>(base)[idx] = v;
-  else reinterpret_cast<bf16_t*>(base)[idx] = f2bf(v);
-}
 __device__ __forceinline__ float dot4f(f32x4 a, f32x4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 
 constexpr int MIX_MAX_S = 8;
@@ -68,7 +42,7 @@ __global__ __launch_bounds__(256) void softmax_mix_fwd_kernel(const MixArgs a) {
       if (a.w_att) {
         float acc = 0.f;
         for (int c = lane * 4; c < a.D; c += 256)
-          acc += dot4f(fld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c), *reinterpret_cast<const f32x4*>(a.w_att + c));
+          acc += dot4f(ld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c), *reinterpret_cast<const f32x4*>(a.w_att + c));
         lg[s] = wave_sum(acc) + a.b_att[0];
       } else {
         lg[s] = a.logits[(long long)b * a.ldl + s];
@@ -91,8 +65,8 @@ __global__ __launch_bounds__(256) void softmax_mix_fwd_kernel(const MixArgs a) {
     f32x4 o{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < MIX_MAX_S; ++s)
-      if (s < a.S) o += w[s] * fld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c);
-    fst4<F32>(a.out, (long long)b * a.ld_out + c, o);
+      if (s < a.S) o += w[s] * ld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c);
+    st4<F32>(a.out, (long long)b * a.ld_out + c, o);
   }
 }
 
@@ -109,7 +83,7 @@ __global__ __launch_bounds__(256) void softmax_mix_bwd_kernel(const MixArgs a) {
     if (s < a.S) {
       float acc = 0.f;
       for (int c = lane * 4; c < a.D; c += 256)
-        acc += dot4f(fld4<F32>(a.dout, (long long)b * a.ld_do + c), fld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c));
+        acc += dot4f(ld4<F32>(a.dout, (long long)b * a.ld_do + c), ld4<F32>(a.P, (long long)b * a.ldp + s * a.sp + c));
       dw[s] = wave_sum(acc);
     }
   }
@@ -120,35 +94,35 @@ __global__ __launch_bounds__(256) void softmax_mix_bwd_kernel(const MixArgs a) {
 #pragma unroll
   for (int s = 0; s < MIX_MAX_S; ++s) ds[s] = w[s] * (dw[s] - dot);     // zero beyond S (w = 0)
   if (lane == 0) {
-    fst4<F32>(a.dlogits8, 8ll * b, f32x4{ds[0], ds[1], ds[2], ds[3]});
-    fst4<F32>(a.dlogits8, 8ll * b + 4, f32x4{ds[4], ds[5], ds[6], ds[7]});
+    st4<F32>(a.dlogits8, 8ll * b, f32x4{ds[0], ds[1], ds[2], ds[3]});
+    st4<F32>(a.dlogits8, 8ll * b + 4, f32x4{ds[4], ds[5], ds[6], ds[7]});
   }
   for (int c = lane * 4; c < a.D; c += 256) {
-    const f32x4 g = fld4<F32>(a.dout, (long long)b * a.ld_do + c);
+    const f32x4 g = ld4<F32>(a.dout, (long long)b * a.ld_do + c);
     f32x4 wa{0.f, 0.f, 0.f, 0.f};
     if (a.w_att) wa = *reinterpret_cast<const f32x4*>(a.w_att + c);
 #pragma unroll
     for (int s = 0; s < MIX_MAX_S; ++s)
-      if (s < a.S) fst4<F32>(a.dP, (long long)b * a.ldp + s * a.sp + c, w[s] * g + ds[s] * wa);
+      if (s < a.S) st4<F32>(a.dP, (long long)b * a.ldp + s * a.sp + c, w[s] * g + ds[s] * wa);
   }
 }
 
 template <bool F32>
-__global__ __launch_bounds__(256) void outer_fwd_kernel(const void* x1, int ld1, const void* x2, int ld2, void* z, int I, int J, int B) {
+__global__ __launch_bounds__(256) void outer_fwd_kernel(const void* x1, int ldx1, const void* x2, int ldx2, void* z, int I, int J, int B) {
   const int per_i = J / 4;
   const long long per_b = (long long)I * per_i, total = per_b * B;
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
     const int b = (int)(e / per_b);
     const long long r = e - b * per_b;
     const int i = (int)(r / per_i), j = (int)(r - (long long)i * per_i) * 4;
-    const float u = fld1<F32>(x1, (long long)b * ld1 + i);
-    fst4<F32>(z, (long long)b * I * J + (long long)i * J + j, u * fld4<F32>(x2, (long long)b * ld2 + j));
+    const float u = ld1<F32>(x1, (long long)b * ldx1 + i);
+    st4<F32>(z, (long long)b * I * J + (long long)i * J + j, u * ld4<F32>(x2, (long long)b * ldx2 + j));
   }
 }
 
 // one workgroup per sample: wave v takes rows i = v, v + 4, ...; lane l columns 4 l + 256 t (t < 4: J <= 1024)
 template <bool F32>
-__global__ __launch_bounds__(256) void outer_bwd_kernel(const void* dz, const void* x1, int ld1, const void* x2, int ld2, void* dx1, int ldd1,
+__global__ __launch_bounds__(256) void outer_bwd_kernel(const void* dz, const void* x1, int ldx1, const void* x2, int ldx2, void* dx1, int ldd1,
                                                         void* dx2, int ldd2, int I, int J) {
   __shared__ f32x4 red[4][256];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -156,23 +130,23 @@ __global__ __launch_bounds__(256) void outer_bwd_kernel(const void* dz, const vo
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int c = lane * 4 + 256 * t;
-    v2[t] = c < J ? fld4<F32>(x2, (long long)b * ld2 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    v2[t] = c < J ? ld4<F32>(x2, (long long)b * ldx2 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int i = wave; i < I; i += 4) {
-    const float u = fld1<F32>(x1, (long long)b * ld1 + i);
+    const float u = ld1<F32>(x1, (long long)b * ldx1 + i);
     float d = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = lane * 4 + 256 * t;
       if (c < J) {
-        const f32x4 g = fld4<F32>(dz, ((long long)b * I + i) * J + c);
+        const f32x4 g = ld4<F32>(dz, ((long long)b * I + i) * J + c);
         d += dot4f(g, v2[t]);
         acc[t] += u * g;
       }
     }
     d = wave_sum(d);
-    if (lane == 0) fst1<F32>(dx1, (long long)b * ldd1 + i, d);
+    if (lane == 0) st1<F32>(dx1, (long long)b * ldd1 + i, d);
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) red[wave][lane + 64 * t] = acc[t];
@@ -181,7 +155,7 @@ __global__ __launch_bounds__(256) void outer_bwd_kernel(const void* dz, const vo
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int c = lane * 4 + 256 * t;
-      if (c < J) fst4<F32>(dx2, (long long)b * ldd2 + c, (red[0][lane + 64 * t] + red[1][lane + 64 * t]) + (red[2][lane + 64 * t] + red[3][lane + 64 * t]));
+      if (c < J) st4<F32>(dx2, (long long)b * ldd2 + c, (red[0][lane + 64 * t] + red[1][lane + 64 * t]) + (red[2][lane + 64 * t] + red[3][lane + 64 * t]));
     }
   }
 }
@@ -219,9 +193,7 @@ int mmdeer_softmax_mix_fwd(const mmdeer_softmax_mix_args* p) {
   if (p->B == 0) return 0;
   const MixArgs a = to_mix(p);
   const dim3 grid((p->B + 3) / 4);
-  if (p->act_f32) hipLaunchKernelGGL(softmax_mix_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)p->stream, a);
-  else hipLaunchKernelGGL(softmax_mix_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)p->stream, a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(softmax_mix_fwd_kernel, p->act_f32, grid, dim3(256), (hipStream_t)p->stream, a);
   return 0;
 }
 
@@ -230,9 +202,7 @@ int mmdeer_softmax_mix_bwd(const mmdeer_softmax_mix_args* p) {
   if (p->B == 0) return 0;
   const MixArgs a = to_mix(p);
   const dim3 grid((p->B + 3) / 4);
-  if (p->act_f32) hipLaunchKernelGGL(softmax_mix_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)p->stream, a);
-  else hipLaunchKernelGGL(softmax_mix_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)p->stream, a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(softmax_mix_bwd_kernel, p->act_f32, grid, dim3(256), (hipStream_t)p->stream, a);
   return 0;
 }
 
@@ -241,9 +211,7 @@ int mmdeer_outer_fwd(const void* x1, int ld1, const void* x2, int ld2, void* z, 
   if (B == 0) return 0;
   MMDEER_CHECK(x1 && x2 && z && ld1 >= I && ld2 >= J && ld2 % 4 == 0, "outer_fwd: bad pointer or leading dimension");
   const unsigned grid = grid_for_((long long)B * I * (J / 4));
-  if (act_f32) hipLaunchKernelGGL(outer_fwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x1, ld1, x2, ld2, z, I, J, B);
-  else hipLaunchKernelGGL(outer_fwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x1, ld1, x2, ld2, z, I, J, B);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(outer_fwd_kernel, act_f32, dim3(grid), dim3(256), (hipStream_t)stream, x1, ld1, x2, ld2, z, I, J, B);
   return 0;
 }
 
@@ -253,9 +221,7 @@ int mmdeer_outer_bwd(const void* dz, const void* x1, int ld1, const void* x2, in
   if (B == 0) return 0;
   MMDEER_CHECK(dz && x1 && x2 && dx1 && dx2 && ld1 >= I && ldd1 >= I && ld2 >= J && ldd2 >= J && ld2 % 4 == 0 && ldd2 % 4 == 0,
                "outer_bwd: bad pointer or leading dimension");
-  if (act_f32) hipLaunchKernelGGL(outer_bwd_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, dz, x1, ld1, x2, ld2, dx1, ldd1, dx2, ldd2, I, J);
-  else hipLaunchKernelGGL(outer_bwd_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, dz, x1, ld1, x2, ld2, dx1, ldd1, dx2, ldd2, I, J);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(outer_bwd_kernel, act_f32, dim3(B), dim3(256), (hipStream_t)stream, dz, x1, ld1, x2, ld2, dx1, ldd1, dx2, ldd2, I, J);
   return 0;
 }
 

@@ -16,15 +16,13 @@
 // dz W1, a GEMM of the caller), dz, dw2 (per-workgroup partials folded in index order by a second launch: deterministic) and
 // db2 = 0: b2 shifts every score of a sample equally, so the softmax does not depend on it.
 #include "../../include/mmdeer.h"
-#include "common.h"
+#include "elem.h"
 
 namespace mmdeer {
 namespace {
 
 constexpr int SEQ_H = 256;          // hidden units per direction (the reference's hidden_dim 512 / 2)
 constexpr int SEQ_G = 4 * SEQ_H;    // gate columns per direction
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 template <bool F32> struct SeqCfg;
 template <> struct SeqCfg<false> {
@@ -37,7 +35,7 @@ template <> struct SeqCfg<true> {
 };
 
 template <bool F32>
-__device__ __forceinline__ f32x4 mma16(const u32x4_t& a, const u32x4_t& b, f32x4 acc) {
+__device__ __forceinline__ f32x4 mma16(const u32x4& a, const u32x4& b, f32x4 acc) {
   if constexpr (!F32) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
   } else {
@@ -50,39 +48,6 @@ __device__ __forceinline__ f32x4 mma16(const u32x4_t& a, const u32x4_t& b, f32x4
   }
 }
 
-template <bool F32>
-__device__ __forceinline__ float ldE(const void* base, long long idx) {
-  if constexpr (F32) return reinterpret_cast<const float*>(base)[idx];
-  else return bf2f(reinterpret_cast<const bf16_t*>(base)[idx]);
-}
-template <bool F32>
-__device__ __forceinline__ void stE(void* base, long long idx, float v) {
-  if constexpr (F32) reinterpret_cast<float*>(base)[idx] = v;
-  else reinterpret_cast<bf16_t*>(base)[idx] = f2bf(v);
-}
-template <bool F32>
-__device__ __forceinline__ f32x4 ld4E(const void* base, long long idx) {
-  if constexpr (F32) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-  } else {
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    const u32x2_t a = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    return f32x4{__uint_as_float(a.x << 16), __uint_as_float(a.x & 0xFFFF0000u), __uint_as_float(a.y << 16),
-                 __uint_as_float(a.y & 0xFFFF0000u)};
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void st4E(void* base, long long idx, f32x4 v) {
-  if constexpr (F32) {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx) = v;
-  } else {
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    *reinterpret_cast<u32x2_t*>(reinterpret_cast<bf16_t*>(base) + idx) = u32x2_t{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
-  }
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
 // image[d][n][k] = W_d[n][k], image_t[d][k][n] = W_d[n][k] (compute dtype); W_d fp32 [4H][H]
 template <bool F32>
 __global__ __launch_bounds__(256) void lstm_seq_pack_kernel(const float* wf, const float* wr, void* img, void* img_t) {
@@ -92,8 +57,8 @@ __global__ __launch_bounds__(256) void lstm_seq_pack_kernel(const float* wf, con
     const long long r = e - d * per;
     const int n = (int)(r / SEQ_H), k = (int)(r - (long long)n * SEQ_H);
     const float v = (d ? wr : wf)[r];
-    stE<F32>(img, e, v);
-    if (img_t) stE<F32>(img_t, d * per + (long long)k * SEQ_G + n, v);
+    st1<F32>(img, e, v);
+    if (img_t) st1<F32>(img_t, d * per + (long long)k * SEQ_G + n, v);
   }
 }
 
@@ -129,14 +94,14 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_kernel(mmdeer_lstm_seq_args 
       const E* hp = hs[(s - 1) & 1];
 #pragma unroll 2
       for (int kc = 0; kc < H / KC; ++kc) {
-        u32x4_t af[MT];
+        u32x4 af[MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) af[m] = *reinterpret_cast<const u32x4_t*>(hp + (m * 16 + lr) * LDS_LD + kc * KC + lg * EPL);
+        for (int m = 0; m < MT; ++m) af[m] = *reinterpret_cast<const u32x4*>(hp + (m * 16 + lr) * LDS_LD + kc * KC + lg * EPL);
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
           for (int jt = 0; jt < 4; ++jt) {
-            const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(W + (long long)(g * H + w * 64 + jt * 16 + lr) * H + kc * KC + lg * EPL);
+            const u32x4 bf = *reinterpret_cast<const u32x4*>(W + (long long)(g * H + w * 64 + jt * 16 + lr) * H + kc * KC + lg * EPL);
 #pragma unroll
             for (int m = 0; m < MT; ++m) acc[m][g][jt] = mma16<F32>(af[m], bf, acc[m][g][jt]);
           }
@@ -154,10 +119,10 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_kernel(mmdeer_lstm_seq_args 
           if (b < B) {
             const long long row = (long long)t * B + b;
             const long long xo = row * a.ld_xg + d * G4 + j;
-            const float si = sigm(acc[m][0][jt][i] + ldE<F32>(a.xg, xo));
-            const float sf = sigm(acc[m][1][jt][i] + ldE<F32>(a.xg, xo + H));
-            const float tg = tanhf(acc[m][2][jt][i] + ldE<F32>(a.xg, xo + 2 * H));
-            const float so = sigm(acc[m][3][jt][i] + ldE<F32>(a.xg, xo + 3 * H));
+            const float si = sigmoidf_(acc[m][0][jt][i] + ld1<F32>(a.xg, xo));
+            const float sf = sigmoidf_(acc[m][1][jt][i] + ld1<F32>(a.xg, xo + H));
+            const float tg = tanhf(acc[m][2][jt][i] + ld1<F32>(a.xg, xo + 2 * H));
+            const float so = sigmoidf_(acc[m][3][jt][i] + ld1<F32>(a.xg, xo + 3 * H));
             const float c = sf * cst[m][jt][i] + si * tg;
             cst[m][jt][i] = c;
             hv = so * tanhf(c);
@@ -166,9 +131,9 @@ __global__ __launch_bounds__(256) void lstm_seq_fwd_kernel(mmdeer_lstm_seq_args 
               gt[0] = si; gt[H] = sf; gt[2 * H] = tg; gt[3 * H] = so;
               a.tape_c[row * (2 * H) + d * H + j] = c;
             }
-            stE<F32>(a.h, row * a.ld_h + d * H + j, hv);
+            st1<F32>(a.h, row * a.ld_h + d * H + j, hv);
           }
-          stE<F32>(hn, r * LDS_LD + j, hv);       // rows past B stay zero: the MFMA reads whole tiles
+          st1<F32>(hn, r * LDS_LD + j, hv);       // rows past B stay zero: the MFMA reads whole tiles
         }
     __syncthreads();
   }
@@ -211,7 +176,7 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(mmdeer_lstm_seq_args 
           float dg[4] = {0.f, 0.f, 0.f, 0.f};
           if (b < B) {
             const long long row = (long long)t * B + b;
-            const float dh = ldE<F32>(a.dh_out, row * a.ld_dh + d * H + j) + acc[m][jt][i];
+            const float dh = ld1<F32>(a.dh_out, row * a.ld_dh + d * H + j) + acc[m][jt][i];
             const float* gt = a.tape_gates + row * (2 * G4) + d * G4 + j;
             const float si = gt[0], sf = gt[H], tg = gt[2 * H], so = gt[3 * H];
             const float c = a.tape_c[row * (2 * H) + d * H + j];
@@ -225,10 +190,10 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(mmdeer_lstm_seq_args 
             dg[3] = dh * tc * so * (1.f - so);
             const long long go = row * a.ld_dg + d * G4 + j;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) stE<F32>(a.dgates, go + g * H, dg[g]);
+            for (int g = 0; g < 4; ++g) st1<F32>(a.dgates, go + g * H, dg[g]);
           }
 #pragma unroll
-          for (int g = 0; g < 4; ++g) stE<F32>(gs, r * LDS_LD + g * H + j, dg[g]);
+          for (int g = 0; g < 4; ++g) st1<F32>(gs, r * LDS_LD + g * H + j, dg[g]);
         }
     __syncthreads();
     if (s + 1 < T) {
@@ -238,12 +203,12 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(mmdeer_lstm_seq_args 
         for (int jt = 0; jt < 4; ++jt) acc[m][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
       for (int kc = 0; kc < G4 / KC; ++kc) {
-        u32x4_t af[MT];
+        u32x4 af[MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) af[m] = *reinterpret_cast<const u32x4_t*>(gs + (m * 16 + lr) * LDS_LD + kc * KC + lg * EPL);
+        for (int m = 0; m < MT; ++m) af[m] = *reinterpret_cast<const u32x4*>(gs + (m * 16 + lr) * LDS_LD + kc * KC + lg * EPL);
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
-          const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(WT + (long long)(w * 64 + jt * 16 + lr) * G4 + kc * KC + lg * EPL);
+          const u32x4 bf = *reinterpret_cast<const u32x4*>(WT + (long long)(w * 64 + jt * 16 + lr) * G4 + kc * KC + lg * EPL);
 #pragma unroll
           for (int m = 0; m < MT; ++m) acc[m][jt] = mma16<F32>(af[m], bf, acc[m][jt]);
         }
@@ -256,7 +221,7 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(mmdeer_lstm_seq_args 
 // ---- attention pool over time: one wave per sample; lane l owns z columns 4l .. 4l+3 and h columns 8l .. 8l+7
 template <bool F32>
 __device__ __forceinline__ float pool_score(const mmdeer_temporal_pool_args& a, long long row, const f32x4& w2, float b2, int lane) {
-  const f32x4 z = ld4E<F32>(a.z, row * a.ld_z + lane * 4);
+  const f32x4 z = ld4<F32>(a.z, row * a.ld_z + lane * 4);
   const float s = w2.x * tanhf(z.x) + w2.y * tanhf(z.y) + w2.z * tanhf(z.z) + w2.w * tanhf(z.w);
   return wave_sum(s) + b2;
 }
@@ -281,11 +246,11 @@ __global__ __launch_bounds__(256) void temporal_pool_fwd_kernel(mmdeer_temporal_
     const long long row = (long long)t * B + b;
     const float at = expf(pool_score<F32>(a, row, w2, b2, lane) - mx) * inv;
     if (lane == 0) a.weights[(long long)b * T + t] = at;
-    o0 += at * ld4E<F32>(a.h, row * a.ld_h + lane * 8);
-    o1 += at * ld4E<F32>(a.h, row * a.ld_h + lane * 8 + 4);
+    o0 += at * ld4<F32>(a.h, row * a.ld_h + lane * 8);
+    o1 += at * ld4<F32>(a.h, row * a.ld_h + lane * 8 + 4);
   }
-  st4E<F32>(a.attended, (long long)b * a.ld_att + lane * 8, o0);
-  st4E<F32>(a.attended, (long long)b * a.ld_att + lane * 8 + 4, o1);
+  st4<F32>(a.attended, (long long)b * a.ld_att + lane * 8, o0);
+  st4<F32>(a.attended, (long long)b * a.ld_att + lane * 8 + 4, o1);
 }
 
 constexpr int POOL_BWD_WG = 256;   // workgroups of the backward: one fp32 [256] partial of dw2 each
@@ -297,25 +262,25 @@ __global__ __launch_bounds__(256) void temporal_pool_bwd_kernel(mmdeer_temporal_
   const f32x4 w2 = *reinterpret_cast<const f32x4*>(a.w2 + lane * 4);
   f32x4 pw{0.f, 0.f, 0.f, 0.f};
   for (int b = blockIdx.x * 4 + w; b < B; b += gridDim.x * 4) {
-    const f32x4 d0 = ld4E<F32>(a.dout, (long long)b * a.ld_dout + lane * 8), d1 = ld4E<F32>(a.dout, (long long)b * a.ld_dout + lane * 8 + 4);
+    const f32x4 d0 = ld4<F32>(a.dout, (long long)b * a.ld_dout + lane * 8), d1 = ld4<F32>(a.dout, (long long)b * a.ld_dout + lane * 8 + 4);
     float dot = 0.f;                               // sum_t a_t (dout . h_t)
     for (int t = 0; t < T; ++t) {
       const long long row = (long long)t * B + b;
-      const f32x4 h0 = ld4E<F32>(a.h, row * a.ld_h + lane * 8), h1 = ld4E<F32>(a.h, row * a.ld_h + lane * 8 + 4);
+      const f32x4 h0 = ld4<F32>(a.h, row * a.ld_h + lane * 8), h1 = ld4<F32>(a.h, row * a.ld_h + lane * 8 + 4);
       const f32x4 p = d0 * h0 + d1 * h1;
       dot += a.weights[(long long)b * T + t] * wave_sum(p.x + p.y + p.z + p.w);
     }
     for (int t = 0; t < T; ++t) {
       const long long row = (long long)t * B + b;
       const float at = a.weights[(long long)b * T + t];
-      const f32x4 h0 = ld4E<F32>(a.h, row * a.ld_h + lane * 8), h1 = ld4E<F32>(a.h, row * a.ld_h + lane * 8 + 4);
+      const f32x4 h0 = ld4<F32>(a.h, row * a.ld_h + lane * 8), h1 = ld4<F32>(a.h, row * a.ld_h + lane * 8 + 4);
       const f32x4 p = d0 * h0 + d1 * h1;
       const float ds = at * (wave_sum(p.x + p.y + p.z + p.w) - dot);
-      st4E<F32>(a.dh, row * a.ld_dh + lane * 8, at * d0);
-      st4E<F32>(a.dh, row * a.ld_dh + lane * 8 + 4, at * d1);
-      const f32x4 z = ld4E<F32>(a.z, row * a.ld_z + lane * 4);
+      st4<F32>(a.dh, row * a.ld_dh + lane * 8, at * d0);
+      st4<F32>(a.dh, row * a.ld_dh + lane * 8 + 4, at * d1);
+      const f32x4 z = ld4<F32>(a.z, row * a.ld_z + lane * 4);
       const f32x4 tz{tanhf(z.x), tanhf(z.y), tanhf(z.z), tanhf(z.w)};
-      st4E<F32>(a.dz, row * a.ld_dz + lane * 4, ds * w2 * (1.f - tz * tz));
+      st4<F32>(a.dz, row * a.ld_dz + lane * 4, ds * w2 * (1.f - tz * tz));
       pw += ds * tz;
     }
   }
@@ -333,8 +298,6 @@ __global__ __launch_bounds__(256) void temporal_pool_fold_kernel(const float* sc
   dw2[k] = s;
   if (k == 0) db2[0] = 0.f;
 }
-
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int check_seq(const mmdeer_lstm_seq_args* a, bool bwd) {
   const char* op = bwd ? "lstm_seq_bwd" : "lstm_seq_fwd";
@@ -397,9 +360,7 @@ int mmdeer_lstm_seq_pack(const float* w_hh_fwd, const float* w_hh_rev, int hidde
   MMDEER_CHECK(hidden == SEQ_H, "lstm_seq_pack: hidden must be %d (got %d)", SEQ_H, hidden);
   MMDEER_CHECK(w_hh_fwd && w_hh_rev && image, "lstm_seq_pack: NULL pointer (w_hh_fwd, w_hh_rev, image)");
   const unsigned grid = 1024;
-  if (act_f32) hipLaunchKernelGGL(lstm_seq_pack_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_hh_fwd, w_hh_rev, image, image_t);
-  else hipLaunchKernelGGL(lstm_seq_pack_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_hh_fwd, w_hh_rev, image, image_t);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(lstm_seq_pack_kernel, act_f32, dim3(grid), dim3(256), (hipStream_t)stream, w_hh_fwd, w_hh_rev, image, image_t);
   return 0;
 }
 
@@ -408,9 +369,7 @@ int mmdeer_lstm_seq_fwd(const mmdeer_lstm_seq_args* a) {
   if (a->T == 0 || a->B == 0) return 0;
   const int bt = a->act_f32 ? SeqCfg<true>::BT : SeqCfg<false>::BT;
   const dim3 grid((unsigned)((a->B + bt - 1) / bt), 2);
-  if (a->act_f32) hipLaunchKernelGGL(lstm_seq_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(lstm_seq_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(lstm_seq_fwd_kernel, a->act_f32, grid, dim3(256), (hipStream_t)a->stream, *a);
   return 0;
 }
 
@@ -419,9 +378,7 @@ int mmdeer_lstm_seq_bwd(const mmdeer_lstm_seq_args* a) {
   if (a->T == 0 || a->B == 0) return 0;
   const int bt = a->act_f32 ? SeqCfg<true>::BT : SeqCfg<false>::BT;
   const dim3 grid((unsigned)((a->B + bt - 1) / bt), 2);
-  if (a->act_f32) hipLaunchKernelGGL(lstm_seq_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(lstm_seq_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(lstm_seq_bwd_kernel, a->act_f32, grid, dim3(256), (hipStream_t)a->stream, *a);
   return 0;
 }
 
@@ -429,9 +386,7 @@ int mmdeer_temporal_pool_fwd(const mmdeer_temporal_pool_args* a) {
   if (check_pool(a, false) != 0) return -1;
   if (a->T == 0 || a->B == 0) return 0;
   const dim3 grid((unsigned)((a->B + 3) / 4));
-  if (a->act_f32) hipLaunchKernelGGL(temporal_pool_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(temporal_pool_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(temporal_pool_fwd_kernel, a->act_f32, grid, dim3(256), (hipStream_t)a->stream, *a);
   return 0;
 }
 
@@ -440,9 +395,7 @@ int mmdeer_temporal_pool_bwd(const mmdeer_temporal_pool_args* a) {
   if (a->T == 0 || a->B == 0) return 0;
   int nwg = (a->B + 3) / 4;
   if (nwg > POOL_BWD_WG) nwg = POOL_BWD_WG;
-  if (a->act_f32) hipLaunchKernelGGL(temporal_pool_bwd_kernel<true>, dim3(nwg), dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(temporal_pool_bwd_kernel<false>, dim3(nwg), dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(temporal_pool_bwd_kernel, a->act_f32, dim3(nwg), dim3(256), (hipStream_t)a->stream, *a);
   hipLaunchKernelGGL(temporal_pool_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
   MMDEER_HIP(hipGetLastError());
   return 0;

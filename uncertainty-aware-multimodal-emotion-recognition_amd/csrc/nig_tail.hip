@@ -17,6 +17,7 @@
 //                 thread over the part's samples in index order -> one partial per part.
 //   tail_bwd_fold: dw, db = the P partials added in index order.  Two runs give identical bits.
 #include "../../include/mmdeer.h"
+#include "elem.h"
 #include "nig_dev.h"
 
 namespace mmdeer {
@@ -25,35 +26,6 @@ namespace {
 constexpr int TAIL_ROWS = 64;        // samples per workgroup (4 lanes each)
 constexpr int TAIL_MAX_PARTS = 64;   // batch parts of the weight gradient
 constexpr int TAIL_PANEL = 256;      // weight columns staged per pass of the backward
-
-typedef unsigned tail_u32x4 __attribute__((ext_vector_type(4)));
-
-// 8 consecutive elements of the activation dtype as floats (two 16-byte loads in fp32, one in bf16)
-template <bool F32>
-__device__ __forceinline__ void load8(const void* base, long long idx, float (&x)[8]) {
-  if constexpr (F32) {
-    const float* p = reinterpret_cast<const float*>(base) + idx;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-  } else {
-    const tail_u32x4 a = *reinterpret_cast<const tail_u32x4*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    x[0] = __uint_as_float(a.x << 16); x[1] = __uint_as_float(a.x & 0xFFFF0000u);
-    x[2] = __uint_as_float(a.y << 16); x[3] = __uint_as_float(a.y & 0xFFFF0000u);
-    x[4] = __uint_as_float(a.z << 16); x[5] = __uint_as_float(a.z & 0xFFFF0000u);
-    x[6] = __uint_as_float(a.w << 16); x[7] = __uint_as_float(a.w & 0xFFFF0000u);
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void store8(void* base, long long idx, const float (&x)[8]) {
-  if constexpr (F32) {
-    float* p = reinterpret_cast<float*>(base) + idx;
-    *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
-    *reinterpret_cast<f32x4*>(p + 4) = f32x4{x[4], x[5], x[6], x[7]};
-  } else {
-    *reinterpret_cast<tail_u32x4*>(reinterpret_cast<bf16_t*>(base) + idx) =
-        tail_u32x4{pack_bf2(x[0], x[1]), pack_bf2(x[2], x[3]), pack_bf2(x[4], x[5]), pack_bf2(x[6], x[7])};
-  }
-}
 
 // rows [0, R) x columns [c0, c0 + cols) of the net's [R][K] weights -> LDS [R][cols], 16 bytes per thread and step
 template <bool F32>
@@ -66,7 +38,7 @@ __device__ __forceinline__ void stage_w(const void* w, long long net_off, int R,
     if constexpr (F32)
       reinterpret_cast<f32x4*>(lds)[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(w) + src);
     else
-      reinterpret_cast<tail_u32x4*>(lds)[i] = *reinterpret_cast<const tail_u32x4*>(reinterpret_cast<const bf16_t*>(w) + src);
+      reinterpret_cast<u32x4*>(lds)[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(w) + src);
   }
 }
 
@@ -86,11 +58,11 @@ __global__ __launch_bounds__(256) void evidence_tail_fwd_kernel(mmdeer_evidence_
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = q; c < nchunk; c += 4) {
       float x[8];
-      load8<F32>(a.x, xrow + 8 * c, x);
+      ld8<F32>(a.x, xrow + 8 * c, x);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float w[8];
-        load8<F32>(tail_lds, (long long)(4 * o + j) * K + 8 * c, w);
+        ld8<F32>(tail_lds, (long long)(4 * o + j) * K + 8 * c, w);
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[j] = fmaf(x[i], w[i], acc[j]);
       }
@@ -176,18 +148,18 @@ __global__ __launch_bounds__(256) void evidence_tail_bwd_dx_kernel(mmdeer_eviden
       for (int r = 0; r < R; ++r) {
         const float d = de[s * ldd + r];
         float w[8];
-        load8<F32>(wl, (long long)r * cols + 8 * c, w);
+        ld8<F32>(wl, (long long)r * cols + 8 * c, w);
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = fmaf(d, w[i], acc[i]);
       }
       const long long col = (long long)g * K + c0 + 8 * c;
       if (scale > 0.f) {
         float x[8];
-        load8<F32>(a.x, (long long)b * a.ld_x + col, x);
+        ld8<F32>(a.x, (long long)b * a.ld_x + col, x);
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = x[i] > 0.f ? acc[i] * scale : 0.f;
       }
-      store8<F32>(a.dx, (long long)b * a.ld_dx + col, acc);
+      st8<F32>(a.dx, (long long)b * a.ld_dx + col, acc);
     }
   }
 }
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(256) void evidence_tail_bwd_dw_kernel(mmdeer_eviden
     for (int h = 0; h < 2; ++h) {
       const int c = 16 * q + 8 * h;
       float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (live && k0 + c < K) load8<F32>(a.x, (long long)b * a.ld_x + (long long)g * K + k0 + c, x);
+      if (live && k0 + c < K) ld8<F32>(a.x, (long long)b * a.ld_x + (long long)g * K + k0 + c, x);
 #pragma unroll
       for (int i = 0; i < 8; ++i) xs[s][c + i] = x[i];
     }
@@ -261,8 +233,6 @@ __global__ __launch_bounds__(256) void evidence_tail_bwd_fold_kernel(const float
   if (i < nw) dw[i] = sum;
   else db[i - nw] = sum;
 }
-
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int tail_parts(int B) {
   const int nblk = (B + TAIL_ROWS - 1) / TAIL_ROWS;
@@ -322,9 +292,7 @@ int mmdeer_evidence_tail_fwd(const mmdeer_evidence_tail_args* a) {
   if (a->B == 0) return 0;
   const dim3 grid((unsigned)((a->B + TAIL_ROWS - 1) / TAIL_ROWS), (unsigned)a->G);
   const size_t lds = (size_t)4 * a->O * a->K * (a->act_f32 ? 4 : 2);
-  if (a->act_f32) hipLaunchKernelGGL(evidence_tail_fwd_kernel<true>, grid, dim3(256), lds, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(evidence_tail_fwd_kernel<false>, grid, dim3(256), lds, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT_LDS(evidence_tail_fwd_kernel, a->act_f32, grid, dim3(256), lds, (hipStream_t)a->stream, *a);
   return 0;
 }
 
@@ -345,13 +313,9 @@ int mmdeer_evidence_tail_bwd(const mmdeer_evidence_tail_args* a) {
   const dim3 grid((unsigned)((a->B + TAIL_ROWS - 1) / TAIL_ROWS), (unsigned)a->G);
   const int cols = a->K < TAIL_PANEL ? a->K : TAIL_PANEL;
   const size_t lds = (size_t)((TAIL_ROWS * (R + 1) * 4 + 15) & ~15) + (size_t)R * cols * (a->act_f32 ? 4 : 2);
-  if (a->act_f32) hipLaunchKernelGGL(evidence_tail_bwd_dx_kernel<true>, grid, dim3(256), lds, s, *a, devid);
-  else hipLaunchKernelGGL(evidence_tail_bwd_dx_kernel<false>, grid, dim3(256), lds, s, *a, devid);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT_LDS(evidence_tail_bwd_dx_kernel, a->act_f32, grid, dim3(256), lds, s, *a, devid);
   const dim3 gw((unsigned)((a->K + 63) / 64), (unsigned)a->G, (unsigned)P);
-  if (a->act_f32) hipLaunchKernelGGL(evidence_tail_bwd_dw_kernel<true>, gw, dim3(256), 0, s, *a, (const float*)devid, pw, pb);
-  else hipLaunchKernelGGL(evidence_tail_bwd_dw_kernel<false>, gw, dim3(256), 0, s, *a, (const float*)devid, pw, pb);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(evidence_tail_bwd_dw_kernel, a->act_f32, gw, dim3(256), s, *a, (const float*)devid, pw, pb);
   hipLaunchKernelGGL(evidence_tail_bwd_fold_kernel, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, (const float*)pw,
                      (const float*)pb, P, nw, nb, a->dw, a->db);
   MMDEER_HIP(hipGetLastError());

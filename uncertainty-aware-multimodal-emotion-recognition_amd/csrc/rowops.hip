@@ -1,14 +1,12 @@
 // Row-wise HBM-bound kernels for gfx950: every global access is an 8- or 16-byte vector per lane,
 // one wave (64 lanes) owns one row, reductions are wave shuffles (no LDS on the per-row path).
 #include "rowops.h"
+#include "elem.h"
 #include "ln_rows.h"
 
 namespace mmdeer {
 
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // kernel arguments live in the constant address space; indexing them through this pointer (instead of the
 // by-value parameter) keeps descriptor tables out of scratch when the index is a runtime value.
@@ -18,17 +16,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T& karg() {
 }
 
 template <bool F32>
-__device__ __forceinline__ f32x4 load4(const void* base, long long idx) {
-  if constexpr (F32) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-  } else {
-    u32x2 r = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    return f32x4{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xFFFF0000u),
-                 __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xFFFF0000u)};
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void store4(void* base, long long idx, f32x4 v) {
+__device__ __forceinline__ void store4_wt(void* base, long long idx, f32x4 v) {
   // a wave stores whole rows contiguously: full cache lines, written through (common.h: store_wt*)
   if constexpr (F32) {
     store_wt16(reinterpret_cast<float*>(base) + idx, v);
@@ -63,8 +51,8 @@ __global__ __launch_bounds__(256) void pack_params_kernel(const PackTable t, voi
     while (sg + 1 < nseg && T.chunk_start[sg + 1] <= c) ++sg;
     const int e = (c - T.chunk_start[sg]) * 4;
     const f32x4 v = *reinterpret_cast<const f32x4*>((const float*)T.src[sg] + e);
-    if (T.is_vec[sg]) store4<true>(vdst, T.dst_off[sg] + e, v);
-    else store4<DST_F32>(wdst, T.dst_off[sg] + e, v);
+    if (T.is_vec[sg]) store4_wt<true>(vdst, T.dst_off[sg] + e, v);
+    else store4_wt<DST_F32>(wdst, T.dst_off[sg] + e, v);
   }
 }
 
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* y, void* out, f
   for (int i = 0; i < NV; ++i) {
     const int c = lane * 4 + i * 256;
     if (EXACT || c < N) {
-      x[i] = load4<F32>(y, base + c);
+      x[i] = ld4<F32>(y, base + c);
       g[i] = *reinterpret_cast<const f32x4*>(gamma + c);
       b[i] = *reinterpret_cast<const f32x4*>(beta + c);
     } else {
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* y, void* out, f
     const int c = lane * 4 + i * 256;
     if (EXACT || c < N) {
       f32x4 o = (x[i] - mu) * rs * g[i] + b[i];
-      store4<F32>(out, base + c, o);
+      store4_wt<F32>(out, base + c, o);
       if (out32) *reinterpret_cast<f32x4*>(out32 + base + c) = o;
     }
   }
@@ -256,8 +244,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* dout, const voi
       for (int i = 0; i < NV; ++i) {
         const int c = lane * 4 + i * 256;
         if (EXACT || c < N) {
-          yv[r][i] = load4<F32>(y, base + c);
-          d[r][i] = load4<F32>(dout, base + c);
+          yv[r][i] = ld4<F32>(y, base + c);
+          d[r][i] = ld4<F32>(dout, base + c);
         } else {
           yv[r][i] = d[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -292,7 +280,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* dout, const voi
             o.z = yv[r][i].z > 0.f ? dy.z * mask_scale : 0.f;
             o.w = yv[r][i].w > 0.f ? dy.w * mask_scale : 0.f;
           }
-          store4<F32>(dz, base + c, o);
+          store4_wt<F32>(dz, base + c, o);
         }
       }
     }
@@ -382,14 +370,14 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(DropCtx d, int site, 
 template <bool SF32, bool DF32>
 __global__ __launch_bounds__(256) void convert_kernel(const void* src, void* dst, long long n4) {
   for (long long c = blockIdx.x * 256ll + threadIdx.x; c < n4; c += gridDim.x * 256ll)
-    store4<DF32>(dst, c * 4, load4<SF32>(src, c * 4));
+    store4_wt<DF32>(dst, c * 4, ld4<SF32>(src, c * 4));
 }
 
 // dst (activation dtype) += src (fp32)
 template <bool DF32>
 __global__ __launch_bounds__(256) void add_f32_kernel(void* dst, const float* src, long long n4) {
   for (long long c = blockIdx.x * 256ll + threadIdx.x; c < n4; c += gridDim.x * 256ll)
-    store4<DF32>(dst, c * 4, load4<DF32>(dst, c * 4) + *reinterpret_cast<const f32x4*>(src + c * 4));
+    store4_wt<DF32>(dst, c * 4, ld4<DF32>(dst, c * 4) + *reinterpret_cast<const f32x4*>(src + c * 4));
 }
 
 inline int grid_for(long long work, int per_block = 256, int cap = 2048) {
@@ -411,9 +399,7 @@ int launch_pack_params(PackTable& t, void* wdst, int w_f32, float* vdst, hipStre
   t.chunk_start[t.nseg] = chunks;
   t.total_chunks = chunks;
   const int grid = (chunks + 1023) / 1024;
-  if (w_f32) hipLaunchKernelGGL(pack_params_kernel<true>, dim3(grid), dim3(256), 0, s, t, wdst, vdst);
-  else hipLaunchKernelGGL(pack_params_kernel<false>, dim3(grid), dim3(256), 0, s, t, wdst, vdst);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(pack_params_kernel, w_f32, dim3(grid), dim3(256), s, t, wdst, vdst);
   return 0;
 }
 
@@ -425,9 +411,7 @@ int launch_pack_transposed(PackTTable& t, void* wtdst, int w_f32, hipStream_t s)
     tiles += ((t.rows[i] + 31) / 32) * ((t.cols[i] + 31) / 32);
   }
   for (int i = t.nmat; i <= PACKT_MAX; ++i) t.tstart[i] = tiles;
-  if (w_f32) hipLaunchKernelGGL(pack_transposed_kernel<true>, dim3(tiles), dim3(256), 0, s, t, wtdst);
-  else hipLaunchKernelGGL(pack_transposed_kernel<false>, dim3(tiles), dim3(256), 0, s, t, wtdst);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(pack_transposed_kernel, w_f32, dim3(tiles), dim3(256), s, t, wtdst);
   return 0;
 }
 
@@ -525,9 +509,7 @@ int launch_add_f32(void* dst, int dst_f32, const float* src, long long n, hipStr
   MMDEER_CHECK(n % 4 == 0, "add: n=%lld must be a multiple of 4", n);
   if (n == 0) return 0;
   const int grid = grid_for(n / 4);
-  if (dst_f32) hipLaunchKernelGGL(add_f32_kernel<true>, dim3(grid), dim3(256), 0, s, dst, src, n / 4);
-  else hipLaunchKernelGGL(add_f32_kernel<false>, dim3(grid), dim3(256), 0, s, dst, src, n / 4);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(add_f32_kernel, dst_f32, dim3(grid), dim3(256), s, dst, src, n / 4);
   return 0;
 }
 

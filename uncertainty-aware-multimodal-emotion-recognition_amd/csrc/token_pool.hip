@@ -17,7 +17,7 @@
 //
 // Statistics (mmdeer_token_stats): one workgroup per sample, ids in LDS, O(L^2) duplicate count, integer LDS atomics only.
 #include "../../include/mmdeer.h"
-#include "common.h"
+#include "elem.h"
 
 namespace mmdeer {
 namespace {
@@ -28,33 +28,6 @@ constexpr int TOK_ZL = TOK_A / 8;    // lanes that own a piece of a score row
 constexpr int TOK_STATS_MAX_L = 2048;
 constexpr long long TOK_MAX_ROWS = 1ll << 20;   // mmdeer_sort_pairs' limit
 constexpr float TOK_EPS = 1e-10f;
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// 8 consecutive elements from element index idx (a multiple of 8 from a 16-byte aligned base)
-template <bool F32>
-__device__ __forceinline__ void ld8(const void* base, long long idx, f32x4& lo, f32x4& hi) {
-  if constexpr (F32) {
-    const float* p = reinterpret_cast<const float*>(base) + idx;
-    lo = *reinterpret_cast<const f32x4*>(p);
-    hi = *reinterpret_cast<const f32x4*>(p + 4);
-  } else {
-    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    lo = f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xFFFF0000u)};
-    hi = f32x4{__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xFFFF0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xFFFF0000u)};
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void st8(void* base, long long idx, const f32x4& lo, const f32x4& hi) {
-  if constexpr (F32) {
-    float* p = reinterpret_cast<float*>(base) + idx;
-    *reinterpret_cast<f32x4*>(p) = lo;
-    *reinterpret_cast<f32x4*>(p + 4) = hi;
-  } else {
-    *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(base) + idx) =
-        u32x4_t{pack_bf2(lo.x, lo.y), pack_bf2(lo.z, lo.w), pack_bf2(hi.x, hi.y), pack_bf2(hi.z, hi.w)};
-  }
-}
 
 // one 768-wide row in a wave: v[0], v[1] = piece `lane`, v[2], v[3] = piece 64 + lane (lanes 0 .. 31, zero elsewhere)
 template <bool F32>
@@ -381,10 +354,6 @@ __global__ __launch_bounds__(256) void token_stats_kernel(mmdeer_token_stats_arg
 }
 
 // ------------------------------------------------------------------------------------------------ host checks
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-
 unsigned row_grid(long long rows) {
   long long g = (rows + 3) / 4;
   return (unsigned)(g > 2048 ? 2048 : g);
@@ -478,9 +447,7 @@ int mmdeer_token_embed_fwd(const mmdeer_token_embed_args* a) {
   if (check_embed(a, false) != 0) return -1;
   if (a->B == 0 || a->L == 0) return 0;
   const long long rows = (long long)a->B * a->L;
-  if (a->act_f32) hipLaunchKernelGGL(token_embed_fwd_kernel<true>, dim3(row_grid(rows)), dim3(256), 0, (hipStream_t)a->stream, *a, rows);
-  else hipLaunchKernelGGL(token_embed_fwd_kernel<false>, dim3(row_grid(rows)), dim3(256), 0, (hipStream_t)a->stream, *a, rows);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(token_embed_fwd_kernel, a->act_f32, dim3(row_grid(rows)), dim3(256), (hipStream_t)a->stream, *a, rows);
   return 0;
 }
 
@@ -490,14 +457,10 @@ int mmdeer_token_embed_bwd(const mmdeer_token_embed_args* a) {
   const long long rows = (long long)a->B * a->L;
   hipStream_t st = (hipStream_t)a->stream;
   if (a->d_src) {
-    if (a->act_f32) hipLaunchKernelGGL(token_embed_dsrc_kernel<true>, dim3(row_grid(rows)), dim3(256), 0, st, *a, rows);
-    else hipLaunchKernelGGL(token_embed_dsrc_kernel<false>, dim3(row_grid(rows)), dim3(256), 0, st, *a, rows);
-    MMDEER_HIP(hipGetLastError());
+    MMDEER_LAUNCH_ACT(token_embed_dsrc_kernel, a->act_f32, dim3(row_grid(rows)), dim3(256), st, *a, rows);
     return 0;
   }
-  if (a->act_f32) hipLaunchKernelGGL(token_embed_dpos_kernel<true>, dim3(a->P), dim3(256), 0, st, *a);
-  else hipLaunchKernelGGL(token_embed_dpos_kernel<false>, dim3(a->P), dim3(256), 0, st, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(token_embed_dpos_kernel, a->act_f32, dim3(a->P), dim3(256), st, *a);
   const long long r16 = (rows + 3) / 4 * 4;
   float* keys = (float*)a->scratch;
   int* order = (int*)(keys + r16);
@@ -507,18 +470,14 @@ int mmdeer_token_embed_bwd(const mmdeer_token_embed_args* a) {
   hipLaunchKernelGGL(token_embed_keys_kernel, dim3((unsigned)(kg > 2048 ? 2048 : kg)), dim3(256), 0, st, a->ids32, a->mask, rows, a->V, keys);
   MMDEER_HIP(hipGetLastError());
   TRY(mmdeer_sort_pairs(keys, 1, rows, order, sorted, mmdeer_sort_pairs_scratch(rows), a->stream));
-  if (a->act_f32) hipLaunchKernelGGL(token_embed_demb_kernel<true>, dim3(row_grid(rows)), dim3(256), 0, st, *a, (const unsigned long long*)sorted, rows);
-  else hipLaunchKernelGGL(token_embed_demb_kernel<false>, dim3(row_grid(rows)), dim3(256), 0, st, *a, (const unsigned long long*)sorted, rows);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(token_embed_demb_kernel, a->act_f32, dim3(row_grid(rows)), dim3(256), st, *a, (const unsigned long long*)sorted, rows);
   return 0;
 }
 
 int mmdeer_token_pool_fwd(const mmdeer_token_pool_args* a) {
   if (check_tpool(a, false) != 0) return -1;
   if (a->B == 0 || a->L == 0) return 0;
-  if (a->act_f32) hipLaunchKernelGGL(token_pool_fwd_kernel<true>, dim3(a->B), dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(token_pool_fwd_kernel<false>, dim3(a->B), dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(token_pool_fwd_kernel, a->act_f32, dim3(a->B), dim3(256), (hipStream_t)a->stream, *a);
   return 0;
 }
 
@@ -526,9 +485,7 @@ int mmdeer_token_pool_bwd(const mmdeer_token_pool_args* a) {
   if (check_tpool(a, true) != 0) return -1;
   if (a->B == 0 || a->L == 0) return 0;
   const int nwg = a->B < TOK_POOL_BWD_WG ? a->B : TOK_POOL_BWD_WG;
-  if (a->act_f32) hipLaunchKernelGGL(token_pool_bwd_kernel<true>, dim3(nwg), dim3(256), 0, (hipStream_t)a->stream, *a);
-  else hipLaunchKernelGGL(token_pool_bwd_kernel<false>, dim3(nwg), dim3(256), 0, (hipStream_t)a->stream, *a);
-  MMDEER_HIP(hipGetLastError());
+  MMDEER_LAUNCH_ACT(token_pool_bwd_kernel, a->act_f32, dim3(nwg), dim3(256), (hipStream_t)a->stream, *a);
   hipLaunchKernelGGL(token_pool_fold_kernel, dim3(1), dim3(TOK_A), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
   MMDEER_HIP(hipGetLastError());
   return 0;
