@@ -122,13 +122,15 @@ ROUTES = {
     # LDS-DMA NT kernel (gemm_nt_glds_kernel<BM, BN, NST, NW>): bf16 V16 x V16, K % 64 == 0, no split-K, no bias_grad.
     # tile 0: 64x64.  tile 1: 8-wave 128x64 up to 320 tiles (option nt8), 4-wave above; 128x128 (glds128, option nt128) when
     # N % 128 == 0, more than 320 tiles of 128x64 and 160..320 tiles of 128x128
-    "glds_64x64": dict(tr=NT, f32=0, a32=0, w32=0, tile=0, shapes=[(1, 4, 64), (63, 68, 128), (65, 196, 192), (131, 132, 64)]),
+    "glds_64x64": dict(tr=NT, f32=0, a32=0, w32=0, tile=0, shapes=[(1, 4, 64), (63, 68, 128), (65, 196, 192), (131, 132, 64),
+                                                                               (65, 68, 320)]),   # 5 K-tiles: the ring's steady state
     "glds_128x64_8w": dict(tr=NT, f32=0, a32=0, w32=0, tile=1, shapes=[(127, 68, 64), (129, 4, 128), (1031, 196, 64)]),
     "glds_128x64_4w": dict(tr=NT, f32=0, a32=0, w32=0, tile=1, shapes=[(4093, 708, 64), (2689, 1028, 128)]),
     "glds_128x128": dict(tr=NT, f32=0, a32=0, w32=0, tile=1, shapes=[(2561, 1280, 64), (2049, 2304, 128)]),
     # 256-row forward LDS-DMA kernel (gemm_nt256_kernel<BN>): tile 3, bf16 V16 x V16, K % 32 == 0, no Y / bias_grad / split-K,
     # C 16-byte aligned, ldc % 8 == 0.  BN = 192 (option nt192) when N % 192 == 0, t192 <= 256 and t192 > t256
-    "nt256_256": dict(tr=NT, f32=0, a32=0, w32=0, tile=3, shapes=[(1, 4, 32), (257, 260, 96), (255, 1028, 64)]),
+    "nt256_256": dict(tr=NT, f32=0, a32=0, w32=0, tile=3, shapes=[(1, 4, 32), (257, 260, 96), (255, 1028, 64),
+                                                                              (257, 260, 160)]),   # 5 K stages: the ring's steady state
     "nt256_192": dict(tr=NT, f32=0, a32=0, w32=0, tile=3, shapes=[(777, 768, 96), (1, 768, 32)]),
     # weight-gradient LDS-DMA kernel (gemm_tt_dma_kernel<BM, BN, KG>): TT, bf16 A and W in 16-byte chunks (pad256: a half-valid
     # last chunk when ld >= extent rounded up to 8), K % 32 == 0, fp32 C 16-byte aligned, no epilogue but bias_grad / accumulate.
@@ -160,6 +162,8 @@ EPI_FWD = {
     "Y16": dict(Y=1, y32=0, mask_scale=1.5),
     "acc": dict(accumulate=1, bias=1),
     "c16": dict(c32=0, bias=1, relu=1),
+    "c16_drop0": dict(c32=0, bias=1, relu=1, drop_site=4, drop_shift=0, p=0.3),   # dropout on a bf16 C: per column ...
+    "c16_drop5": dict(c32=0, drop_site=1, drop_shift=5, p=0.25),                  # ... and per 32 columns
     "bgrad": dict(bias_grad=1),
 }
 EPI_DW = {
@@ -186,7 +190,8 @@ def _epilogues(name, r):
         for k in ("Y32", "Y16", "bgrad"):              # each of these moves the call off that kernel (see fb_nt_mask)
             e.pop(k)
     if r.get("c_shift"):
-        e.pop("c16")                                   # a bf16 C two elements off is not 8-byte aligned (a refusal)
+        for k in ("c16", "c16_drop0", "c16_drop5"):    # a bf16 C two elements off is not 8-byte aligned (a refusal)
+            e.pop(k)
     return e
 
 

@@ -60,15 +60,6 @@
 namespace mmdeer {
 namespace {
 
-template <int N>
-__device__ __forceinline__ void ch_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void dma16(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
 // ---- the weight ring: D stages of 2 KiB per wave (16 output columns x 64 k, in the lane order of the MFMA A operand) in the wave's
 // TOP registers v[256 - 8 D : 255], loaded straight from the fragment-major weight image (chain.h) by global_load_dwordx4 and copied
 // to compiler-visible registers just before the MFMAs.  The kernel is compiled with amdgpu_num_vgpr(256 - 8 D): the register
@@ -529,7 +520,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
       const int image = q / rg, g8 = q - image * rg;
       const int r = g8 * 8 + r8;
       const long long gr = valid_of(r) ? grow_of(r) : (long long)(r >> LOG_MS) * gstride;
-      dma16(a.X + gr * a.ldx + image * 64 + kchunk, lds + image * img + g8 * 1024);
+      lds_dma16(a.X + gr * a.ldx + image * 64 + kchunk, lds + image * img + g8 * 1024);
     }
   }
   // ---- second input panel (input chain): the video rows by DMA, the 84-wide audio rows (168-byte rows: no 16-byte alignment) by
@@ -540,7 +531,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
       const int image = wave >> 1, g8 = wave & 1;       // 4 images x 2 groups of 8 rows: one DMA piece per wave
       const int r = g8 * 8 + r8;
       const long long gr = valid_of(r) ? grow_of(r) : 0;
-      dma16(a.aux_video + gr * a.aux_ldv + image * 64 + kchunk, lds + AUX + image * (MS * 128) + g8 * 1024);
+      lds_dma16(a.aux_video + gr * a.aux_ldv + image * 64 + kchunk, lds + AUX + image * (MS * 128) + g8 * 1024);
     }
   }
   stamp(1);
@@ -608,7 +599,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
     unsigned char* dst = lds + VEC + KA.vec[e].off * 4;
     const int n4 = KA.vec[e].n4;
     for (int j = 0; j * 64 < n4; ++j) {
-      if (src) { if (j * 64 + lane < n4) dma16(src + 4 * (j * 64 + lane), dst + j * 1024); }
+      if (src) { if (j * 64 + lane < n4) lds_dma16(src + 4 * (j * 64 + lane), dst + j * 1024); }
       else if (j * 64 + lane < n4) *reinterpret_cast<f32x4*>(dst + j * 1024 + lane * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
@@ -722,7 +713,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
         if constexpr (kt < NKT) {
           u32x4 f0{0u, 0u, 0u, 0u}, f1{0u, 0u, 0u, 0u};
           if (active) wr_take<S, FLY - 2>(f0, f1);
-          else ch_wait_vm<FLY - 2>();
+          else wait_vm<FLY - 2>();
           issue(std::integral_constant<int, S>{});
           if constexpr (!AFR_REG && kt + 1 < NKT) { if (active) frag_load(std::integral_constant<int, kt + 1>{}); }
           if (active) {
@@ -739,7 +730,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
             }
           }
         } else {      // padding stage: keeps the ring slot / wait count pattern, multiplies nothing
-          ch_wait_vm<FLY - 2>();
+          wait_vm<FLY - 2>();
           issue(std::integral_constant<int, S>{});
         }
       };

@@ -96,6 +96,20 @@ __host__ __device__ __forceinline__ Rand4 drop_rand4(const DropCtx& d, int site,
   return Rand4{mix32(r ^ ((4 * cq) * 0x85EBCA77u) ^ key), mix32(r ^ ((4 * cq + 1) * 0x85EBCA77u) ^ key),
                mix32(r ^ ((4 * cq + 2) * 0x85EBCA77u) ^ key), mix32(r ^ ((4 * cq + 3) * 0x85EBCA77u) ^ key)};
 }
+// dropout applied to the four consecutive columns dcol .. dcol + 3 of a row with key rk = (row * 0x9E3779B1u) ^ drop_key(d, site):
+// one decision per column (shift == 0), or one per 2^shift columns (the four then share it: dcol % 4 == 0)
+__device__ __forceinline__ f32x4 drop4(f32x4 v, unsigned rk, unsigned dcol, int shift, const DropCtx& dc) {
+  if (shift == 0) {
+    v.x = mix32(rk ^ (dcol * 0x85EBCA77u)) < dc.thresh ? v.x * dc.scale : 0.f;
+    v.y = mix32(rk ^ ((dcol + 1) * 0x85EBCA77u)) < dc.thresh ? v.y * dc.scale : 0.f;
+    v.z = mix32(rk ^ ((dcol + 2) * 0x85EBCA77u)) < dc.thresh ? v.z * dc.scale : 0.f;
+    v.w = mix32(rk ^ ((dcol + 3) * 0x85EBCA77u)) < dc.thresh ? v.w * dc.scale : 0.f;
+  } else {
+    const float f = mix32(rk ^ ((dcol >> shift) * 0x85EBCA77u)) < dc.thresh ? dc.scale : 0.f;
+    v.x *= f; v.y *= f; v.z *= f; v.w *= f;
+  }
+  return v;
+}
 // keep decision of one element; `c` is the column index already shifted by the site's granularity
 __host__ __device__ __forceinline__ bool drop_keep(const DropCtx& d, int site, unsigned row, unsigned c) {
   return drop_rand1(drop_key(d, site), row, c) < d.thresh;

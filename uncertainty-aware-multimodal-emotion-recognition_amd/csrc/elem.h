@@ -72,6 +72,12 @@ __device__ __forceinline__ void st8(void* base, long long idx, const float (&x)[
   st8<F32>(base, idx, f32x4{x[0], x[1], x[2], x[3]}, f32x4{x[4], x[5], x[6], x[7]});
 }
 
+// four bf16 in two dwords -> fp32 (exact), and ReLU on four values
+__device__ __forceinline__ f32x4 bf4_to_f32(u32x2 y) {
+  return f32x4{__uint_as_float(y.x << 16), __uint_as_float(y.x & 0xFFFF0000u), __uint_as_float(y.y << 16), __uint_as_float(y.y & 0xFFFF0000u)};
+}
+__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 }  // namespace mmdeer

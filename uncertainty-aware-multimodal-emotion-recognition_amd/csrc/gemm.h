@@ -40,7 +40,7 @@ struct GemmProblem {
   unsigned char pad_[2];
 };
 
-static_assert(sizeof(GemmProblem) == 192, "gemm_glds.hip touches the descriptor's cache lines by byte offset");
+static_assert(sizeof(GemmProblem) == 192, "warm_descriptor (gemm_tile.h) touches the descriptor's cache lines by byte offset");
 
 enum SrcMode { SRC_F32 = 0, SRC_BF16_V16 = 1, SRC_BF16_V8 = 2 };
 

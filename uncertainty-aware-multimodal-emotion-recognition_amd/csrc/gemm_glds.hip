@@ -11,61 +11,23 @@
 // gfx950 ({0-3,12-15,20-27}, ...) the 16 rows x 2 chunks of a group land on 16 distinct 16-byte slots per bank
 // parity: conflict-free (checked on paper in DESIGN.md, and against SQ_LDS_BANK_CONFLICT).
 //
-// Synchronisation (MI355X_MICROARCH: an LDS-DMA is ordered for a ds_read only by the issuing wave's vmcnt plus a
-// barrier the reader has passed): iteration t first waits until its own pieces of tile t have landed
-// (vmcnt = pieces of the younger tiles still allowed in flight), then s_barrier -- which also proves every wave
-// finished reading tile t-1 -- and only then re-issues into the stage tile t-1 occupied.  Raw s_barrier, never
-// __syncthreads(): the latter would drain vmcnt to 0.
+// Synchronisation (pipe.h, rules 1 and 2): iteration t first waits until its own pieces of tile t have landed, then
+// s_barrier -- which also proves every wave finished reading tile t-1 -- and only then re-issues into the stage tile
+// t-1 occupied.
 #include "gemm_kernel.inc"
 #include "options.h"
 
 namespace mmdeer {
 namespace {
 
-#ifdef MMDEER_STAMPS
-#define KSTAMP(slot)                                                                       \
-  do {                                                                                     \
-    if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0) {                                 \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-      g.stamps[slot] = t_;                                                                 \
-    }                                                                                      \
-  } while (0)
-// per-workgroup begin / end on the 100 MHz real-time counter (comparable across XCDs): stamps[256 + 2 bid + {0, 1}]
-#define KWGSTAMP(which)                                                                    \
-  do {                                                                                     \
-    if (g.stamps && threadIdx.x == 0 && blockIdx.x < 1024) {                               \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");       \
-      g.stamps[256 + 2 * blockIdx.x + (which)] = t_;                                       \
-    }                                                                                      \
-  } while (0)
-#else
-#define KSTAMP(slot) do {} while (0)
-#define KWGSTAMP(which) do {} while (0)
-#endif
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// stamps.h: wave 0 of workgroup 0; per-workgroup begin / end at stamps[256 + 2 bid + {0, 1}] (the first 1024 workgroups)
+#define KSTAMP(slot) MMDEER_STAMP(g.stamps, slot, blockIdx.x == 0 && threadIdx.x == 0)
+#define KWGSTAMP(which) MMDEER_WGSTAMP(g.stamps, 256 + 2 * blockIdx.x + (which), threadIdx.x == 0 && blockIdx.x < 1024)
 
 // pieces (1 KiB wave-instructions) each wave issues per K-tile
 template <int BM, int BN, int NW> struct Glds { static constexpr int PA = BM / (8 * NW), PB = BN / (8 * NW), LPT = PA + PB; };
 
-// Problem 0 of the launch as plain scalar kernel arguments: they lead the kernarg segment and are preloaded into
-// SGPRs by the command processor (-mllvm -amdgpu-kernarg-preload-count), so a workgroup of problem 0 -- all of
-// them in most launches -- computes its DMA addresses without waiting for a single kernarg fetch (measured before:
-// ~3000 cycles from wave start to the first DMA, two dependent cold scalar loads).  Workgroups of the other
-// problems of a group (bid >= nt0) read their descriptor from `g` as before.  nt0 = 0 disables the fast path
-// (batched problem 0).
-struct NtKernargs {   // mirror of the kernel's parameter list (for the offset of `g` in the kernarg segment)
-  const bf16_t* A;
-  const bf16_t* B;
-  int M, N, nk, lda, ldb, tiles_n, nt0, nwg;
-  GemmGroup g;
-};
-
+// The leading scalars are problem 0 of the launch, preloaded into SGPRs (gemm_tile.h); nk0 counts 64-element K tiles.
 // NW = waves per workgroup: 4 (2 x 2, two workgroups per CU for the tiles up to 128x64) or 8 (4 x 2 on a 128x64 tile,
 // one workgroup per CU).  The K loop of the 64x64 kernel is bound by the CU's vector-memory path, not by latency:
 // two resident workgroups pull 2 x 16 KiB per K-tile at ~54 of the 64 B/clk the path delivers.  A 128x64 tile shared
@@ -90,12 +52,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && BM * BN <= 128 * 64) ? 2 : 1) 
   KWGSTAMP(0);
 
   int bid = blockIdx.x;
-  if (nwg > 0) {   // XCD-contiguous renumbering (nwg = grid size; 0 switches it off)
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
-  typedef const __attribute__((address_space(4))) unsigned char* karg_ptr;
-  typedef const __attribute__((address_space(4))) GemmProblem* desc_ptr;
+  if (nwg > 0) bid = xcd_contiguous(bid, nwg);   // nwg = grid size; 0 switches the renumbering off
   karg_ptr kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(NtKernargs, g);
   desc_ptr pp = (desc_ptr)(kbase + __builtin_offsetof(GemmGroup, p));
   const bf16_t *Ab = A0, *Bb = B0;
@@ -140,14 +97,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && BM * BN <= 128 * 64) ? 2 : 1) 
     unsigned char* sa = lds + stage * STAGE + wave * 1024;
 #pragma unroll
     for (int j = 0; j < PA; ++j) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pa[j],
-                                       (__attribute__((address_space(3))) void*)(sa + j * NW * 1024), 16, 0, 0);
+      lds_dma16(pa[j], sa + j * NW * 1024);
       pa[j] += 64;
     }
 #pragma unroll
     for (int j = 0; j < PB; ++j) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pb[j],
-                                       (__attribute__((address_space(3))) void*)(sa + A_BYTES + j * NW * 1024), 16, 0, 0);
+      lds_dma16(pb[j], sa + A_BYTES + j * NW * 1024);
       pb[j] += 64;
     }
   };
@@ -168,15 +123,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && BM * BN <= 128 * 64) ? 2 : 1) 
   for (int t = 0; t < NST - 1; ++t)
     if (t < nk) issue(t);
   KSTAMP(2);
-  // Warm the scalar cache with this problem's descriptor lines: the epilogue reads ~20 fields of it, which would
-  // otherwise miss (cold, ~1000 cycles) at the very end of the kernel.  Asm loads so that they are issued HERE; the
-  // results are dead, the registers stay reserved until the matching wait after the K loop.
-  unsigned warm0, warm1, warm2, warm3;
-  asm volatile("s_load_dword %0, %4, 0x0\n\ts_load_dword %1, %4, 0x40\n\ts_load_dword %2, %4, 0x80\n\ts_load_dword %3, %4, 0xbc"
-               : "=&s"(warm0), "=&s"(warm1), "=&s"(warm2), "=&s"(warm3) : "s"(pp) : "memory");
-  // bias chunks of this lane's output columns, consumed after the K loop.  These loads are younger than the prologue
-  // DMAs, so the first counted waits below are merely stricter than needed (never too weak).
+  unsigned warm0, warm1, warm2, warm3;   // descriptor lines for the epilogue
+  warm_descriptor(pp, warm0, warm1, warm2, warm3);
   f32x4 bias4[TN];
+  // bias chunks of this lane's output columns, consumed after the K loop (gemm_tile.h)
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = col0 + wn * WTN + 16 * j + 4 * lg;
@@ -188,9 +138,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && BM * BN <= 128 * 64) ? 2 : 1) 
   for (int kt = 0; kt < nk; ++kt) {
     // pieces of tile kt have landed once at most `younger` whole tiles of this wave are still in flight
     const int younger = (nk - 1 - kt) < (NST - 2) ? (nk - 1 - kt) : (NST - 2);
-    if (younger >= 2) wait_vmcnt<2 * LPT>();
-    else if (younger == 1) wait_vmcnt<LPT>();
-    else wait_vmcnt<0>();
+    wait_tiles<LPT, 2>(younger);
     __builtin_amdgcn_s_barrier();
     if (kt == 0) KSTAMP(3);
     if (kt == 1) KSTAMP(8);
@@ -212,25 +160,17 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && BM * BN <= 128 * 64) ? 2 : 1) 
     }
     stage = stage + 1 == NST ? 0 : stage + 1;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(warm0), "s"(warm1), "s"(warm2), "s"(warm3) : "memory");
+  warm_wait(warm0, warm1, warm2, warm3);
   KSTAMP(4);
   epilogue_direct<TM, TN, WTM, WTN, true>(g, p, acc, bias4, z, row0, col0, wm, wn, li, lg);
-#ifdef MMDEER_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+  MMDEER_STAMP_DRAIN();
   KSTAMP(5);
   KWGSTAMP(1);
 }
 
 template <int BM, int BN, int NST, int NW>
 int launch_glds(const GemmGroup& g, int total, hipStream_t stream) {
-  const GemmProblem& q = g.p[0];
-  const int nt0 = q.batch == 1 ? g.tile_start[1] : 0;   // tile_start[nprob..] = total
-  hipLaunchKernelGGL((gemm_nt_glds_kernel<BM, BN, NST, NW>), dim3(total), dim3(NW * 64), 0, stream,
-                     reinterpret_cast<const bf16_t*>(q.A), reinterpret_cast<const bf16_t*>(q.B), q.M, q.N, q.K >> 6, q.lda,
-                     q.ldb, q.tiles_n, nt0, g.xcd_remap ? total : 0, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
+  return launch_nt_preloaded(gemm_nt_glds_kernel<BM, BN, NST, NW>, g, total, 6, NW * 64, stream);
 }
 
 }  // namespace

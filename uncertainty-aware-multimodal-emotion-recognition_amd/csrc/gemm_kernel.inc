@@ -4,17 +4,16 @@
 // the MFMAs of the current one.  (With the source modes as runtime switches -- inside or around the loop -- the
 // control-flow joins made it wait for every load before the LDS reads: ~3700 cycles per K-tile.)
 #pragma once
-#include "gemm.h"
+#include "gemm_tile.h"
+#include "stamps.h"
 
 namespace mmdeer {
 namespace {
 
 constexpr int LDS_ROW = 144;  // bytes: 128 B of K + 16 B pad
 
-// Native clang vectors (not HIP's uint4/float4 union structs): they stay SSA values, so the register tiles
-// below are never materialised in scratch or promoted to LDS.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// u32x4 / u32x2 / f32x4 are native clang vectors (not HIP's uint4/float4 union structs): they stay SSA values, so the
+// register tiles below are never materialised in scratch or promoted to LDS.
 
 __device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
 
@@ -176,19 +175,9 @@ __device__ __forceinline__ float chunk_sum(const u32x4& a) {
   }
 }
 
-#ifdef MMDEER_STAMPS
-// diagnostic build only: cycle stamps of wave 0 of workgroup 0 (6 stamps per K-tile for the first 16 tiles)
-#define STAMP(slot)                                                                                        \
-  do {                                                                                                     \
-    if (ka.stamps && blockIdx.x == 0 && threadIdx.x == 0 && (kt - ka.kt0) < 16) {                          \
-      unsigned long long t_;                                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                           \
-      ka.stamps[(kt - ka.kt0) * 8 + (slot)] = t_;                                                          \
-    }                                                                                                      \
-  } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#endif
+// stamps.h: wave 0 of workgroup 0, 6 stamps per K-tile for the first 16 tiles
+#define STAMP(slot) \
+  MMDEER_STAMP(ka.stamps, (kt - ka.kt0) * 8 + (slot), blockIdx.x == 0 && threadIdx.x == 0 && (kt - ka.kt0) < 16)
 
 // source element type / vector width of a compile-time loader mode
 template <typename CT, int MODE> struct SrcOf { typedef bf16_t type; static constexpr bool V16 = (MODE == SRC_BF16_V16); };
@@ -352,9 +341,7 @@ __device__ __forceinline__ void k_loop(const KArgs& ka, unsigned char* lds, f32x
     STAMP(1);
     compute(cur);
     STAMP(2);
-#ifdef MMDEER_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+    MMDEER_STAMP_DRAIN();
     STAMP(3);
     lstore(cur ^ 1);
     STAMP(4);
@@ -435,31 +422,17 @@ __device__ __forceinline__ void gemm_epilogue(const GemmGroup& g, const __attrib
     if (gr >= M || !col_ok) continue;
     f32x4 v = *reinterpret_cast<const f32x4*>(S + row * SPAD + cc * 4);
     v += bias4;
-    if (relu) {
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    }
-    if (site >= 0) {
-      const unsigned rk = ((unsigned)gr * 0x9E3779B1u) ^ dkey;
-      if (shift == 0) {
-        v.x = mix32(rk ^ (dcol * 0x85EBCA77u)) < dc.thresh ? v.x * dc.scale : 0.f;
-        v.y = mix32(rk ^ ((dcol + 1) * 0x85EBCA77u)) < dc.thresh ? v.y * dc.scale : 0.f;
-        v.z = mix32(rk ^ ((dcol + 2) * 0x85EBCA77u)) < dc.thresh ? v.z * dc.scale : 0.f;
-        v.w = mix32(rk ^ ((dcol + 3) * 0x85EBCA77u)) < dc.thresh ? v.w * dc.scale : 0.f;
-      } else {
-        const float f = mix32(rk ^ ((dcol >> shift) * 0x85EBCA77u)) < dc.thresh ? dc.scale : 0.f;
-        v.x *= f; v.y *= f; v.z *= f; v.w *= f;
-      }
-    }
+    if (relu) v = relu4(v);
+    if (site >= 0) v = drop4(v, ((unsigned)gr * 0x9E3779B1u) ^ dkey, dcol, shift, dc);
     if (Yp) {
       const long long yo = y_base + (long long)gr * ldy + gc;
-      float y0, y1, y2, y3;
+      float y0, y1, y2, y3;   // four scalars across the join: one vector value there changes the register assignment
       if (y_f32) {
-        f32x4 y = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Yp) + yo);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Yp) + yo);
         y0 = y.x; y1 = y.y; y2 = y.z; y3 = y.w;
       } else {
-        u32x2 y = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(Yp) + yo);
-        y0 = __uint_as_float(y.x << 16); y1 = __uint_as_float(y.x & 0xFFFF0000u);
-        y2 = __uint_as_float(y.y << 16); y3 = __uint_as_float(y.y & 0xFFFF0000u);
+        const f32x4 y = bf4_to_f32(*reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(Yp) + yo));
+        y0 = y.x; y1 = y.y; y2 = y.z; y3 = y.w;
       }
       v.x = y0 > 0.f ? v.x * ms : 0.f; v.y = y1 > 0.f ? v.y * ms : 0.f;
       v.z = y2 > 0.f ? v.z * ms : 0.f; v.w = y3 > 0.f ? v.w * ms : 0.f;
@@ -510,13 +483,8 @@ __device__ __forceinline__ void epilogue_direct(const GemmGroup& g, const __attr
         yv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (m < M && n < N) {
           const long long yo = y_base + (long long)m * ldy + n;
-          if (y_f32) {
-            yv[i][j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Yp) + yo);
-          } else {
-            const u32x2 y = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(Yp) + yo);
-            yv[i][j] = f32x4{__uint_as_float(y.x << 16), __uint_as_float(y.x & 0xFFFF0000u), __uint_as_float(y.y << 16),
-                             __uint_as_float(y.y & 0xFFFF0000u)};
-          }
+          if (y_f32) yv[i][j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Yp) + yo);
+          else yv[i][j] = bf4_to_f32(*reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(Yp) + yo));
         }
       }
   }
@@ -530,19 +498,9 @@ __device__ __forceinline__ void epilogue_direct(const GemmGroup& g, const __attr
       const int n = nb + 16 * j;
       if (n >= N) continue;   // N % 4 == 0: a 4-column group is all in or all out
       f32x4 v = acc[i][j] + bias4[j];
-      if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-      if (site >= 0) {
-        const unsigned dcol = (unsigned)(n + z * N);   // batched problems: the column index continues across the batch
-        if (shift == 0) {
-          v.x = mix32(rk ^ (dcol * 0x85EBCA77u)) < dc.thresh ? v.x * dc.scale : 0.f;
-          v.y = mix32(rk ^ ((dcol + 1) * 0x85EBCA77u)) < dc.thresh ? v.y * dc.scale : 0.f;
-          v.z = mix32(rk ^ ((dcol + 2) * 0x85EBCA77u)) < dc.thresh ? v.z * dc.scale : 0.f;
-          v.w = mix32(rk ^ ((dcol + 3) * 0x85EBCA77u)) < dc.thresh ? v.w * dc.scale : 0.f;
-        } else {
-          const float f = mix32(rk ^ ((dcol >> shift) * 0x85EBCA77u)) < dc.thresh ? dc.scale : 0.f;
-          v.x *= f; v.y *= f; v.z *= f; v.w *= f;
-        }
-      }
+      if (relu) v = relu4(v);
+      // batched problems: the column index continues across the batch
+      if (site >= 0) v = drop4(v, rk, (unsigned)(n + z * N), shift, dc);
       if constexpr (HAS_Y) if (Yp) {
         const f32x4 y = yv[i][j];
         v.x = y.x > 0.f ? v.x * ms : 0.f; v.y = y.y > 0.f ? v.y * ms : 0.f;
@@ -573,33 +531,11 @@ __global__ __launch_bounds__(256, (BM * BN <= 64 * 64) ? 3 : 2) void gemm_group_
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 15, lg = lane >> 4;
 
-  // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD group).  Renumber so each
-  // group owns a contiguous range of tiles: neighbouring tiles share an A row-panel, so the panel is fetched
-  // into ONE XCD's L2 instead of all eight (speed only -- any placement is correct).
   int bid = blockIdx.x;
-  if (g.xcd_remap) {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-    if (i < g.nprob && bid >= g.tile_start[i]) pi = i;
-  // Read the selected descriptor straight from the kernarg segment (constant address space, scalar loads):
-  // indexing the by-value struct with a runtime index would make the compiler spill a private copy of it.
-  typedef const __attribute__((address_space(4))) unsigned char* karg_ptr;
-  karg_ptr kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-  const __attribute__((address_space(4))) GemmProblem& p =
-      *(const __attribute__((address_space(4))) GemmProblem*)(
-          kbase + __builtin_offsetof(GemmGroup, p) + (size_t)pi * sizeof(GemmProblem));
-  const int local = bid - g.tile_start[pi];
-  const int per_slice = p.tiles_m * p.tiles_n;
-  const int per_batch = per_slice * p.splitk;
-  const int z = local / per_batch;
-  const int rem_b = local - z * per_batch;
-  const int slice = rem_b / per_slice;
-  const int rem = rem_b - slice * per_slice;
-  const int tmb = rem / p.tiles_n, tnb = rem - tmb * p.tiles_n;
+  if (g.xcd_remap) bid = xcd_contiguous(bid, gridDim.x);
+  TileAt at;
+  const __attribute__((address_space(4))) GemmProblem& p = *locate_tile(g, bid, 0, at);
+  const int z = at.z, slice = at.slice, tmb = at.tmb, tnb = at.tnb;
   const int row0 = tmb * BM, col0 = tnb * BN;
   const int M = p.M, N = p.N, K = p.K;
 

@@ -15,11 +15,6 @@
 namespace mmdeer {
 namespace {
 
-template <int N>
-__device__ __forceinline__ void lnw_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 struct LnGemmArgs {
   const bf16_t* Y;      // [M][KDIM] raw rows (output of the Linear-ReLU-Dropout in front of the LayerNorm)
   const float* gamma;   // [KDIM]
@@ -50,22 +45,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_ln_kernel(const LnGemmArgs a, co
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN_WAVES, wn = wave % WN_WAVES;
   const int li = lane & 15, lg = lane >> 4;
-  int bid = blockIdx.x;
-  {
-    const int nwg = a.nwg, q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
+  const int bid = xcd_contiguous(blockIdx.x, a.nwg);
   const int tmb = bid / a.tiles_n, tnb = bid - tmb * a.tiles_n;
   const int row0 = tmb * BM, col0 = tnb * BN;
   const int M = a.M;
-  typedef const __attribute__((address_space(4))) GemmProblem* desc_ptr;
-  typedef const __attribute__((address_space(4))) unsigned char* karg_ptr;
   const __attribute__((address_space(4))) GemmProblem& p =
       *(desc_ptr)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LnGemmArgs) + __builtin_offsetof(GemmGroup, p));
   const int N = p.N;
 
-  // ---- bias of this lane's output columns, requested first as loads the compiler does not track (they retire before the
-  //      DMAs behind them; the counted wait below names their registers)
+  // ---- bias of this lane's output columns, requested first as untracked loads (pipe.h: they retire before the DMAs behind
+  //      them; the counted wait below names their registers)
   f32x4 bias4[TN];
   {
     const float* zero_ok = p.bias ? p.bias : a.gamma;     // no bias: any valid address, the value is masked below
@@ -73,7 +62,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_ln_kernel(const LnGemmArgs a, co
     for (int j = 0; j < TN; ++j) {
       const int n = col0 + wn * WTN + 16 * j + 4 * lg;
       const float* q = zero_ok + (p.bias && n < N ? n : 0);
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bias4[j]) : "v"(q) : "memory");
+      gload16_untracked(bias4[j], q);
     }
   }
 
@@ -85,8 +74,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_ln_kernel(const LnGemmArgs a, co
       const int q = j * NW + wave;                    // piece: image q >> 3, row group q & 7
       const int row = row0 + (q & 7) * 8 + r8;
       const bf16_t* src = a.Y + (long long)(row < M ? row : 0) * KDIM + (q >> 3) * 64 + kchunk;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(lds + q * 1024), 16, 0, 0);
+      lds_dma16(src, lds + q * 1024);
     }
   }
   const bf16_t* Bb = reinterpret_cast<const bf16_t*>(p.B);
@@ -101,8 +89,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_ln_kernel(const LnGemmArgs a, co
     unsigned char* sb = lds + PANEL + stage * BSTAGE + wave * 1024;
 #pragma unroll
     for (int j = 0; j < PB; ++j) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pb[j],
-                                       (__attribute__((address_space(3))) void*)(sb + j * NW * 1024), 16, 0, 0);
+      lds_dma16(pb[j], sb + j * NW * 1024);
       pb[j] += 64;
     }
   };
@@ -216,9 +203,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_ln_kernel(const LnGemmArgs a, co
     // the weight pieces of tile kt have landed once at most `younger` whole tiles of this wave are in flight; the panel
     // writer's global stores are younger than the prologue tiles and older than the rest: the counts stay conservative
     const int younger = (NKT - 1 - kt) < (NST - 2) ? (NKT - 1 - kt) : (NST - 2);
-    if (younger >= 2) lnw_wait_vm<2 * PB>();
-    else if (younger == 1) lnw_wait_vm<PB>();
-    else lnw_wait_vm<0>();
+    wait_tiles<PB, 2>(younger);
     __builtin_amdgcn_s_barrier();
     if (kt + NST - 1 < NKT) issue_b(stage == 0 ? NST - 1 : stage - 1);
     const unsigned char* sa = lds + kt * (BM * 128);

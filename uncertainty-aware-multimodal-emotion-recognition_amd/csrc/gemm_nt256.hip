@@ -14,52 +14,11 @@
 namespace mmdeer {
 namespace {
 
-#ifdef MMDEER_STAMPS
-#define NSTAMP(slot)                                                                       \
-  do {                                                                                     \
-    if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0 && (slot) < 128) {                 \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-      g.stamps[slot] = t_;                                                                 \
-    }                                                                                      \
-  } while (0)
-// per-workgroup begin / end on the 100 MHz real-time counter (comparable across XCDs): stamps[256 + 2 bid + {0, 1}]
-#define WGSTAMP(which)                                                                     \
-  do {                                                                                     \
-    if (g.stamps && threadIdx.x == 0) {                                                    \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");       \
-      g.stamps[256 + 2 * blockIdx.x + (which)] = t_;                                       \
-    }                                                                                      \
-  } while (0)
-#else
-#define NSTAMP(slot) do {} while (0)
-#define WGSTAMP(which) do {} while (0)
-#endif
+// stamps.h: wave 0 of workgroup 0; per-workgroup begin / end at stamps[256 + 2 bid + {0, 1}]
+#define NSTAMP(slot) MMDEER_STAMP(g.stamps, slot, blockIdx.x == 0 && threadIdx.x == 0 && (slot) < 128)
+#define WGSTAMP(which) MMDEER_WGSTAMP(g.stamps, 256 + 2 * blockIdx.x + (which), threadIdx.x == 0)
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS reads as inline asm: invisible to the compiler's LDS-DMA hazard tracking (see gemm_tt256.hip)
-__device__ __forceinline__ u32x4 lds_read128(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-__device__ __forceinline__ void wait_lgkm0(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-
-struct Nt256Kernargs {   // mirror of the kernel's parameter list (offset of `g` in the kernarg segment)
-  const bf16_t* A;
-  const bf16_t* B;
-  int M, N, nk, lda, ldb, tiles_n, nt0, nwg;
-  GemmGroup g;
-};
-
-// leading scalars = problem 0, preloaded into SGPRs (see gemm_glds.hip); nk counts 32-element K stages.
+// leading scalars = problem 0, preloaded into SGPRs (gemm_tile.h); nk counts 32-element K stages.
 // BN = 256, or 192 (each wave 64x96): the in_proj (N = 1536) is 32 x 6 = 192 tiles of 256x256 -- a quarter of the 256
 // CUs idle -- but 32 x 8 = 256 tiles of 256x192.  The weight image in LDS keeps 256 rows either way (the DMA pieces
 // are 16 rows x 8 waves; the 64 extra rows are loaded and never read), so only fragment reads and the epilogue differ.
@@ -84,18 +43,13 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
   WGSTAMP(0);
 
   int bid = blockIdx.x;
-  if (nwg > 0) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
-  typedef const __attribute__((address_space(4))) unsigned char* karg_ptr;
-  typedef const __attribute__((address_space(4))) GemmProblem* desc_ptr;
-  karg_ptr kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(Nt256Kernargs, g);
+  if (nwg > 0) bid = xcd_contiguous(bid, nwg);
+  karg_ptr kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(NtKernargs, g);
   desc_ptr pp = (desc_ptr)(kbase + __builtin_offsetof(GemmGroup, p));
   const bf16_t *Ab = A0, *Bb = B0;
   int M = M0, N = N0, nk = nk0, lda = lda0, ldb = ldb0, z = 0;
   int tmb = bid / tiles_n0, tnb = bid - tmb * tiles_n0;
-  if (bid >= nt0) {
+  if (bid >= nt0) {   // not problem 0 (or problem 0 is batched): descriptor from the kernarg segment
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
@@ -131,14 +85,12 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
     unsigned char* sa = lds + stage * STAGE + wave * 1024;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pa[j],
-                                       (__attribute__((address_space(3))) void*)(sa + j * 8192), 16, 0, 0);
+      lds_dma16(pa[j], sa + j * 8192);
       pa[j] += KT;
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pb[j],
-                                       (__attribute__((address_space(3))) void*)(sa + OPER + j * 8192), 16, 0, 0);
+      lds_dma16(pb[j], sa + OPER + j * 8192);
       pb[j] += KT;
     }
   };
@@ -150,21 +102,21 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- fragment addresses: row 16 i + li of the wave's sub-tile, slot lg ^ G[(li >> 2) & 3]
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+  const unsigned lds_base = lds_addr(lds);
   const unsigned frag_off = li * ROWB + ((lg ^ ((4 - (li >> 2)) & 3)) * 16);
   const unsigned offa = lds_base + wm * WTM * ROWB + frag_off;          // + i * 16 * ROWB
   const unsigned offb = lds_base + OPER + wn * WTN * ROWB + frag_off;   // + j * 16 * ROWB
 
-  // ---- ring + ping-pong (see gemm_tt256.hip for the validity argument)
+  // ---- ring + ping-pong (see gemm_tt256.hip for the validity argument); fragment reads are untracked asm reads (pipe.h, rule 3)
   const bool second = wave >= 4;
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t)
     if (t < nk) issue(t);
   NSTAMP(1);
-  unsigned warm0, warm1, warm2, warm3;   // descriptor lines for the epilogue (see gemm_glds.hip)
-  asm volatile("s_load_dword %0, %4, 0x0\n\ts_load_dword %1, %4, 0x40\n\ts_load_dword %2, %4, 0x80\n\ts_load_dword %3, %4, 0xbc"
-               : "=&s"(warm0), "=&s"(warm1), "=&s"(warm2), "=&s"(warm3) : "s"(pp) : "memory");
+  unsigned warm0, warm1, warm2, warm3;   // descriptor lines for the epilogue
+  warm_descriptor(pp, warm0, warm1, warm2, warm3);
   f32x4 bias4[TN];
+  // bias chunks of this lane's output columns, consumed after the K loop (gemm_tile.h)
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int n = col0 + wn * WTN + 16 * j + 4 * lg;
@@ -189,12 +141,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
     wait_lgkm0(fb[0], fb[1], fb[2], fb[3]);
     if constexpr (TN == 8) wait_lgkm0(fb[4], fb[5], fb[6], fb[7]);
     else wait_lgkm0(fb[4], fb[5], fb[4], fb[5]);
-    {
-      const int younger = nk - 2 - kt;   // tiles after kt+1 that have been issued: own pieces of tile kt+1 must have landed
-      if (younger >= 2) wait_vm<2 * LPT>();
-      else if (younger == 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    }
+    wait_tiles<LPT, 2>(nk - 2 - kt);   // tiles after kt+1 that have been issued: own pieces of tile kt+1 must have landed
     __builtin_amdgcn_s_barrier();
     NSTAMP(8 + kt * 4 + 1);
     // ---- M(kt)
@@ -208,7 +155,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
     stage = (stage + 1) & (NST - 1);
   }
   if (!second) __builtin_amdgcn_s_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(warm0), "s"(warm1), "s"(warm2), "s"(warm3) : "memory");
+  warm_wait(warm0, warm1, warm2, warm3);
   NSTAMP(2);
   if (p.c_f32 || p.accumulate) {
     epilogue_direct<TM, TN, WTM, WTN, false>(g, p, acc, bias4, z, row0, col0, wm, wn, li, lg);
@@ -229,19 +176,8 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
       for (int j = 0; j < TN; ++j) {
         const int nl = wn * WTN + 16 * j + 4 * lg;
         f32x4 v = acc[i][j] + bias4[j];
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        if (site >= 0) {
-          const unsigned dcol = (unsigned)(col0 + nl + z * N);
-          if (shift == 0) {
-            v.x = mix32(rk ^ (dcol * 0x85EBCA77u)) < dc.thresh ? v.x * dc.scale : 0.f;
-            v.y = mix32(rk ^ ((dcol + 1) * 0x85EBCA77u)) < dc.thresh ? v.y * dc.scale : 0.f;
-            v.z = mix32(rk ^ ((dcol + 2) * 0x85EBCA77u)) < dc.thresh ? v.z * dc.scale : 0.f;
-            v.w = mix32(rk ^ ((dcol + 3) * 0x85EBCA77u)) < dc.thresh ? v.w * dc.scale : 0.f;
-          } else {
-            const float f = mix32(rk ^ ((dcol >> shift) * 0x85EBCA77u)) < dc.thresh ? dc.scale : 0.f;
-            v.x *= f; v.y *= f; v.z *= f; v.w *= f;
-          }
-        }
+        if (relu) v = relu4(v);
+        if (site >= 0) v = drop4(v, rk, (unsigned)(col0 + nl + z * N), shift, dc);
         *reinterpret_cast<u32x2*>(lds + ml * CROW + nl * 2) = u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
       }
     }
@@ -260,9 +196,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
       else store_wt8(dst, u32x2{v.x, v.y});                        // N % 4 == 0: the last chunk may be half valid
     }
   }
-#ifdef MMDEER_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+  MMDEER_STAMP_DRAIN();
   NSTAMP(3);
   WGSTAMP(1);
 }
@@ -272,18 +206,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
 // caller guarantees: bf16 compute, no transposition, both operands bf16 with ld % 8 == 0 and 16-byte aligned, K % 32 == 0,
 // no split-K / bias_grad / Y mask, tiles counted 256 x bn (bn = 256 or 192)
 int gemm_dispatch_nt256(const GemmGroup& g, int total, int bn, hipStream_t s) {
-  const GemmProblem& q = g.p[0];
-  const int nt0 = q.batch == 1 ? g.tile_start[1] : 0;
-  if (bn == 192)
-    hipLaunchKernelGGL(gemm_nt256_kernel<192>, dim3(total), dim3(512), 0, s, reinterpret_cast<const bf16_t*>(q.A),
-                       reinterpret_cast<const bf16_t*>(q.B), q.M, q.N, q.K >> 5, q.lda, q.ldb, q.tiles_n, nt0,
-                       g.xcd_remap ? total : 0, g);
-  else
-    hipLaunchKernelGGL(gemm_nt256_kernel<256>, dim3(total), dim3(512), 0, s, reinterpret_cast<const bf16_t*>(q.A),
-                       reinterpret_cast<const bf16_t*>(q.B), q.M, q.N, q.K >> 5, q.lda, q.ldb, q.tiles_n, nt0,
-                       g.xcd_remap ? total : 0, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
+  return launch_nt_preloaded(bn == 192 ? gemm_nt256_kernel<192> : gemm_nt256_kernel<256>, g, total, 5, 512, s);
 }
 
 }  // namespace mmdeer

@@ -11,11 +11,11 @@
 // STORED by LDS-DMA (global_load_lds, 16 B per lane, 1 KiB = 2 rows per instruction, 4 instructions per wave per
 // stage) into a 5-stage ring (160 KiB: the whole LDS of the CU), three to four stages in flight.  The two waves of a SIMD
 // work in opposite phases (one issues MFMAs, interleaved with the fragment reads of its NEXT tile, while the other issues
-// DMA and waits), see the loop.  Fragments are read with ds_read_b64_tr_b16 (the
-// hardware transposes a 4-row x 16-column block), two reads per fragment.  Swizzle: the 16-byte chunk at slot p of
+// DMA and waits), see the loop.  Fragments are read with ds_read_b64_tr_b16 (pipe.h:
+// lds_tr_read), two reads per fragment.  Swizzle: the 16-byte chunk at slot p of
 // image row r holds logical chunk p ^ f(r), f(r) = (((r >> 3) & 1) << 3) | ((r & 3) << 1), applied to the DMA source
 // address and to the read address alike: the 8 rows a half-wave reads in one LDS cycle land on 8 distinct 32-byte
-// bank groups.  Counted vmcnt + raw s_barrier as in gemm_glds.hip.
+// bank groups.  Counted vmcnt + raw s_barrier (pipe.h).
 //
 // Round 3 measured the launch as memory-bound INCLUDING its own split-K slabs (130 MB of operand reads + 59 MB of slab writes,
 // then the fold reads them back): with 256x256 tiles only ~56 tiles exist and split-K supplies the parallelism.  On 128x128
@@ -29,34 +29,9 @@
 namespace mmdeer {
 namespace {
 
-#ifdef MMDEER_STAMPS
-// diagnostic build: s_memtime stamps of wave 0 of workgroup 0 (placed only where lgkmcnt is already 0)
-#define TSTAMP(slot)                                                                       \
-  do {                                                                                     \
-    if (g.stamps && blockIdx.x == 0 && threadIdx.x == 0 && (slot) < 128) {                 \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-      g.stamps[slot] = t_;                                                                 \
-    }                                                                                      \
-  } while (0)
-#else
-#define TSTAMP(slot) do {} while (0)
-#endif
+// stamps.h: wave 0 of workgroup 0
+#define TSTAMP(slot) MMDEER_STAMP(g.stamps, slot, blockIdx.x == 0 && threadIdx.x == 0 && (slot) < 128)
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Transposed LDS read as inline asm.  Through the builtin the compiler cannot tell the read from the LDS-DMA writes
-// in flight and drains vmcnt to 0 after every DMA issue (no prefetch left); asm reads are invisible to that pass, the
-// waits (vmcnt for the DMA, lgkmcnt for these reads) are placed by hand.
-template <int OFF>
-__device__ __forceinline__ u32x2 lds_tr_read(unsigned addr) {
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
 // BM x BN = 256 x 256 (the kernel described above), 128 x 128 or 256 x 128: the same schedule on smaller tiles.  128 x 128: a wave owns 32 x 64 (2 x 4 accumulators),
 // image rows are 256 B (a 1-KiB DMA piece = 4 rows, two pieces per wave per stage), 80 KiB of ring.  The small tile exists to
 // run weight gradients WITHOUT split-K: ~175 full-K tiles fill the chip, no partial slabs are written and re-read.
@@ -87,27 +62,10 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
   const int li = lane & 15, lg = lane >> 4;
 
   int bid = blockIdx.x;
-  if (g.xcd_remap) {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-    if (i < g.nprob && bid >= g.tile_start[i]) pi = i;
-  typedef const __attribute__((address_space(4))) unsigned char* karg_ptr;
-  karg_ptr kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-  const __attribute__((address_space(4))) GemmProblem& p =
-      *(const __attribute__((address_space(4))) GemmProblem*)(
-          kbase + __builtin_offsetof(GemmGroup, p) + (size_t)pi * sizeof(GemmProblem));
-  const int local = bid - g.tile_start[pi];
-  const int per_slice = p.tiles_m * p.tiles_n;
-  const int per_batch = per_slice * p.splitk;
-  const int z = local / per_batch;
-  const int rem_b = local - z * per_batch;
-  const int slice = rem_b / per_slice;
-  const int rem = rem_b - slice * per_slice;
-  const int tmb = rem / p.tiles_n, tnb = rem - tmb * p.tiles_n;
+  if (g.xcd_remap) bid = xcd_contiguous(bid, gridDim.x);
+  TileAt at;
+  const __attribute__((address_space(4))) GemmProblem& p = *locate_tile(g, bid, 0, at);
+  const int z = at.z, slice = at.slice, tmb = at.tmb, tnb = at.tnb;
   const int row0 = tmb * BM, col0 = tnb * BN;
   const int M = p.M, N = p.N;
   const int nk_all = p.K / KT;   // K % KT == 0 (checked by the launcher)
@@ -134,12 +92,10 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
     unsigned char* sa = lds + stage * STAGE + wave * 1024;
 #pragma unroll
     for (int j = 0; j < PPWA; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pa + 8 * RPPA * j * lda),
-                                       (__attribute__((address_space(3))) void*)(sa + j * 8192), 16, 0, 0);
+      lds_dma16(pa + 8 * RPPA * j * lda, sa + j * 8192);
 #pragma unroll
     for (int j = 0; j < PPWB; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pb + 8 * RPPB * j * ldb),
-                                       (__attribute__((address_space(3))) void*)(sa + OPER + j * 8192), 16, 0, 0);
+      lds_dma16(pb + 8 * RPPB * j * ldb, sa + OPER + j * 8192);
     pa += KT * lda;
     pb += KT * ldb;
   };
@@ -164,7 +120,7 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
   const int h = ((lg & 1) << 2) | q;   // f(row) >> 1
   const int lane_off_a = (32 * kg + 8 * lg + q) * ROWA + (pp >> 1) * 16 + (pp & 1) * 8;
   const int lane_off_b = (32 * kg + 8 * lg + q) * ROWB + (pp >> 1) * 16 + (pp & 1) * 8;
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+  const unsigned lds_base = lds_addr(lds);
   unsigned offa[TM], offb[TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) offa[i] = lds_base + lane_off_a + (((wm * TM + i) ^ h) * 32);
@@ -189,19 +145,7 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t)
     if (t < nk) issue(t);
-  // wait until at most `younger` whole tiles of this wave's DMA pieces are in flight (0 <= younger <= NST - 3)
-  auto wait_tiles = [&](int younger) __attribute__((always_inline)) {
-    static_assert(NST - 3 <= 7, "cases below");
-    if (younger >= NST - 3) wait_vm<(NST - 3) * LPT>();
-    else if (younger == 6) wait_vm<6 * LPT>();
-    else if (younger == 5) wait_vm<5 * LPT>();
-    else if (younger == 4) wait_vm<4 * LPT>();
-    else if (younger == 3) wait_vm<3 * LPT>();
-    else if (younger == 2) wait_vm<2 * LPT>();
-    else if (younger == 1) wait_vm<LPT>();
-    else wait_vm<0>();
-  };
-  wait_tiles((nk < NST - 1 ? nk : NST - 1) - 2);   // tiles 0 and 1 landed (those issued after them may be in flight)
+  wait_tiles<LPT, NST - 3>((nk < NST - 1 ? nk : NST - 1) - 2);   // tiles 0 and 1 landed (those issued after them may be in flight)
   __builtin_amdgcn_s_barrier();
   TSTAMP(1);
   u32x2 al0[TM], ah0[TM], bl0[TN], bh0[TN], al1[TM], ah1[TM], bl1[TN], bh1[TN];
@@ -227,7 +171,7 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
     if (kt + NST - 1 < nk) { issue(wr); wr = wr + 1 == NST ? 0 : wr + 1; }
     retire(al, ah, bl, bh);
     // own pieces of tile kt+2 landed; the tiles issued after it (kt+3, kt+4, where they exist) may be in flight
-    wait_tiles((nk - 1 < kt + NST - 1 ? nk - 1 : kt + NST - 1) - (kt + 2));
+    wait_tiles<LPT, NST - 3>((nk - 1 < kt + NST - 1 ? nk - 1 : kt + NST - 1) - (kt + 2));
     __builtin_amdgcn_s_barrier();
   };
   // M phase: MFMA column block j (4 MFMAs, all row blocks) behind three fragment reads of the next tile -- reads 3 j .. 3 j + 2

@@ -5,19 +5,13 @@
 // consumer kernel sums the slabs in a fixed order, so loss values and gradients are run-to-run deterministic
 // and the ECE bin COUNTS are exact integers (bit-exact vs the reference's boolean masks for equal inputs).
 #include "nig.h"
+#include "stamps.h"
 
 namespace mmdeer {
 namespace {
 #ifdef MMDEER_STAMPS
 __device__ unsigned long long g_nig_stamps[16];   // diagnostic build: s_memtime of workgroup (0, 0) through nig_bwd_kernel
-#define GSTAMP(slot)                                                                        \
-  do {                                                                                     \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {                          \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-      g_nig_stamps[slot] = t_;                                                             \
-    }                                                                                      \
-  } while (0)
+#define GSTAMP(slot) MMDEER_STAMP((unsigned long long*)g_nig_stamps, slot, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
 #endif
 }  // namespace
 }  // namespace mmdeer

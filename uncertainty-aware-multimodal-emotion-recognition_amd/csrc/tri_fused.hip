@@ -41,29 +41,6 @@ constexpr int TF_FLAGS = cmax(TF_RING, TF_SCR + 2 * TF_BM * 8);   // 8 words beh
 constexpr int TF_LDS = TF_FLAGS + 64;
 static_assert(TF_LDS <= 160 * 1024, "LDS budget");
 
-template <int N>
-__device__ __forceinline__ void tf_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// own pieces of the next tile have landed once at most `younger` whole tiles of this wave are still in flight
-template <int LPT>
-__device__ __forceinline__ void tf_wait_tiles(int younger) {
-  if (younger >= 2) tf_wait_vm<2 * LPT>();
-  else if (younger == 1) tf_wait_vm<LPT>();
-  else tf_wait_vm<0>();
-}
-__device__ __forceinline__ u32x4 tf_lds_read128(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-__device__ __forceinline__ void tf_wait_lgkm0(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
-}
-__device__ __forceinline__ void tf_wait_lgkm0(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory");
-}
-
 // the other token's value: lanes li and li ^ 1 (quad_perm [1, 0, 3, 2])
 __device__ __forceinline__ float tok_swap(float v) { return dpp_read<0xB1>(v); }
 // sum over the four 16-lane rows of the wave (lanes l, l ^ 16, l ^ 32, l ^ 48), result in all of them.
@@ -92,52 +69,37 @@ __device__ __forceinline__ void xrow_sum2(float& va, float& vb) {
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));       // a: [A A A A]  b: [B B B B]
   va = __builtin_bit_cast(float, a); vb = __builtin_bit_cast(float, b);
 }
-__device__ __forceinline__ f32x4 bf4_to_f32(u32x2 y) {
-  return f32x4{__uint_as_float(y.x << 16), __uint_as_float(y.x & 0xFFFF0000u), __uint_as_float(y.y << 16), __uint_as_float(y.y & 0xFFFF0000u)};
-}
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float s) {
   s = fmaf(a.x, b.x, s); s = fmaf(a.y, b.y, s); s = fmaf(a.z, b.z, s); s = fmaf(a.w, b.w, s);
   return s;
 }
 __device__ __forceinline__ f32x4 tok_swap4(f32x4 v) { return f32x4{tok_swap(v.x), tok_swap(v.y), tok_swap(v.z), tok_swap(v.w)}; }
 
-template <int OFF>
-__device__ __forceinline__ u32x4 tf_lds_read128o(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
 template <int TM, int TN>
 __device__ __forceinline__ void tf_read_frags(u32x4 (&fa)[TM], u32x4 (&fb)[TN], unsigned ra, unsigned rb) {
-  fa[0] = tf_lds_read128o<0>(ra); fa[1] = tf_lds_read128o<1024>(ra); fa[2] = tf_lds_read128o<2048>(ra); fa[3] = tf_lds_read128o<3072>(ra);
-  fb[0] = tf_lds_read128o<0>(rb); fb[1] = tf_lds_read128o<1024>(rb); fb[2] = tf_lds_read128o<2048>(rb); fb[3] = tf_lds_read128o<3072>(rb);
-  fb[4] = tf_lds_read128o<4096>(rb); fb[5] = tf_lds_read128o<5120>(rb);
+  fa[0] = lds_read128<0>(ra); fa[1] = lds_read128<1024>(ra); fa[2] = lds_read128<2048>(ra); fa[3] = lds_read128<3072>(ra);
+  fb[0] = lds_read128<0>(rb); fb[1] = lds_read128<1024>(rb); fb[2] = lds_read128<2048>(rb); fb[3] = lds_read128<3072>(rb);
+  fb[4] = lds_read128<4096>(rb); fb[5] = lds_read128<5120>(rb);
 }
 // group G of an M phase: one fragment read of the next tile (groups 0-3: A rows 16 G .., groups 4-9: B rows 16 (G - 4) ..)
 // in front of MFMAs 2 G and 2 G + 1 of the current tile (MFMA e: accumulator (i = e & 3, j = e >> 2))
 template <int G>
 __device__ __forceinline__ void tf_mm_group(f32x4 (&acc)[4][6], const u32x4 (&fa)[4], const u32x4 (&fb)[6], u32x4 (&na)[4],
                                             u32x4 (&nb)[6], unsigned ra, unsigned rb) {
-  if constexpr (G < 4) na[G] = tf_lds_read128o<G * 1024>(ra);
-  else if constexpr (G < 10) nb[G - 4] = tf_lds_read128o<(G - 4) * 1024>(rb);
+  if constexpr (G < 4) na[G] = lds_read128<G * 1024>(ra);
+  else if constexpr (G < 10) nb[G - 4] = lds_read128<(G - 4) * 1024>(rb);
   constexpr int e0 = 2 * G, e1 = 2 * G + 1;
   acc[e0 & 3][e0 >> 2] = mma_chunk<bf16_t>(fb[e0 >> 2], fa[e0 & 3], acc[e0 & 3][e0 >> 2]);
   acc[e1 & 3][e1 >> 2] = mma_chunk<bf16_t>(fb[e1 >> 2], fa[e1 & 3], acc[e1 & 3][e1 >> 2]);
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// stamps.h: waves 0 and 4 of workgroup 0 (slots [64 * (wave >> 2) + slot])
+#define TFSTAMP(slot) MMDEER_STAMP(a.stamps, 64 * (tid >> 8) + (slot), blockIdx.x == 0 && (tid & 255) == 0 && (slot) < 64)
 #ifdef MMDEER_STAMPS
 unsigned long long* g_tf_stamps = nullptr;    // diagnostic library only (tools/tf_stamps.py)
-// cycle stamps of waves 0 and 4 of workgroup 0 (slots [64 * (wave >> 2) + slot]); placed only where lgkmcnt is (nearly) 0
-#define TFSTAMP(slot)                                                                                  \
-  do {                                                                                                 \
-    if (a.stamps && blockIdx.x == 0 && (tid & 255) == 0 && (slot) < 64) {                              \
-      unsigned long long t_;                                                                           \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                       \
-      a.stamps[64 * (tid >> 8) + (slot)] = t_;                                                         \
-    }                                                                                                  \
-  } while (0)
-// per-workgroup begin / end: 100 MHz real-time counter at [256 + 2 bid + w], shader clock at [2304 + 2 bid + w]
+// per-workgroup begin / end: 100 MHz real-time counter at [256 + 2 bid + w], shader clock at [2304 + 2 bid + w] -- both sampled
+// by one statement, which MMDEER_WGSTAMP does not offer
 #define TFWG(which)                                                                                    \
   do {                                                                                                 \
     if (a.stamps && tid == 0 && blockIdx.x < 1024) {                                                   \
@@ -148,7 +110,6 @@ unsigned long long* g_tf_stamps = nullptr;    // diagnostic library only (tools/
     }                                                                                                  \
   } while (0)
 #else
-#define TFSTAMP(slot) do {} while (0)
 #define TFWG(which) do {} while (0)
 #endif
 #ifdef MMDEER_STAMPS_LOOP      // stamps inside the K loop lengthen it (their waits drain the LDS queue): a build of their own
@@ -186,11 +147,7 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
 
   // XCD-contiguous renumbering: the 8 heads of a row tile (same X rows) and the row tiles of an XCD (same head
   // weights) share one L2
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7, idx = bid >> 3;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-  }
+  const int bid = xcd_contiguous(blockIdx.x, nwg);
   const int tmb = bid >> 3, h = bid & 7;
   const int row0 = tmb * TF_BM;
 
@@ -208,18 +165,18 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
     pb0 = Wh + (long long)(16 * wave + (lane >> 2)) * TF_KDIM + kchunk;
     pb1 = Wh + (long long)(128 + 16 * (wave & 3) + (lane >> 2)) * TF_KDIM + kchunk;
   }
-  // ---- in_proj bias of this lane's columns (q, k, v x two 16-column blocks): requested FIRST, as loads the compiler does
-  //      not track (it would drain the DMA queue at their first use); they retire, in order, before the first tile and
-  //      the prologue's counted wait below names their registers.  The accumulators START at the bias.
+  // ---- in_proj bias of this lane's columns (q, k, v x two 16-column blocks): requested FIRST, as untracked loads (pipe.h);
+  //      they retire, in order, before the first tile and the prologue's counted wait below names their registers.  The
+  //      accumulators START at the bias.
   const float* bh = a.bias + h * 64 + wn * 32 + 4 * lg;
   f32x4 bias4[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const float* bp = bh + (j >> 1) * TF_E + 16 * (j & 1);
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bias4[j]) : "v"(bp) : "memory");
+    gload16_untracked(bias4[j], bp);
   }
 
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+  const unsigned lds_base = lds_addr(lds);
   const unsigned frag_off = li * ROWB + ((lg ^ ((4 - (li >> 2)) & 3)) * 16);
   const unsigned offa = lds_base + wm * 64 * ROWB + frag_off;                 // + i * 16 * ROWB
   const unsigned offb = lds_base + TF_A_BYTES + wn * 96 * ROWB + frag_off;    // + j * 16 * ROWB
@@ -239,12 +196,10 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
   // pieces of every wave: the counted waits need no per-half immediates.
   auto issue = [&](int slot, bool extra) __attribute__((always_inline)) {
     unsigned char* sa = lds + slot * STAGE + wave * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pa0, (__attribute__((address_space(3))) void*)sa, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pa1, (__attribute__((address_space(3))) void*)(sa + 8192), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pb0, (__attribute__((address_space(3))) void*)(sa + TF_A_BYTES), 16, 0, 0);
-    if (extra)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)pb1,
-                                       (__attribute__((address_space(3))) void*)(lds + slot * STAGE + TF_A_BYTES + 8192 + (wave & 3) * 1024), 16, 0, 0);
+    lds_dma16(pa0, sa);
+    lds_dma16(pa1, sa + 8192);
+    lds_dma16(pb0, sa + TF_A_BYTES);
+    if (extra) lds_dma16(pb1, lds + slot * STAGE + TF_A_BYTES + 8192 + (wave & 3) * 1024);
     pa0 += KT; pa1 += KT; pb0 += KT; pb1 += KT;
   };
   // tiles 0 and 1 of every wave go into the memory queue first (the first MFMA phase needs all of them); the dropout
@@ -288,11 +243,11 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
   auto phase_l = [&](bool do_issue, bool extra, auto wait_tag, u32x4 (&fa)[TM], u32x4 (&fb)[TN]) __attribute__((always_inline)) {
     TFSTAMP_LOOP(st_);
     if (do_issue) { issue(wr, extra); wr = wr + 1 == NST ? 0 : wr + 1; }
-    tf_wait_lgkm0(fa[0], fa[1], fa[2], fa[3]);
-    tf_wait_lgkm0(fb[0], fb[1], fb[2], fb[3]);
-    tf_wait_lgkm0(fb[4], fb[5]);
+    wait_lgkm0(fa[0], fa[1], fa[2], fa[3]);
+    wait_lgkm0(fb[0], fb[1], fb[2], fb[3]);
+    wait_lgkm0(fb[4], fb[5]);
     TFSTAMP_LOOP(st_ + 1);
-    tf_wait_vm<decltype(wait_tag)::value>();
+    wait_vm<decltype(wait_tag)::value>();
     __builtin_amdgcn_s_barrier();
     TFSTAMP_LOOP(st_ + 2);
     st_ += 3;
@@ -326,9 +281,9 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
   phase_l(false, false, W0{}, fa1, fb1);  phase_m(false, fa1, fb1, fa0, fb0);     // kt = nk - 3: everything has landed
   phase_l(false, false, W0{}, fa0, fb0);  phase_m(false, fa0, fb0, fa1, fb1);
   phase_l(false, false, W0{}, fa1, fb1);  phase_m(true, fa1, fb1, fa0, fb0);
-  tf_wait_lgkm0(fa0[0], fa0[1], fa0[2], fa0[3]);            // the dummy reads of the last phase: their registers are dead, but
-  tf_wait_lgkm0(fb0[0], fb0[1], fb0[2], fb0[3]);            // must not be written after the compiler has reused them
-  tf_wait_lgkm0(fb0[4], fb0[5]);
+  wait_lgkm0(fa0[0], fa0[1], fa0[2], fa0[3]);            // the dummy reads of the last phase: their registers are dead, but
+  wait_lgkm0(fb0[0], fb0[1], fb0[2], fb0[3]);            // must not be written after the compiler has reused them
+  wait_lgkm0(fb0[4], fb0[5]);
   TFSTAMP(3);
   if (!second) __builtin_amdgcn_s_barrier();
   TFSTAMP(4);
@@ -408,9 +363,7 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
     }
     TFSTAMP(6);
     if (!store_tile) {
-#ifdef MMDEER_STAMPS
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+      MMDEER_STAMP_DRAIN();
       TFSTAMP(7);
       TFWG(1);
       return;
@@ -489,9 +442,7 @@ __global__ __launch_bounds__(512) void tri_fused_kernel(const bf16_t* X, const b
     const u32x4 v = *reinterpret_cast<const u32x4*>(lds + r * TF_CROW + c * 16);
     store_wt16(a.tile_out + (long long)row * (3 * TF_E) + (c >> 3) * TF_E + h * 64 + (c & 7) * 8, v);
   }
-#ifdef MMDEER_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+  MMDEER_STAMP_DRAIN();
   TFSTAMP(7);
   TFWG(1);
 }
