@@ -163,18 +163,140 @@ constexpr ImageRange kImages[] = {
 constexpr int kNumImages = sizeof(kImages) / sizeof(kImages[0]);
 static_assert(kNumImages <= ADAM_MAX_IMAGED, "the fused optimiser step takes one AdamImaged per range");
 
-// the forward head chain ends in the NIG head (option chain_nigf): the loss statistics in the workspace are wave partials then.
-// Forward, backward and mmdeer_loss_stats of one step must agree on it: it depends on the options and the batch size only.
-bool nig_tail_plan(int B, int f32) {
-  return !f32 && opt(OPT_CHAIN) && opt(OPT_CHAIN_NIGF) && B >= opt(OPT_CHAIN_MIN) && B <= opt(OPT_CHAIN_MAX);
+// ------------------------------------------------------------------ which chains run
+// One answer for mmdeer_forward, mmdeer_backward and mmdeer_loss_stats: the three must agree on nig_tail (the loss statistics in the
+// workspace are wave partials then), and it depends on the options and the batch size only.
+struct Plan {
+  // one workgroup per 16 samples (32 above B = 4096), each streaming all weights of its chain -- a fixed 25-45 us per chain
+  // whatever the batch: worth it while the chip holds all workgroups at once and most CUs have one (measured per step: B = 4096
+  // -5 to -15 us depending on the box, 3072 -4 us, 2048 0, 1024 +1 us, 64 +12 us; 16-sample workgroups in two rounds at 8192:
+  // +9 us, 32-sample workgroups: see DESIGN.md)
+  bool chains;     // forward: F2-F6 and F9-F17 as one launch each (chain.hip); option "chain" = 0 restores the separate launches
+  // The input chain: with bf16 feature blocks and 16-sample chain workgroups (B <= 4096) the three input projections run as the
+  // first two layers of the audio-visual chain -- the workgroup reads its samples' text, video and raw 84-wide audio rows
+  // itself (padding the audio rows in LDS and leaving the padded copy for the weight-gradient launch): no pad launch, no F1 launch.
+  bool in_chain;
+  bool nig_tail;   // the forward head chain ends in the NIG head (option chain_nigf)
+  int nwp;         // ... and leaves this many wave partials of the loss statistics, one per 16 samples (else 0)
+  // backward chains: the head / trimodal run always when enabled (no outside gradient on fused_features); the audio-visual run only in
+  // the single-call mode (in the two-call mode its first product, the token-0 dX, belongs to the first call)
+  bool bchain, dchain;
+  bool nigfold;    // the head's last layer backward + loss gradient as the prologue of bchain (loss mode, option chain_nig)
+};
+Plan make_plan(int B, int f32, int phase, bool g_fused, bool inputs_bf16, bool targets) {
+  Plan p{};
+  p.chains = !f32 && opt(OPT_CHAIN) && B >= opt(OPT_CHAIN_MIN) && B <= opt(OPT_CHAIN_MAX);
+  p.in_chain = p.chains && opt(OPT_CHAIN_IN) && inputs_bf16 && chain_samples_per_workgroup(B) == 16;
+  p.nig_tail = p.chains && opt(OPT_CHAIN_NIGF);
+  p.nwp = p.nig_tail ? (B + 15) / 16 : 0;
+  const bool bwd = p.chains && opt(OPT_CHAIN_BWD);
+  p.bchain = bwd && !g_fused;
+  p.dchain = bwd && phase == 0;
+  p.nigfold = p.bchain && opt(OPT_CHAIN_NIG) && targets;
+  return p;
 }
 
-// Builder for the executor's GEMM problems.  `es` = bytes of one activation element.
+// ------------------------------------------------------------------ the layers of Stack C
+// Every Linear layer, with the LayerNorm behind it where it has one, is described ONCE (make_net); the forward and the backward derive
+// each form a plan runs it in from that description (Exec below): forward GEMM problem, forward chain segment, dX GEMM problem, dX
+// chain segment, dW GEMM problem.  What is irregular about a layer is a field here, not a patch at a use.
+struct Rows { void* p; int ld; };   // rows of a workspace buffer or of a caller's feature block: first element, leading dimension
+struct Layer {
+  int pidW, pidB;
+  int N, K, M;           // Y [M][N] = X [M][K] W^T + b as the kernels run it; M counts the rows of X and dY (B, or 2B: both AV calls / tokens)
+  Rows in, out;          // X, Y (pre-LayerNorm)
+  int in_f32;            // X's element type: the compute dtype, or that of the caller's feature blocks
+  Rows dout, din;        // dY, dX; no din: an input projection
+  int relu, site;        // ReLU; dropout site behind it, -1 = none
+  Rows mask;             // dX is masked by (mask > 0) * mask_scale: the ReLU + dropout output that X is, where no LayerNorm lies between
+  int shift = 0;         // dropout decisions per 2^shift columns (5 = one per head of the AV attention weights)
+  int w_row0 = 0;        // the kernels multiply by rows [w_row0, w_row0 + N) of pidW only, columns of its [K][wt_ld] W^T copy ...
+  int wt_ld;             // ... (AV value projection: the v third of in_proj [q; k; v] -- one key per query, so q / k are dead)
+  int heads = 1;         // > 1: that many equal parameters from pidW / pidB on, on neighbouring N columns of Y / K columns of X: one batched
+                         // problem with strides, one chain segment each (the heads' second layers)
+  bool padded = false;   // bf16 audio projection: X = L.audio_pad, K = AUD_PAD, W = L.wa_pad / its fragment-major image L.wa_frag
+  int row0 = 0;          // Y / dY are rows [row0, row0 + M) of out / dout: row group 1 of the chain's panel (audio under video in L.avin)
+  int aux_col = -1;      // >= 0, input chain: X is these columns on of the chain's SECOND input panel [video | padded audio]
+  bool open = false;     // the next layer's rows complete this one's output panel in the chain (video, then audio)
+  bool cat_out = false;  // Y = torch.cat of the two AV calls: forward rows [z M/2, (z+1) M/2) of X land in columns [z N, (z+1) N) of out --
+                         // batch = 2 / fold_groups = 1; the backward sees dout stacked again, M rows
+  bool cat_in = false;   // ... and the layer that consumes it: dX is written stacked, the weight halves a batch of 2 / fold_groups = 2
+  int regen = -1;        // dX is multiplied by the REGENERATED keep mask of this site (the no-ReLU dropout in front: the AV attention weights)
+  int regen_shift = 0;
+  // LayerNorm over Y (-1: none): normalised rows, optional fp32 copy for the caller, statistics; backward: dout holds its dz, the
+  // gradient of the normalised rows is the consuming layer's din, gamma / beta partial slabs
+  int pidG = -1, pidBt = -1;
+  void* xln = nullptr; float* out32 = nullptr; float* mean = nullptr; float* rstd = nullptr; float* part = nullptr;
+};
+Layer linear(int pidW, int pidB, int N, int K, int M, Rows in, int in_f32, Rows out, Rows dout, Rows din, int relu = 0, int site = -1,
+             Rows mask = {nullptr, 0}) {
+  Layer l{pidW, pidB, N, K, M, in, out, in_f32, dout, din, relu, site, mask};
+  l.wt_ld = N;
+  return l;
+}
+void layer_norm(Layer& l, int pidG, int pidBt, void* xln, float* out32, float* mean, float* rstd, float* part) {
+  l.pidG = pidG; l.pidBt = pidBt; l.xln = xln; l.out32 = out32; l.mean = mean; l.rstd = rstd; l.part = part;
+}
+
+struct Net { Layer vid, aud, txt, avv, aout, avf, avp, tin, tout, tff, op, fp0, fp1, ev0, ev1; };
+// av32 / tri32 / fused32: the forward's optional fp32 copies of the three feature outputs
+Net make_net(const Layout& L, int B, int f32, const void* audio, const void* video, const void* text, int in_f32, float* av32,
+             float* tri32, float* fused32) {
+  const size_t es = f32 ? 4 : 2;
+  auto in = [](const void* p, int ld) { return Rows{const_cast<void*>(p), ld}; };
+  const Rows none{nullptr, 0};
+  Net n;
+  // the input projections (fusion.py:236-237, 322): video / audio -> rows [0, B) / [B, 2B) of the stacked attention input, text -> token 1
+  n.vid = linear(P_VID_W, P_VID_B, INTER, VID, B, in(video, VID), in_f32, {L.avin, INTER}, {L.davin, INTER}, none);
+  n.vid.aux_col = 0; n.vid.open = true;
+  // bf16 mode: 84-wide rows are not 16-byte aligned -- the audio block zero-padded to 128 columns runs on the LDS-DMA kernels
+  n.aud = linear(P_AUD_W, P_AUD_B, INTER, f32 ? AUD : AUD_PAD, B, f32 ? in(audio, AUD) : Rows{L.audio_pad, AUD_PAD}, f32 ? in_f32 : 0,
+                 {L.avin, INTER}, {L.davin, INTER}, none);
+  n.aud.padded = !f32; n.aud.row0 = B; n.aud.aux_col = VID;
+  // the two token slots of xtok / dxtok: token t of a sample at columns [t FUS, (t + 1) FUS) of its 2 FUS-wide row
+  const Rows tok0{L.xtok, 2 * FUS}, tok1{L.xtok + (size_t)FUS * es, 2 * FUS}, dtok0{L.dxtok, 2 * FUS}, dtok1{L.dxtok + (size_t)FUS * es, 2 * FUS};
+  n.txt = linear(P_TXT_W, P_TXT_B, FUS, TXT, B, in(text, TXT), in_f32, tok1, dtok1, none);
+  // the shared AV cross-attention on [video_proj; audio_proj] (fusion.py:244-255; L = S = 1: softmax == 1, only the value and output
+  // projections remain), attention-weight dropout = one decision per (row, head)
+  n.avv = linear(P_AIN_W, P_AIN_B, INTER, INTER, 2 * B, {L.avin, INTER}, f32, {L.avv, INTER}, {L.davv, INTER}, {L.davin, INTER}, 0, SITE_AV_ATTN);
+  n.avv.shift = 5; n.avv.w_row0 = 2 * INTER; n.avv.wt_ld = 3 * INTER;
+  // out_proj of both calls; call z lands in columns [256 z, 256 z + 256) of cat (fusion.py:262)
+  n.aout = linear(P_AOUT_W, P_AOUT_B, INTER, INTER, 2 * B, {L.avv, INTER}, f32, {L.cat, 2 * INTER}, {L.dcats, INTER}, {L.davv, INTER});
+  n.aout.cat_out = true; n.aout.regen = SITE_AV_ATTN; n.aout.regen_shift = 5;
+  // fusion_layers = Linear -> ReLU -> Dropout -> LayerNorm (fusion.py:263); its dX = d cat unfolded into the two calls' rows: [2B][256]
+  // stacked, rows [0, B) = d audio_attended, rows [B, 2B) = d video_attended
+  n.avf = linear(P_AVF_W, P_AVF_B, INTER, 2 * INTER, B, {L.cat, 2 * INTER}, f32, {L.y_a2, INTER}, {L.dz_a2, INTER}, {L.dcats, INTER}, 1, SITE_AV_FUSE);
+  n.avf.cat_in = true;
+  layer_norm(n.avf, P_AVF_G, P_AVF_BT, L.av, av32, L.mean_a2, L.rstd_a2, L.part_ln_a2);
+  // audiovisual_projection -> token 0 (fusion.py:321, 325)
+  n.avp = linear(P_AVP_W, P_AVP_B, FUS, INTER, B, {L.av, INTER}, f32, tok0, dtok0, {L.dav, INTER});
+  // packed q|k|v in_proj of the 2-token self-attention (fusion.py:328): a GEMM of its own in the backward, and in the unfused forward
+  n.tin = linear(P_TIN_W, P_TIN_B, 3 * FUS, FUS, 2 * B, {L.xtok, FUS}, f32, {L.qkv, 3 * FUS}, {L.dqkv, 3 * FUS}, {L.dxtok, FUS});
+  // its out_proj on the pooled context (mean over tokens commutes with the linear map; fusion.py:335)
+  n.tout = linear(P_TOUT_W, P_TOUT_B, FUS, FUS, B, {L.obar, FUS}, f32, {L.pool, FUS}, {L.dpool, FUS}, {L.dobar, FUS});
+  // final_fusion (fusion.py:338) and output_projection (fusion.py:162): Linear -> ReLU -> Dropout -> LayerNorm
+  n.tff = linear(P_TFF_W, P_TFF_B, FUS, FUS, B, {L.pool, FUS}, f32, {L.y_t3, FUS}, {L.dz_t3, FUS}, {L.dpool, FUS}, 1, SITE_TRI_FUSE);
+  layer_norm(n.tff, P_TFF_G, P_TFF_BT, L.tri, tri32, L.mean_t3, L.rstd_t3, L.part_ln_t3);
+  n.op = linear(P_OP_W, P_OP_B, FUS, FUS, B, {L.tri, FUS}, f32, {L.y_o1, FUS}, {L.dz_o1, FUS}, {L.dtri, FUS}, 1, SITE_OUT_PROJ);
+  layer_norm(n.op, P_OP_G, P_OP_BT, L.fused, fused32, L.mean_o1, L.rstd_o1, L.part_ln_o1);
+  // feature_processor (deer.py:246)
+  n.fp0 = linear(P_FP0_W, P_FP0_B, HID, FUS, B, {L.fused, FUS}, f32, {L.h1, HID}, {L.dh1, HID}, {L.dfused, FUS}, 1, SITE_FP0);
+  n.fp1 = linear(P_FP1_W, P_FP1_B, HID, HID, B, {L.h1, HID}, f32, {L.h2, HID}, {L.dh2, HID}, {L.dh1, HID}, 1, SITE_FP1, {L.h1, HID});
+  // the three DEERLayer first layers (deer.py:49): neighbouring parameters read as ONE stacked [384][256] matrix (kImages)
+  n.ev0 = linear(P_EV0_W, P_EV0_B, 3 * EV1, HID, B, {L.h2, HID}, f32, {L.e1, 3 * EV1}, {L.de1, 3 * EV1}, {L.dh2, HID}, 1, SITE_EV0, {L.h2, HID});
+  // their second layers (deer.py:52), [64][128] each on its own third of e1
+  n.ev1 = linear(P_EV1_W, P_EV1_B, EV2, EV1, B, {L.e1, 3 * EV1}, f32, {L.e2, 3 * EV2}, {L.dz2, 3 * EV2}, {L.de1, 3 * EV1}, 1, SITE_EV1, {L.e1, 3 * EV1});
+  n.ev1.heads = 3;
+  return n;
+}
+
+// Builder for the executor's GEMM problems and chain segments.  `es` = bytes of one activation element.
 struct Exec {
   int B, f32;
   int slice_div = 1; // > 1: weight-gradient K-slices this many times shorter (a launch with few problems: see mmdeer_backward phase 2)
   size_t es;
   bool drop_on;      // dropout active
+  bool bump;         // the step advances the device-side dropout counter (bump_offset_dev)
   float mask_scale;  // 1/(1-p) when dropout is active, else 1
   DropCtx dc;
   const Layout* L;
@@ -182,50 +304,119 @@ struct Exec {
 
   const char* W(int pid) const { return L->wpack + (size_t)kParams[pid].off * es; }
   const float* V(int pid) const { return L->vpack + kParams[pid].off; }
-
-  // Y = X W^T + b: activations in, activations out
-  GemmProblem fwd(const void* A, int a_f32, int lda, int pidW, int pidB, void* C, int ldc, int M, int relu, int site) const {
-    GemmProblem p;
-    gemm_problem_defaults(p);
-    p.A = A; p.a_f32 = a_f32; p.lda = lda;
-    p.B = W(pidW); p.b_f32 = f32; p.ldb = kParams[pidW].cols;
-    p.C = C; p.c_f32 = f32; p.ldc = ldc;
-    p.bias = V(pidB);
-    p.M = M; p.N = kParams[pidW].rows; p.K = kParams[pidW].cols;
-    p.relu = relu;
-    p.drop_site = drop_on ? site : -1;
-    return p;
-  }
-  // dX = dY W, optionally masked by (Yprev > 0) * mask_scale.  Runs as an NT GEMM against the packed W^T
-  // ([K_layer][N_layer], reduction-contiguous), i.e. on the LDS-DMA kernel in bf16 mode.
+  // the packed W^T ([K_layer][N_layer], reduction-contiguous) the dX GEMMs multiply by
   const char* WT(int pid) const { return L->wtpack + (size_t)kParams[pid].off * es; }
   // fragment-major images of W / W^T for the layer chains (bf16 mode; kImages above says which exist)
   const bf16_t* WF(int pid, size_t elem_off = 0) const { return reinterpret_cast<const bf16_t*>(L->wfpack) + kParams[pid].off + elem_off; }
   const bf16_t* WTF(int pid, size_t elem_off = 0) const { return reinterpret_cast<const bf16_t*>(L->wtfpack) + kParams[pid].off + elem_off; }
-  GemmProblem dx(const void* dY, int ldy_in, int pidW, void* dX, int ldx, int M, const void* Ymask, int ldmask) const {
+  // rows [row0, ...) of r
+  char* at(const Rows& r, int row0) const { return reinterpret_cast<char*>(r.p) + (size_t)row0 * r.ld * es; }
+  static bf16_t* bf(const void* p) { return reinterpret_cast<bf16_t*>(const_cast<void*>(p)); }
+
+  // Y = X W^T + b: activations in, activations out
+  GemmProblem fwd(const Layer& l) const {
     GemmProblem p;
     gemm_problem_defaults(p);
-    p.A = dY; p.a_f32 = f32; p.lda = ldy_in;
-    p.B = WT(pidW); p.b_f32 = f32; p.ldb = kParams[pidW].rows;
-    p.C = dX; p.c_f32 = f32; p.ldc = ldx;
-    p.M = M; p.N = kParams[pidW].cols; p.K = kParams[pidW].rows;
-    p.Y = Ymask; p.y_f32 = f32; p.ldy = ldmask; p.mask_scale = mask_scale;
+    p.A = l.in.p; p.a_f32 = l.in_f32; p.lda = l.in.ld;
+    p.B = l.padded ? L->wa_pad : W(l.pidW) + (size_t)l.w_row0 * l.K * es; p.b_f32 = f32; p.ldb = l.K;
+    p.C = at(l.out, l.row0); p.c_f32 = f32; p.ldc = l.out.ld;
+    p.bias = V(l.pidB) + l.w_row0;
+    p.M = l.M; p.N = l.N; p.K = l.K;
+    p.relu = l.relu;
+    p.drop_site = drop_on ? l.site : -1; p.drop_shift = l.shift;
+    if (l.heads > 1) { p.batch = l.heads; p.sA = l.K; p.sB = (long long)l.N * l.K; p.sC = l.N; p.sBias = l.N; }
+    if (l.cat_out) { p.M = l.M / 2; p.batch = 2; p.sA = (long long)p.M * l.in.ld; p.sC = l.N; }
     return p;
   }
-  // dW = dY^T X (+ db = column sums of dY), written into the flat gradient buffer.  The reduction runs over the
-  // batch (K = Mred rows): it is split into K-slices of ~ksteps_target() K-tiles whose partials go to the slab.
-  GemmProblem dw(const void* dY, int ldy_in, const void* X, int x_f32, int ldx, int pidW, int pidB, float* grads, int Mred) const {
+  // ... as segment(s) of a forward chain, one per head; the layer's own LayerNorm runs at the layer end
+  void fwd_seg(ChainArgs& c, const Layer& l) const {
+    for (int z = 0; z < l.heads; ++z) {
+      ChainSeg q;
+      chain_seg_defaults(q);
+      q.W = l.padded ? bf(L->wa_frag) : WF(l.pidW, ((size_t)l.w_row0 + (size_t)z * l.N) * l.K);
+      q.bias = V(l.pidB) + l.w_row0 + z * l.N;
+      q.N = l.N; q.K = l.K; q.ldw = l.K;
+      q.relu = l.relu; q.drop_site = drop_on ? l.site : -1; q.drop_shift = l.shift;
+      q.kin_off = z * l.K; q.nout_off = z * l.N; q.dcol_off = z * l.N;
+      if (l.aux_col >= 0) { q.in_aux = 1; q.kin_off = l.aux_col; }
+      q.row_group = l.row0 ? 1 : 0;
+      q.fold_groups = l.cat_out ? 1 : 0;
+      if (z == l.heads - 1 && !l.open) {
+        q.end_layer = 1; q.nout = (l.cat_out ? 2 : l.heads) * l.N; q.stash = bf(l.out.p); q.ld_stash = l.out.ld;
+        if (l.pidG >= 0) { q.gamma = V(l.pidG); q.beta = V(l.pidBt); q.xln = bf(l.xln); q.out32 = l.out32; q.mean = l.mean; q.rstd = l.rstd; }
+      }
+      c.seg[c.nseg++] = q;
+    }
+  }
+  // bf16 mode: a LayerNorm runs inside the GEMM that consumes it (gemm_ln.hip: the workgroup of a 64-row tile owns whole rows of its A
+  // operand, K = the LayerNorm width) -- three launches fewer in the forward; option "ln_fused" = 0 restores the stand-alone kernel
+  int fwd_ln(const Layer& l, const Layer& norm) const {
+    GemmGroup g{};
+    g.nprob = 1;
+    g.p[0] = fwd(l);
+    g.drop = dc;
+    return launch_gemm_ln(g, norm.out.p, V(norm.pidG), V(norm.pidBt), norm.xln, norm.out32, norm.mean, norm.rstd, s);
+  }
+  int ln_fwd(const Layer& l) const {
+    return launch_ln_fwd(l.out.p, l.xln, l.out32, l.mean, l.rstd, V(l.pidG), V(l.pidBt), l.M, l.N, f32, s);
+  }
+  // the LayerNorm of `l` backwards: the gradient of its normalised rows is the dX of the layer `next` that consumes them
+  int ln_bwd(const Layer& l, const Layer& next) const {
+    return launch_ln_bwd(next.din.p, l.out.p, l.mean, l.rstd, V(l.pidG), l.dout.p, l.part, l.M, l.N, f32, mask_scale, s);
+  }
+  // dX = dY W, optionally masked by (Yprev > 0) * mask_scale.  Runs as an NT GEMM against the packed W^T, i.e. on the LDS-DMA
+  // kernel in bf16 mode.
+  GemmProblem dx(const Layer& l) const {
     GemmProblem p;
     gemm_problem_defaults(p);
-    p.A = dY; p.a_f32 = f32; p.lda = ldy_in; p.trans_a = 1;
-    p.B = X; p.b_f32 = x_f32; p.ldb = ldx; p.trans_b = 1;
-    p.C = grads + kParams[pidW].off; p.c_f32 = 1; p.ldc = kParams[pidW].cols;
-    p.bias_grad = grads + kParams[pidB].off;
-    p.M = kParams[pidW].rows; p.N = kParams[pidW].cols; p.K = Mred;
+    p.A = l.dout.p; p.a_f32 = f32; p.lda = l.dout.ld;
+    p.B = WT(l.pidW) + (size_t)l.w_row0 * es; p.b_f32 = f32; p.ldb = l.wt_ld;
+    p.C = l.din.p; p.c_f32 = f32; p.ldc = l.din.ld;
+    p.M = l.M; p.N = l.K; p.K = l.N;
+    p.Y = l.mask.p; p.y_f32 = f32; p.ldy = l.mask.ld; p.mask_scale = mask_scale;
+    if (drop_on && l.regen >= 0) { p.regen_site = l.regen; p.drop_shift = l.regen_shift; }
+    if (l.heads > 1) { p.batch = l.heads; p.sA = l.N; p.sB = (long long)l.N * l.K; p.sC = l.K; p.sY = l.K; }
+    if (l.cat_in) { p.N = l.K / 2; p.batch = 2; p.sB = (long long)p.N * l.N; p.sC = (long long)l.M * l.din.ld; }   // rows [z K/2, (z+1) K/2) of W^T
+    return p;
+  }
+  // ... as segment(s) of a backward chain (the fragment-major W^T images).  `norm`: the LayerNorm whose normalised rows are this
+  // layer's X runs backwards at the layer end, on the finished dX (mask of its Linear-ReLU-Dropout included)
+  void dx_seg(ChainArgs& c, const Layer& l, const Layer* norm = nullptr) const {
+    for (int z = 0; z < l.heads; ++z) {
+      ChainSeg q;
+      chain_seg_defaults(q);
+      q.W = WTF(l.pidW, ((size_t)l.w_row0 + (size_t)z * l.N) * l.K);
+      q.N = l.K; q.K = l.N; q.ldw = l.N;
+      q.kin_off = z * l.N; q.nout_off = z * l.K;
+      if (l.mask.p) { q.mask_y = bf(l.mask.p); q.ld_mask = l.mask.ld; q.mask_col0 = z * l.K; q.mask_scale = mask_scale; }
+      if (drop_on && l.regen >= 0) { q.drop_site = l.regen; q.drop_shift = l.regen_shift; }
+      q.fold_groups = l.cat_in ? 2 : 0;
+      if (z == l.heads - 1) {
+        q.end_layer = 1; q.nout = l.cat_in ? l.K / 2 : l.heads * l.K; q.stash = bf(l.din.p); q.ld_stash = l.din.ld;
+        if (norm) {
+          q.lnb_gamma = V(norm->pidG); q.lnb_y = bf(norm->out.p); q.lnb_mean = norm->mean; q.lnb_rstd = norm->rstd;
+          q.lnb_dz = bf(norm->dout.p); q.lnb_partial = norm->part; q.lnb_mask_scale = mask_scale;
+        }
+      }
+      c.seg[c.nseg++] = q;
+    }
+  }
+  // dW = dY^T X (+ db = column sums of dY), written into the flat gradient buffer.  The reduction runs over the
+  // batch (K = M rows): it is split into K-slices of ~ksteps_target() K-tiles whose partials go to the slab.
+  GemmProblem dw(const Layer& l, float* grads) const {
+    const int cols = kParams[l.pidW].cols;   // (the padded audio projection: 84 of X's 128 columns)
+    GemmProblem p;
+    gemm_problem_defaults(p);
+    p.A = at(l.dout, l.row0); p.a_f32 = f32; p.lda = l.dout.ld; p.trans_a = 1;
+    p.B = l.in.p; p.b_f32 = l.in_f32; p.ldb = l.in.ld; p.trans_b = 1;
+    p.C = grads + kParams[l.pidW].off + (long long)l.w_row0 * cols; p.c_f32 = 1; p.ldc = cols;
+    p.bias_grad = grads + kParams[l.pidB].off + l.w_row0;
+    p.M = l.N; p.N = cols; p.K = l.M;
+    if (l.heads > 1) { p.batch = l.heads; p.sA = l.N; p.sB = l.K; p.sC = (long long)l.N * l.K; p.sBiasGrad = l.N; }
     set_split(p, grads);
     return p;
   }
-  // (re)derive the split-K fields from p.K and the final destinations p.C / p.bias_grad
+  // derive the split-K fields from p.K and the final destinations p.C / p.bias_grad
   void set_split(GemmProblem& p, float* grads) const {
     const int nk = gemm_ktiles(p.K, f32);
     int kst = ksteps_target(f32);
@@ -259,6 +450,20 @@ struct Exec {
     }
     t.nseg = k;
   }
+  // the gamma / beta partial slabs of l's LayerNorm backward -> the flat gradient (the two slices are adjacent there: N is a multiple
+  // of 64).  `chained`: written by a layer chain, one per workgroup of ITS grid (32-sample workgroups above B = 4096)
+  void add_ln_segment(ReduceTable& t, const Layer& l, float* grads, bool chained) const {
+    const int k = t.nseg++;
+    t.src[k] = l.part; t.dst[k] = grads + kParams[l.pidG].off; t.nparts[k] = chained ? chain_workgroups(B) : ln_bwd_nparts(B);
+    t.n[k] = 2 * l.N; t.stride[k] = 2 * l.N;
+  }
+  // a chain over this batch whose workgroups read K0-wide input rows (two row groups: rows [0, B) and [group_stride, group_stride + B))
+  ChainArgs chain(const Rows& x, int K0, int groups, long long group_stride) const {
+    ChainArgs c{};
+    c.X = bf(x.p); c.ldx = x.ld; c.K0 = K0; c.B = B; c.groups = groups; c.group_stride = group_stride;
+    c.drop = dc;
+    return c;
+  }
   int run(GemmGroup& g) const {
     g.drop = dc;
     return launch_gemm_group(g, f32, pick_tile(g), s);
@@ -270,6 +475,21 @@ struct Exec {
     return run(g);
   }
 };
+// `bump_offset_dev`: the device-side dropout step counter (HIP-graph replays) is advanced by the LAST kernel of the STEP (the fold at
+// the end of mmdeer_backward -- of phase 2 in the two-call mode -- which draws no mask): with it every kernel of the forward and of
+// the backward adds the pending 1 to the host-side offset -- the same effective offset everywhere, and no kernel has to exist just to
+// bump the counter (round 3: the pad launch in front of the first mask; the chains took that launch away).
+Exec make_exec(const Layout& L, int B, int f32, hipStream_t s, int training, float dropout_p, uint64_t seed, uint64_t offset,
+               const uint64_t* offset_dev, int bump_offset_dev) {
+  Exec X;
+  X.B = B; X.f32 = f32; X.es = f32 ? 4 : 2; X.L = &L; X.s = s;
+  X.drop_on = training && dropout_p > 0.f;
+  X.bump = bump_offset_dev && offset_dev;
+  X.dc = make_drop(dropout_p, seed, offset + (X.bump ? 1 : 0), offset_dev);
+  X.mask_scale = X.drop_on ? X.dc.scale : 1.f;
+  return X;
+}
+
 
 int check_weights(const void* w, size_t w_bytes, int f32) {
   MMDEER_CHECK(w != nullptr, "weights buffer is NULL");
@@ -432,164 +652,63 @@ int mmdeer_forward(const mmdeer_forward_args* a) {
   MMDEER_CHECK(a->audio && a->video && a->text, "audio / video / text must be non-NULL");
   MMDEER_CHECK(a->nig_out != nullptr, "nig_out is NULL");
 
-  Exec X;
-  X.B = B; X.f32 = f32; X.es = f32 ? 4 : 2; X.L = &L; X.s = s;
-  X.drop_on = a->training && a->dropout_p > 0.f;
-  // The device-side dropout step counter (HIP-graph replays) is advanced by the LAST kernel of the STEP (the fold at the end of
-  // mmdeer_backward, which draws no mask): with bump_offset_dev every kernel of the forward and of the backward adds the pending 1
-  // to the host-side offset -- the same effective offset everywhere, and no kernel has to exist just to bump the counter (round 3:
-  // the pad launch in front of the first mask; the chains took that launch away).
-  const bool bump = a->bump_offset_dev && a->offset_dev;
-  X.dc = make_drop(a->dropout_p, a->seed, a->offset + (bump ? 1 : 0), a->offset_dev);
-  X.mask_scale = X.drop_on ? X.dc.scale : 1.f;
+  const Exec X = make_exec(L, B, f32, s, a->training, a->dropout_p, a->seed, a->offset, a->offset_dev, a->bump_offset_dev);
   const int in_f32 = a->inputs_bf16 ? 0 : 1;
-  const size_t es = X.es;
-  const bool chains = !f32 && opt(OPT_CHAIN) && B >= opt(OPT_CHAIN_MIN) && B <= opt(OPT_CHAIN_MAX);
-  // The input chain: with bf16 feature blocks and 16-sample chain workgroups (B <= 4096) the three input projections run as the
-  // first two layers of the audio-visual chain below -- the workgroup reads its samples' text, video and raw 84-wide audio rows
-  // itself (padding the audio rows in LDS and leaving the padded copy for the weight-gradient launch): no pad launch, no F1 launch.
-  const bool in_chain = chains && opt(OPT_CHAIN_IN) && !in_f32 && chain_samples_per_workgroup(B) == 16;
-  const bool nig_tail = nig_tail_plan(B, f32);
+  const Plan plan = make_plan(B, f32, 0, false, !in_f32, false);
+  const Net n = make_net(L, B, f32, a->audio, a->video, a->text, in_f32, a->audiovisual_features, a->trimodal_features, a->fused_features);
 
   // F0 (bf16 mode): 84-wide rows are not 16-byte aligned -- zero-pad the audio block to 128 columns so that it runs on the
   //     LDS-DMA kernels
-  if (!f32 && !in_chain) {
+  if (!f32 && !plan.in_chain) {
     PadTable pt{};
     pt.src[0] = a->audio; pt.dst[0] = L.audio_pad; pt.src_f32[0] = in_f32; pt.rows[0] = B; pt.cols[0] = AUD; pt.ld_dst[0] = AUD_PAD;
     pt.nseg = 1;
     TRY(launch_pad_cols(pt, s));
     MARK("pad_cols (audio 84 -> 128)");
   }
-  // F1: the three input projections (fusion.py:236-237, 322) in one launch
-  if (!in_chain) {
+  // F1: the three input projections in one launch
+  if (!plan.in_chain) {
     GemmGroup g{};
     g.nprob = 3;
-    g.p[0] = X.fwd(a->video, in_f32, VID, P_VID_W, P_VID_B, L.avin, INTER, B, 0, -1);                       // rows [0,B)
-    g.p[1] = X.fwd(a->audio, in_f32, AUD, P_AUD_W, P_AUD_B, L.avin + (size_t)B * INTER * es, INTER, B, 0, -1); // rows [B,2B)
-    if (!f32) {
-      g.p[1].A = L.audio_pad; g.p[1].a_f32 = 0; g.p[1].lda = AUD_PAD;
-      g.p[1].B = L.wa_pad; g.p[1].ldb = AUD_PAD; g.p[1].K = AUD_PAD;
-    }
-    g.p[2] = X.fwd(a->text, in_f32, TXT, P_TXT_W, P_TXT_B, L.xtok + (size_t)FUS * es, 2 * FUS, B, 0, -1);     // token 1
+    g.p[0] = X.fwd(n.vid);
+    g.p[1] = X.fwd(n.aud);
+    g.p[2] = X.fwd(n.txt);
     TRY(X.run(g));
     MARK("F1 input projections (3 problems)");
   }
-  // bf16 mode: each LayerNorm runs inside the GEMM that consumes it (gemm_ln.hip: the workgroup of a 64-row tile owns whole
-  // rows of its A operand, K = the LayerNorm width) -- three launches fewer in the forward; option "ln_fused" = 0 restores
-  // the stand-alone LayerNorm kernel
-  const bool lnf = !f32 && opt(OPT_LN_FUSED);
-  auto ln_gemm = [&](const GemmProblem& q, const void* Y, int pidG, int pidBt, void* xln, float* out32, float* mean, float* rstd) -> int {
-    GemmGroup g{};
-    g.nprob = 1;
-    g.p[0] = q;
-    g.drop = X.dc;
-    return launch_gemm_ln(g, Y, X.V(pidG), X.V(pidBt), xln, out32, mean, rstd, s);
-  };
-  // one workgroup per 16 samples (32 above B = 4096), each streaming all weights of its chain -- a fixed 25-45 us per chain
-  // whatever the batch: worth it while the chip holds all workgroups at once and most CUs have one (measured per step: B = 4096
-  // -5 to -15 us depending on the box, 3072 -4 us, 2048 0, 1024 +1 us, 64 +12 us; 16-sample workgroups in two rounds at 8192:
-  // +9 us, 32-sample workgroups: see DESIGN.md)
-  // F2-F6 are local to a sample (the AV "attention" has one key per query: softmax == 1, only the value and output projections
-  // remain): in bf16 mode ONE launch walks them with the rows resident in LDS (chain.hip).  A workgroup holds the video and the
-  // audio row of its 16 samples as two row groups; torch.cat of the two attention outputs is a re-view of the panel.
-  if (chains) {
-    ChainArgs c{};
-    c.X = reinterpret_cast<const bf16_t*>(L.avin); c.ldx = INTER; c.K0 = INTER; c.B = B; c.groups = 2; c.group_stride = B;
-    c.drop = X.dc;
-    int k = 0;
-    if (in_chain) {
-      c.X = reinterpret_cast<const bf16_t*>(a->text); c.ldx = TXT; c.K0 = TXT; c.groups = 1;
-      c.aux_video = reinterpret_cast<const bf16_t*>(a->video); c.aux_ldv = VID;
+  const bool lnf = !f32 && opt(OPT_LN_FUSED);   // LayerNorm inside the consuming GEMM (Exec::fwd_ln)
+  // F2-F6 are local to a sample: in bf16 mode ONE launch walks them with the rows resident in LDS (chain.hip).  A workgroup holds the
+  // video and the audio row of its 16 samples as two row groups; torch.cat of the two attention outputs is a re-view of the panel.
+  if (plan.chains) {
+    ChainArgs c = X.chain(n.avv.in, n.avv.K, 2, B);
+    if (plan.in_chain) {    // F1c, F1a, F1b in front: the chain reads the text rows, and video / raw audio as its second input panel
+      c = X.chain(n.txt.in, n.txt.K, 1, B);
+      c.aux_video = Exec::bf(n.vid.in.p); c.aux_ldv = n.vid.in.ld;
       c.aux_audio = reinterpret_cast<const bf16_t*>(a->audio); c.aux_lda = AUD;
       c.aux_audio_pad = reinterpret_cast<bf16_t*>(L.audio_pad);
-      {   // F1c: text_projection -> token 1 of xtok (fusion.py:322, 325)
-        ChainSeg q;
-        chain_seg_defaults(q);
-        q.W = X.WF(P_TXT_W); q.bias = X.V(P_TXT_B); q.N = FUS; q.K = TXT;
-        q.end_layer = 1; q.nout = FUS; q.stash = reinterpret_cast<bf16_t*>(L.xtok) + FUS; q.ld_stash = 2 * FUS;
-        c.seg[k++] = q;
-      }
-      {   // F1a: video_projection -> rows [0, B) of the stacked attention input (fusion.py:237)
-        ChainSeg q;
-        chain_seg_defaults(q);
-        q.W = X.WF(P_VID_W); q.bias = X.V(P_VID_B); q.N = INTER; q.K = VID; q.in_aux = 1; q.kin_off = 0;
-        c.seg[k++] = q;
-      }
-      {   // F1b: audio_projection on the padded rows -> rows [B, 2B) (fusion.py:236)
-        ChainSeg q;
-        chain_seg_defaults(q);
-        q.W = reinterpret_cast<const bf16_t*>(L.wa_frag); q.bias = X.V(P_AUD_B); q.N = INTER; q.K = AUD_PAD; q.in_aux = 1; q.kin_off = VID;
-        q.row_group = 1;
-        q.end_layer = 1; q.nout = INTER; q.stash = reinterpret_cast<bf16_t*>(L.avin); q.ld_stash = INTER;
-        c.seg[k++] = q;
-      }
+      X.fwd_seg(c, n.txt);
+      X.fwd_seg(c, n.vid);
+      X.fwd_seg(c, n.aud);
     }
-    {   // F2: value projection (rows [2E, 3E) of the packed in_proj), attention-weight dropout = one decision per (row, head)
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WF(P_AIN_W, (size_t)2 * INTER * INTER); q.bias = X.V(P_AIN_B) + 2 * INTER;
-      q.N = INTER; q.K = INTER; q.ldw = INTER;
-      q.drop_site = X.drop_on ? SITE_AV_ATTN : -1; q.drop_shift = 5;
-      q.end_layer = 1; q.nout = INTER; q.stash = reinterpret_cast<bf16_t*>(L.avv); q.ld_stash = INTER;
-      c.seg[k++] = q;
-    }
-    {   // F3: out_proj of both calls; group z lands in columns [256 z, 256 z + 256) of cat (fusion.py:262)
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WF(P_AOUT_W); q.bias = X.V(P_AOUT_B); q.N = INTER; q.K = INTER; q.ldw = INTER;
-      q.fold_groups = 1;
-      q.end_layer = 1; q.nout = 2 * INTER; q.stash = reinterpret_cast<bf16_t*>(L.cat); q.ld_stash = 2 * INTER;
-      c.seg[k++] = q;
-    }
-    {   // F4-F5: fusion_layers = Linear -> ReLU -> Dropout -> LayerNorm (fusion.py:263)
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WF(P_AVF_W); q.bias = X.V(P_AVF_B); q.N = INTER; q.K = 2 * INTER; q.ldw = 2 * INTER;
-      q.relu = 1; q.drop_site = X.drop_on ? SITE_AV_FUSE : -1;
-      q.end_layer = 1; q.nout = INTER; q.stash = reinterpret_cast<bf16_t*>(L.y_a2); q.ld_stash = INTER;
-      q.gamma = X.V(P_AVF_G); q.beta = X.V(P_AVF_BT); q.xln = reinterpret_cast<bf16_t*>(L.av); q.out32 = a->audiovisual_features;
-      q.mean = L.mean_a2; q.rstd = L.rstd_a2;
-      c.seg[k++] = q;
-    }
-    {   // F6: audiovisual_projection -> token 0 (fusion.py:321, 325)
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WF(P_AVP_W); q.bias = X.V(P_AVP_B); q.N = FUS; q.K = INTER; q.ldw = INTER;
-      q.end_layer = 1; q.nout = FUS; q.stash = reinterpret_cast<bf16_t*>(L.xtok); q.ld_stash = 2 * FUS;
-      c.seg[k++] = q;
-    }
-    c.nseg = k;
+    X.fwd_seg(c, n.avv);    // F2
+    X.fwd_seg(c, n.aout);   // F3
+    X.fwd_seg(c, n.avf);    // F4-F5
+    X.fwd_seg(c, n.avp);    // F6
     TRY(launch_chain(c, s));
-    MARK(in_chain ? "chain F1-F6 (input projections + audio-visual fusion)" : "chain F2-F6 (audio-visual fusion)");
+    MARK(plan.in_chain ? "chain F1-F6 (input projections + audio-visual fusion)" : "chain F2-F6 (audio-visual fusion)");
   } else {
-    // F2: value projection of the shared AV cross-attention on [video_proj; audio_proj] (fusion.py:244-255;
-    //     L = S = 1 so q/k are dead), attention-weight dropout = one decision per (row, head)
-    {
-      GemmProblem p = X.fwd(L.avin, f32, INTER, P_AIN_W, P_AIN_B, L.avv, INTER, 2 * B, 0, SITE_AV_ATTN);
-      p.B = X.W(P_AIN_W) + (size_t)2 * INTER * INTER * es;   // rows [2E, 3E) of the packed [q;k;v] matrix
-      p.bias = X.V(P_AIN_B) + 2 * INTER;
-      p.N = INTER;
-      p.drop_shift = 5;  // 32 columns = one head
-      TRY(X.run1(p));
-    }
-    // F3: out_proj, batched over the two calls; batch z writes columns [256 z, 256 z + 256) of cat (fusion.py:262)
-    {
-      GemmProblem p = X.fwd(L.avv, f32, INTER, P_AOUT_W, P_AOUT_B, L.cat, 2 * INTER, B, 0, -1);
-      p.batch = 2; p.sA = (long long)B * INTER; p.sC = INTER;
-      TRY(X.run1(p));
-    }
-    // F4-F5: fusion_layers = Linear -> ReLU -> Dropout -> LayerNorm (fusion.py:263)
-    TRY(X.run1(X.fwd(L.cat, f32, 2 * INTER, P_AVF_W, P_AVF_B, L.y_a2, INTER, B, 1, SITE_AV_FUSE)));
-    // F5-F6: LayerNorm + audiovisual_projection -> token 0 (fusion.py:263, 321, 325)
+    TRY(X.run1(X.fwd(n.avv)));    // F2
+    TRY(X.run1(X.fwd(n.aout)));   // F3
+    TRY(X.run1(X.fwd(n.avf)));    // F4
+    // F5-F6: LayerNorm + audiovisual_projection
     if (lnf) {
-      TRY(ln_gemm(X.fwd(L.av, f32, INTER, P_AVP_W, P_AVP_B, L.xtok, 2 * FUS, B, 0, -1), L.y_a2, P_AVF_G, P_AVF_BT, L.av, a->audiovisual_features,
-                  L.mean_a2, L.rstd_a2));
+      TRY(X.fwd_ln(n.avp, n.avf));
     } else {
-      TRY(launch_ln_fwd(L.y_a2, L.av, a->audiovisual_features, L.mean_a2, L.rstd_a2, X.V(P_AVF_G), X.V(P_AVF_BT), B, INTER, f32, s));
-      TRY(X.run1(X.fwd(L.av, f32, INTER, P_AVP_W, P_AVP_B, L.xtok, 2 * FUS, B, 0, -1)));
+      TRY(X.ln_fwd(n.avf));
+      TRY(X.run1(X.fwd(n.avp)));
     }
   }
-  if (!chains) MARK("F2-F6 separate launches");
+  if (!plan.chains) MARK("F2-F6 separate launches");
   // F7: packed q|k|v in_proj of the 2-token self-attention (fusion.py:328)
   //     + F8: 2x2 softmax attention, token-pooled context.  bf16: ONE kernel, q|k|v stay in its accumulators
   if (a->prof_events[0]) MMDEER_HIP(hipEventRecord((hipEvent_t)a->prof_events[0], s));
@@ -601,48 +720,23 @@ int mmdeer_forward(const mmdeer_forward_args* a) {
     TRY(launch_tri_attn_weights(L.probs, a->trimodal_attention, a->av_attention, B, X.drop_on ? 1 : 0, X.dc, s));
     if (a->trimodal_attention || a->av_attention) MARK("attention weights");
   } else {
-    TRY(X.run1(X.fwd(L.xtok, f32, FUS, P_TIN_W, P_TIN_B, L.qkv, 3 * FUS, 2 * B, 0, -1)));
+    TRY(X.run1(X.fwd(n.tin)));
     if (a->prof_events[1]) MMDEER_HIP(hipEventRecord((hipEvent_t)a->prof_events[1], s));
     TRY(launch_tri_attn_fwd(L.qkv, L.obar, L.probs, a->trimodal_attention, a->av_attention, B, f32, X.drop_on ? 1 : 0, X.dc, s));
     MARK("in_proj GEMM + attention (unfused)");
   }
   // F9-F17 are local to a sample (Linear / ReLU / Dropout / LayerNorm): in bf16 mode ONE launch walks the chain with the rows
   // resident in LDS (chain.hip) and writes the same workspace buffers; option "chain" = 0 restores the separate launches
-  if (chains) {
-    ChainArgs c{};
-    c.X = reinterpret_cast<const bf16_t*>(L.obar); c.ldx = FUS; c.K0 = FUS; c.B = B; c.groups = 1; c.group_stride = 0;
-    c.drop = X.dc;
-    auto lin = [&](int pidW, int pidB, int N, int K, int relu, int site, void* stash) {
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WF(pidW); q.bias = X.V(pidB); q.N = N; q.K = K; q.ldw = K;
-      q.relu = relu; q.drop_site = X.drop_on ? site : -1;
-      q.end_layer = 1; q.nout = N; q.stash = reinterpret_cast<bf16_t*>(stash); q.ld_stash = N;
-      return q;
-    };
-    auto with_ln = [&](ChainSeg q, int pidG, int pidBt, void* xln, float* out32, float* mean, float* rstd) {
-      q.gamma = X.V(pidG); q.beta = X.V(pidBt); q.xln = reinterpret_cast<bf16_t*>(xln); q.out32 = out32; q.mean = mean; q.rstd = rstd;
-      return q;
-    };
-    int k = 0;
-    c.seg[k++] = lin(P_TOUT_W, P_TOUT_B, FUS, FUS, 0, -1, L.pool);                                                    // F9
-    c.seg[k++] = with_ln(lin(P_TFF_W, P_TFF_B, FUS, FUS, 1, SITE_TRI_FUSE, L.y_t3), P_TFF_G, P_TFF_BT, L.tri,        // F10-F11
-                         a->trimodal_features, L.mean_t3, L.rstd_t3);
-    c.seg[k++] = with_ln(lin(P_OP_W, P_OP_B, FUS, FUS, 1, SITE_OUT_PROJ, L.y_o1), P_OP_G, P_OP_BT, L.fused,           // F12-F13
-                         a->fused_features, L.mean_o1, L.rstd_o1);
-    c.seg[k++] = lin(P_FP0_W, P_FP0_B, HID, FUS, 1, SITE_FP0, L.h1);                                                   // F14
-    c.seg[k++] = lin(P_FP1_W, P_FP1_B, HID, HID, 1, SITE_FP1, L.h2);                                                   // F15
-    c.seg[k++] = lin(P_EV0_W, P_EV0_B, 3 * EV1, HID, 1, SITE_EV0, L.e1);                                               // F16
-    for (int z = 0; z < 3; ++z) {                                                                                      // F17
-      ChainSeg q = lin(P_EV1_W, P_EV1_B, EV2, EV1, 1, SITE_EV1, nullptr);
-      q.W += (size_t)z * EV2 * EV1; q.bias += z * EV2;
-      q.kin_off = z * EV1; q.nout_off = z * EV2; q.dcol_off = z * EV2;
-      q.end_layer = z == 2; q.nout = 3 * EV2;
-      if (z == 2) { q.stash = reinterpret_cast<bf16_t*>(L.e2); q.ld_stash = 3 * EV2; }
-      c.seg[k++] = q;
-    }
-    c.nseg = k;
-    if (nig_tail) {     // F18 as the chain's tail: last head layer, NIG activations, uncertainties, loss statistics (wave partials)
+  if (plan.chains) {
+    ChainArgs c = X.chain(n.tout.in, n.tout.K, 1, 0);
+    X.fwd_seg(c, n.tout);   // F9
+    X.fwd_seg(c, n.tff);    // F10-F11
+    X.fwd_seg(c, n.op);     // F12-F13
+    X.fwd_seg(c, n.fp0);    // F14
+    X.fwd_seg(c, n.fp1);    // F15
+    X.fwd_seg(c, n.ev0);    // F16
+    X.fwd_seg(c, n.ev1);    // F17
+    if (plan.nig_tail) {     // F18 as the chain's tail: last head layer, NIG activations, uncertainties, loss statistics (wave partials)
       ChainNigF& g = c.nigf;
       g.enabled = 1;
       g.w3 = reinterpret_cast<const bf16_t*>(X.W(P_EV2_W)); g.b3 = X.V(P_EV2_B); g.b3_stride = 64;
@@ -652,44 +746,27 @@ int mmdeer_forward(const mmdeer_forward_args* a) {
     c.stamps = reinterpret_cast<unsigned long long*>(L.slab);   // diagnostic library: cycle samples of workgroup 0 (tools/chain_stamps.py)
 #endif
     TRY(launch_chain(c, s));
-    MARK(nig_tail ? "chain F9-F18 (trimodal fusion tail + head + NIG)" : "chain F9-F17 (trimodal fusion tail + head)");
+    MARK(plan.nig_tail ? "chain F9-F18 (trimodal fusion tail + head + NIG)" : "chain F9-F17 (trimodal fusion tail + head)");
   } else {
-    // F9: out_proj on the pooled context (mean over tokens commutes with the linear map; fusion.py:335)
-    TRY(X.run1(X.fwd(L.obar, f32, FUS, P_TOUT_W, P_TOUT_B, L.pool, FUS, B, 0, -1)));
-    // F10-F11: final_fusion (fusion.py:338)
-    TRY(X.run1(X.fwd(L.pool, f32, FUS, P_TFF_W, P_TFF_B, L.y_t3, FUS, B, 1, SITE_TRI_FUSE)));
-    // F11-F12: LayerNorm of final_fusion + output_projection (fusion.py:338, 162); F13-F14: its LayerNorm + feature_processor.0
+    TRY(X.run1(X.fwd(n.tout)));   // F9
+    TRY(X.run1(X.fwd(n.tff)));    // F10
+    // F11-F12: LayerNorm of final_fusion + output_projection; F13-F14: its LayerNorm + feature_processor.0
     if (lnf) {
-      TRY(ln_gemm(X.fwd(L.tri, f32, FUS, P_OP_W, P_OP_B, L.y_o1, FUS, B, 1, SITE_OUT_PROJ), L.y_t3, P_TFF_G, P_TFF_BT, L.tri, a->trimodal_features,
-                  L.mean_t3, L.rstd_t3));
-      TRY(ln_gemm(X.fwd(L.fused, f32, FUS, P_FP0_W, P_FP0_B, L.h1, HID, B, 1, SITE_FP0), L.y_o1, P_OP_G, P_OP_BT, L.fused, a->fused_features,
-                  L.mean_o1, L.rstd_o1));
+      TRY(X.fwd_ln(n.op, n.tff));
+      TRY(X.fwd_ln(n.fp0, n.op));
     } else {
-      TRY(launch_ln_fwd(L.y_t3, L.tri, a->trimodal_features, L.mean_t3, L.rstd_t3, X.V(P_TFF_G), X.V(P_TFF_BT), B, FUS, f32, s));
-      TRY(X.run1(X.fwd(L.tri, f32, FUS, P_OP_W, P_OP_B, L.y_o1, FUS, B, 1, SITE_OUT_PROJ)));
-      TRY(launch_ln_fwd(L.y_o1, L.fused, a->fused_features, L.mean_o1, L.rstd_o1, X.V(P_OP_G), X.V(P_OP_BT), B, FUS, f32, s));
+      TRY(X.ln_fwd(n.tff));
+      TRY(X.run1(X.fwd(n.op)));
+      TRY(X.ln_fwd(n.op));
+      TRY(X.run1(X.fwd(n.fp0)));
     }
-    {
-      // F14-F15: feature_processor (deer.py:246)
-      if (!lnf) TRY(X.run1(X.fwd(L.fused, f32, FUS, P_FP0_W, P_FP0_B, L.h1, HID, B, 1, SITE_FP0)));
-      TRY(X.run1(X.fwd(L.h1, f32, HID, P_FP1_W, P_FP1_B, L.h2, HID, B, 1, SITE_FP1)));
-      // F16: the three DEERLayer first layers stacked into one N = 384 GEMM (deer.py:49)
-      {
-        GemmProblem p = X.fwd(L.h2, f32, HID, P_EV0_W, P_EV0_B, L.e1, 3 * EV1, B, 1, SITE_EV0);
-        p.N = 3 * EV1;
-        TRY(X.run1(p));
-      }
-      // F17: second layers, strided-batched over the heads (deer.py:52)
-      {
-        GemmProblem p = X.fwd(L.e1, f32, 3 * EV1, P_EV1_W, P_EV1_B, L.e2, 3 * EV2, B, 1, SITE_EV1);
-        p.batch = 3; p.sA = EV1; p.sB = (long long)EV2 * EV1; p.sC = EV2; p.sBias = EV2;
-        TRY(X.run1(p));
-      }
-    }
+    TRY(X.run1(X.fwd(n.fp1)));    // F15
+    TRY(X.run1(X.fwd(n.ev0)));    // F16: one N = 384 GEMM
+    TRY(X.run1(X.fwd(n.ev1)));    // F17: strided-batched over the heads
   }
-  if (!chains) MARK("F9-F17 separate launches");
+  if (!plan.chains) MARK("F9-F17 separate launches");
   // F18: last layer (64 -> 4), NIG activations, uncertainties and -- with targets -- the loss statistics
-  if (!nig_tail) {
+  if (!plan.nig_tail) {
     TRY(launch_nig_fwd(L.e2, X.W(P_EV2_W), X.V(P_EV2_B), 64, L.evid, a->nig_out, a->targets, L.stats, B, f32, s));
     MARK("nig_fwd (head's last layer + loss statistics)");
   }
@@ -705,20 +782,12 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
   MMDEER_CHECK(a->audio && a->video && a->text, "audio / video / text must be non-NULL");
   hipStream_t s = (hipStream_t)a->stream;
   const Layout L = make_layout(a->workspace, a->weights, B, f32);
-  Exec X;
-  X.B = B; X.f32 = f32; X.es = f32 ? 4 : 2; X.L = &L; X.s = s;
-  X.drop_on = a->training && a->dropout_p > 0.f;
-  // bump_offset_dev: the matching forward ran with it -- the pending 1 is added here too, and the last launch of the pass (of phase
-  // 2 in the two-call mode) advances the counter
-  const bool bump = a->bump_offset_dev && a->offset_dev;
-  X.dc = make_drop(a->dropout_p, a->seed, a->offset + (bump ? 1 : 0), a->offset_dev);
-  X.mask_scale = X.drop_on ? X.dc.scale : 1.f;
-  const int in_f32 = a->inputs_bf16 ? 0 : 1;
-  const size_t es = X.es;
+  // (bump_offset_dev: the matching forward ran with it)
+  Exec X = make_exec(L, B, f32, s, a->training, a->dropout_p, a->seed, a->offset, a->offset_dev, a->bump_offset_dev);
+  const Net n = make_net(L, B, f32, a->audio, a->video, a->text, a->inputs_bf16 ? 0 : 1, nullptr, nullptr, nullptr);
   float* G = a->grads;
-  const int nwp = nig_tail_plan(B, f32) ? (B + 15) / 16 : 0;      // the forward left wave partials of the loss statistics
   const LossCfg cfg = loss_cfg(a->loss);
-  const int nblk = nig_nblocks(B), npl = ln_bwd_nparts(B);
+  const int nblk = nig_nblocks(B);
 
   // The q/k thirds of the AV in_proj never receive a gradient (L = S = 1): exact zeros in the reference.  They are
   // not touched here -- like the alignment gaps they keep the zeros of the caller's one-time initialisation of the
@@ -735,24 +804,15 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
     }
     t.nseg = k;
   };
-  // `chained`: the partial slabs were written by a layer chain, one per workgroup of ITS grid (32-sample workgroups above B = 4096)
-  auto reduce_ln = [&](ReduceTable& t, const float* part, int pidG, int N, bool chained) {
-    int k = t.nseg;   // gamma and beta slices are adjacent in the flat buffer (N is a multiple of 64)
-    t.src[k] = part; t.dst[k] = G + kParams[pidG].off; t.nparts[k] = chained ? chain_workgroups(B) : npl; t.n[k] = 2 * N; t.stride[k] = 2 * N; ++k;
-    t.nseg = k;
-  };
   // All weight-gradient problems are collected and run as ONE launch after the chain: a bucket on its own has
   // only 30-180 workgroups of 16-32 sequential K-steps, i.e. each of three launches took one workgroup's latency
   // (~35-40 us) on a mostly idle chip; together they fill it once.
   GemmGroup dwg{};
   ReduceTable rt{};
-  auto add_dw = [&](const GemmProblem& q) { dwg.p[dwg.nprob++] = q; };
+  auto add_dw = [&](const Layer& l) { dwg.p[dwg.nprob++] = X.dw(l, G); };
   const int phase = a->phase;
   MMDEER_CHECK(phase >= 0 && phase <= 2, "backward: phase must be 0, 1 or 2 (got %d)", phase);
-  // backward chains (chain.hip): the head / trimodal run always when enabled; the audio-visual run only in the single-call mode
-  // (in the two-call mode its first product, the token-0 dX, belongs to the first call)
-  const int bmin = opt(OPT_CHAIN_MIN);
-  const bool dchain = !f32 && opt(OPT_CHAIN) && opt(OPT_CHAIN_BWD) && B >= bmin && B <= opt(OPT_CHAIN_MAX) && phase == 0;
+  const Plan plan = make_plan(B, f32, phase, a->g_fused != nullptr, a->inputs_bf16 != 0, a->targets != nullptr);
   // The end of the pass (or of phase 1): one launch of every weight-gradient problem collected + the fold of all partial slabs, then
   // the events of buckets [first_bucket, last_bucket], which are final now.  Per-bucket launches, also on a side stream beside the dX
   // chain, were measured slower: a bucket alone is 30-180 workgroups of 16-32 sequential K-steps on a mostly idle chip.
@@ -762,7 +822,8 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
       MARK("weight gradients (all problems, one launch)");
       for (int i = 0; i < dwg.nprob; ++i) Exec::add_slab_segments(rt, dwg.p[i]);
     }
-    if (bump && (phase == 0 || phase == 2)) rt.bump = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(a->offset_dev));
+    // the last launch of the pass (of phase 2 in the two-call mode) advances the dropout step counter
+    if (X.bump && (phase == 0 || phase == 2)) rt.bump = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(a->offset_dev));
     TRY(launch_reduce_partials(rt, s));
     MARK("reduce_partials (fold)");
     for (int b = first_bucket; b <= last_bucket; ++b)
@@ -774,53 +835,27 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
   // ================= bucket 0: DEER head =================
   // B1: last head layer + NIG activations (+ loss gradient): a launch of its own, or (bf16 chain plan, loss mode, option chain_nig)
   // the prologue of the backward chain below -- the head kernel is 8 us of mostly fixed launch cost at B = 4096
-  const bool bchain = !f32 && opt(OPT_CHAIN) && opt(OPT_CHAIN_BWD) && B >= bmin && B <= opt(OPT_CHAIN_MAX) && !a->g_fused;
-  const bool nigfold = bchain && opt(OPT_CHAIN_NIG) && a->targets;
-  if (!nigfold)
+  if (!plan.nigfold)
     TRY(launch_nig_bwd(L.e2, X.W(P_EV2_W), L.evid, a->targets, L.stats, a->targets ? a->global_stats : nullptr, a->g_mu, a->g_nu, a->g_alpha, a->g_beta, nullptr,
-                       L.dz2, L.part_w3, L.part_b3, a->loss_out, a->bin_counts, B, f32, X.mask_scale, cfg, nwp, s));
-  if (!nigfold) MARK("nig_bwd (head's last layer backward + loss gradient)");
+                       L.dz2, L.part_w3, L.part_b3, a->loss_out, a->bin_counts, B, f32, X.mask_scale, cfg, plan.nwp, s));
+  if (!plan.nigfold) MARK("nig_bwd (head's last layer backward + loss gradient)");
   // B2-B10 are local to a sample like the forward's layers: in bf16 mode (chain_min <= B <= chain_max, no outside gradient on fused_features)
   // ONE launch of the layer-chain kernel walks the head's four dX products, both LayerNorm backwards and the three trimodal dX
   // products with the rows resident in LDS, and writes the same workspace buffers (the weight-gradient launch reads them)
-  if (bchain) {
-    ChainArgs c{};
-    c.X = reinterpret_cast<const bf16_t*>(L.dz2); c.ldx = 3 * EV2; c.K0 = 3 * EV2; c.B = B; c.groups = 1; c.group_stride = 0;
-    c.drop = X.dc;
-    auto dxseg = [&](int pidW, int N, int K, void* stash, const void* ymask, int ldmask) {
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = X.WTF(pidW); q.N = N; q.K = K; q.ldw = K;
-      q.end_layer = 1; q.nout = N; q.stash = reinterpret_cast<bf16_t*>(stash); q.ld_stash = N;
-      q.mask_y = reinterpret_cast<const bf16_t*>(ymask); q.ld_mask = ldmask; q.mask_scale = X.mask_scale;
-      return q;
-    };
-    auto with_lnb = [&](ChainSeg q, int pidG, const void* y, const float* mean, const float* rstd, void* dz, float* part) {
-      q.lnb_gamma = X.V(pidG); q.lnb_y = reinterpret_cast<const bf16_t*>(y); q.lnb_mean = mean; q.lnb_rstd = rstd;
-      q.lnb_dz = reinterpret_cast<bf16_t*>(dz); q.lnb_partial = part; q.lnb_mask_scale = X.mask_scale;
-      return q;
-    };
-    int k = 0;
-    for (int z = 0; z < 3; ++z) {     // evidence_net layer 3 (128 -> 64) per head: W^T [128][64], dX masked by e1
-      ChainSeg q = dxseg(P_EV1_W, EV1, EV2, nullptr, L.e1, 3 * EV1);
-      q.W += (size_t)z * EV2 * EV1;
-      q.kin_off = z * EV2; q.nout_off = z * EV1; q.mask_col0 = z * EV1;
-      q.end_layer = z == 2; q.nout = 3 * EV1;
-      if (z == 2) { q.stash = reinterpret_cast<bf16_t*>(L.de1); q.ld_stash = 3 * EV1; }
-      c.seg[k++] = q;
-    }
-    c.seg[k++] = dxseg(P_EV0_W, HID, 3 * EV1, L.dh2, L.h2, HID);          // evidence_net layer 0: W^T of the stacked heads [256][384]
-    c.seg[k++] = dxseg(P_FP1_W, HID, HID, L.dh1, L.h1, HID);              // feature_processor
-    c.seg[k++] = with_lnb(dxseg(P_FP0_W, FUS, HID, L.dfused, nullptr, 0), P_OP_G, L.y_o1, L.mean_o1, L.rstd_o1, L.dz_o1, L.part_ln_o1);
-    c.seg[k++] = with_lnb(dxseg(P_OP_W, FUS, FUS, L.dtri, nullptr, 0), P_TFF_G, L.y_t3, L.mean_t3, L.rstd_t3, L.dz_t3, L.part_ln_t3);
-    c.seg[k++] = dxseg(P_TFF_W, FUS, FUS, L.dpool, nullptr, 0);
-    c.seg[k++] = dxseg(P_TOUT_W, FUS, FUS, L.dobar, nullptr, 0);         // attention out_proj (pooled context)
-    c.nseg = k;
-    if (nigfold) {
+  if (plan.bchain) {
+    ChainArgs c = X.chain(n.ev1.dout, n.ev1.heads * n.ev1.N, 1, 0);
+    X.dx_seg(c, n.ev1);
+    X.dx_seg(c, n.ev0);
+    X.dx_seg(c, n.fp1);
+    X.dx_seg(c, n.fp0, &n.op);
+    X.dx_seg(c, n.op, &n.tff);
+    X.dx_seg(c, n.tff);
+    X.dx_seg(c, n.tout);
+    if (plan.nigfold) {
       ChainNig& g = c.nig;
       g.enabled = 1;
       g.e2 = reinterpret_cast<const bf16_t*>(L.e2); g.w3 = reinterpret_cast<const bf16_t*>(X.W(P_EV2_W)); g.evid = L.evid;
-      g.targets = a->targets; g.stats = L.stats; g.gstats = a->global_stats; g.nblk = nblk; g.nwp = nwp;
+      g.targets = a->targets; g.stats = L.stats; g.gstats = a->global_stats; g.nblk = nblk; g.nwp = plan.nwp;
       g.dz2 = reinterpret_cast<bf16_t*>(L.dz2); g.partial_w = L.part_w3; g.partial_b = L.part_b3;
       g.loss_out = a->loss_out; g.bin_counts = a->bin_counts; g.mask_scale = X.mask_scale; g.cfg = cfg;
     }
@@ -828,48 +863,30 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
     c.stamps = reinterpret_cast<unsigned long long*>(L.davin);   // diagnostic library: untouched until phase 2 (tools/chain_stamps.py bwd)
 #endif
     TRY(launch_chain(c, s));
-    MARK(nigfold ? "chain B1-B10 (head backward + loss gradient + head / trimodal dX)" : "chain B2-B10 (head / trimodal dX)");
-  } else
-  {
-    // evidence_net layer 3 (128 -> 64), batched over heads: dX masked by e1
-    {
-      GemmProblem p = X.dx(L.dz2, 3 * EV2, P_EV1_W, L.de1, 3 * EV1, B, L.e1, 3 * EV1);
-      p.batch = 3; p.sA = EV2; p.sB = (long long)EV2 * EV1; p.sC = EV1; p.sY = EV1;
-      TRY(X.run1(p));
-    }
-    // evidence_net layer 0 (256 -> 3 x 128 stacked)
-    {
-      GemmProblem p = X.dx(L.de1, 3 * EV1, P_EV0_W, L.dh2, HID, B, L.h2, HID);
-      p.K = 3 * EV1; p.ldb = 3 * EV1;   // W^T of the stacked heads: [256][384]
-      TRY(X.run1(p));
-    }
-    // feature_processor
-    TRY(X.run1(X.dx(L.dh2, HID, P_FP1_W, L.dh1, HID, B, L.h1, HID)));
-    TRY(X.run1(X.dx(L.dh1, HID, P_FP0_W, L.dfused, FUS, B, nullptr, 0)));
+    MARK(plan.nigfold ? "chain B1-B10 (head backward + loss gradient + head / trimodal dX)" : "chain B2-B10 (head / trimodal dX)");
+  } else {
+    TRY(X.run1(X.dx(n.ev1)));
+    TRY(X.run1(X.dx(n.ev0)));
+    TRY(X.run1(X.dx(n.fp1)));
+    TRY(X.run1(X.dx(n.fp0)));
   }
   // a gradient that reaches fused_features from outside the head (a caller's own consumer of that output)
   if (a->g_fused) TRY(launch_add_f32(L.dfused, f32, a->g_fused, (long long)B * FUS, s));
-  {
-    GemmProblem q = X.dw(L.dz2, 3 * EV2, L.e1, f32, 3 * EV1, P_EV1_W, P_EV1_B, G, B);
-    q.batch = 3; q.sA = EV2; q.sB = EV1; q.sC = (long long)EV2 * EV1; q.sBiasGrad = EV2;
-    add_dw(q);
-    GemmProblem r = X.dw(L.de1, 3 * EV1, L.h2, f32, HID, P_EV0_W, P_EV0_B, G, B);
-    r.M = 3 * EV1;
-    add_dw(r);
-    add_dw(X.dw(L.dh2, HID, L.h1, f32, HID, P_FP1_W, P_FP1_B, G, B));
-    add_dw(X.dw(L.dh1, HID, L.fused, f32, FUS, P_FP0_W, P_FP0_B, G, B));
-    reduce_head(rt, nigfold ? chain_workgroups(B) : nblk);
-  }
+  add_dw(n.ev1);
+  add_dw(n.ev0);
+  add_dw(n.fp1);
+  add_dw(n.fp0);
+  reduce_head(rt, plan.nigfold ? chain_workgroups(B) : nblk);
 
   // ================= bucket 1: output_projection + trimodal fusion =================
-  if (!bchain) {
-    TRY(launch_ln_bwd(L.dfused, L.y_o1, L.mean_o1, L.rstd_o1, X.V(P_OP_G), L.dz_o1, L.part_ln_o1, B, FUS, f32, X.mask_scale, s));
-    TRY(X.run1(X.dx(L.dz_o1, FUS, P_OP_W, L.dtri, FUS, B, nullptr, 0)));
-    TRY(launch_ln_bwd(L.dtri, L.y_t3, L.mean_t3, L.rstd_t3, X.V(P_TFF_G), L.dz_t3, L.part_ln_t3, B, FUS, f32, X.mask_scale, s));
-    TRY(X.run1(X.dx(L.dz_t3, FUS, P_TFF_W, L.dpool, FUS, B, nullptr, 0)));
-    TRY(X.run1(X.dx(L.dpool, FUS, P_TOUT_W, L.dobar, FUS, B, nullptr, 0)));      // attention out_proj (pooled context)
+  if (!plan.bchain) {
+    TRY(X.ln_bwd(n.op, n.fp0));
+    TRY(X.run1(X.dx(n.op)));
+    TRY(X.ln_bwd(n.tff, n.op));
+    TRY(X.run1(X.dx(n.tff)));
+    TRY(X.run1(X.dx(n.tout)));
   }
-  if (!bchain) MARK("B2-B10 separate launches");
+  if (!plan.bchain) MARK("B2-B10 separate launches");
   if (!f32 && opt(OPT_FUSED_ATTN) && opt(OPT_QKV_RECOMPUTE)) {   // the forward kept q|k|v on chip: recompute the head tiles
     TRY(launch_tri_fused_bwd(L.xtok, L.wqkv_hm, X.V(P_TIN_B), L.dobar, L.probs, L.dqkv, B, X.drop_on ? 1 : 0, X.dc, s));
     MARK("tri_fused_kernel<1> (attention backward, recompute)");
@@ -877,20 +894,18 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
     TRY(launch_tri_attn_bwd(L.qkv, L.dobar, L.probs, L.dqkv, B, f32, X.drop_on ? 1 : 0, X.dc, s));
     MARK("attention backward (unfused)");
   }
-  TRY(X.run1(X.dx(L.dqkv, 3 * FUS, P_TIN_W, L.dxtok, FUS, 2 * B, nullptr, 0)));  // in_proj
+  TRY(X.run1(X.dx(n.tin)));
   MARK("in_proj dX GEMM");
-  // (with the AV chain below, this product is its first segment)
-  if (!dchain) TRY(X.run1(X.dx(L.dxtok, 2 * FUS, P_AVP_W, L.dav, INTER, B, nullptr, 0)));     // token 0 -> audiovisual features
-  {
-    add_dw(X.dw(L.dz_o1, FUS, L.tri, f32, FUS, P_OP_W, P_OP_B, G, B));
-    add_dw(X.dw(L.dz_t3, FUS, L.pool, f32, FUS, P_TFF_W, P_TFF_B, G, B));
-    add_dw(X.dw(L.dpool, FUS, L.obar, f32, FUS, P_TOUT_W, P_TOUT_B, G, B));
-    add_dw(X.dw(L.dqkv, 3 * FUS, L.xtok, f32, FUS, P_TIN_W, P_TIN_B, G, 2 * B));
-    add_dw(X.dw(L.dxtok, 2 * FUS, L.av, f32, INTER, P_AVP_W, P_AVP_B, G, B));                          // token 0
-    add_dw(X.dw(L.dxtok + (size_t)FUS * es, 2 * FUS, a->text, in_f32, TXT, P_TXT_W, P_TXT_B, G, B));   // token 1
-    reduce_ln(rt, L.part_ln_o1, P_OP_G, FUS, bchain);
-    reduce_ln(rt, L.part_ln_t3, P_TFF_G, FUS, bchain);
-  }
+  // token 0 -> audiovisual features (with the AV chain below, this product is its first segment)
+  if (!plan.dchain) TRY(X.run1(X.dx(n.avp)));
+  add_dw(n.op);
+  add_dw(n.tff);
+  add_dw(n.tout);
+  add_dw(n.tin);
+  add_dw(n.avp);
+  add_dw(n.txt);
+  X.add_ln_segment(rt, n.op, G, plan.bchain);
+  X.add_ln_segment(rt, n.tff, G, plan.bchain);
   if (phase == 1) return finish(0, 1);
   }   // phase != 2
 
@@ -902,80 +917,31 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
   // B13-B17 (token-0 dX, LayerNorm backward, the three AV dX products) are sample-local as well: one more launch of the chain
   // kernel.  The concatenation's backward is a re-view of the panel: columns [0,256) / [256,512) of d cat become the rows of the
   // audio->video / video->audio call.
-  if (dchain) {
-    ChainArgs c{};
-    c.X = reinterpret_cast<const bf16_t*>(L.dxtok); c.ldx = 2 * FUS; c.K0 = FUS; c.B = B; c.groups = 1; c.group_stride = B;
-    c.drop = X.dc;
-    auto dxs = [&](const bf16_t* wt, int N, int K, int ldw, void* stash, int ld_stash, int nout) {
-      ChainSeg q;
-      chain_seg_defaults(q);
-      q.W = wt; q.N = N; q.K = K; q.ldw = ldw;
-      q.end_layer = 1; q.nout = nout; q.stash = reinterpret_cast<bf16_t*>(stash); q.ld_stash = ld_stash;
-      return q;
-    };
-    int k = 0;
-    {   // token 0 -> audiovisual features, then the LayerNorm of fusion_layers backwards (mask of its Linear-ReLU-Dropout)
-      ChainSeg q = dxs(X.WTF(P_AVP_W), INTER, FUS, FUS, L.dav, INTER, INTER);
-      q.lnb_gamma = X.V(P_AVF_G); q.lnb_y = reinterpret_cast<const bf16_t*>(L.y_a2); q.lnb_mean = L.mean_a2; q.lnb_rstd = L.rstd_a2;
-      q.lnb_dz = reinterpret_cast<bf16_t*>(L.dz_a2); q.lnb_partial = L.part_ln_a2; q.lnb_mask_scale = X.mask_scale;
-      c.seg[k++] = q;
-    }
-    {   // fusion_layers dX: W^T [512][256]; the 512 columns = d cat, unfolded into the two calls' rows ([2B,256] stacked)
-      ChainSeg q = dxs(X.WTF(P_AVF_W), 2 * INTER, INTER, INTER, L.dcats, INTER, INTER);
-      q.fold_groups = 2;
-      c.seg[k++] = q;
-    }
-    {   // AV out_proj; dX gets the regenerated attention-dropout factor of the forward value projection
-      ChainSeg q = dxs(X.WTF(P_AOUT_W), INTER, INTER, INTER, L.davv, INTER, INTER);
-      if (X.drop_on) { q.drop_site = SITE_AV_ATTN; q.drop_shift = 5; }
-      c.seg[k++] = q;
-    }
-    // AV value projection (columns [2E, 3E) of W^T [256][768])
-    c.seg[k++] = dxs(X.WTF(P_AIN_W, (size_t)2 * INTER * INTER), INTER, INTER, INTER, L.davin, INTER, INTER);
-    c.nseg = k;
+  if (plan.dchain) {
+    ChainArgs c = X.chain(n.avp.dout, n.avp.N, 1, B);
+    X.dx_seg(c, n.avp, &n.avf);
+    X.dx_seg(c, n.avf);
+    X.dx_seg(c, n.aout);
+    X.dx_seg(c, n.avv);
     TRY(launch_chain(c, s));
     MARK("chain B13-B17 (audio-visual dX)");
   } else {
-    TRY(launch_ln_bwd(L.dav, L.y_a2, L.mean_a2, L.rstd_a2, X.V(P_AVF_G), L.dz_a2, L.part_ln_a2, B, INTER, f32, X.mask_scale, s));
-    // fusion_layers dX, written "stacked" ([2B,256]: rows [0,B) = d audio_attended, rows [B,2B) = d video_attended)
-    // by batching over the two column halves of the weight
-    {
-      GemmProblem p = X.dx(L.dz_a2, INTER, P_AVF_W, L.dcats, INTER, B, nullptr, 0);
-      p.N = INTER; p.batch = 2; p.sB = (long long)INTER * INTER; p.sC = (long long)B * INTER;   // rows [256 z, 256 z + 256) of W^T [512][256]
-      TRY(X.run1(p));
-    }
-    // AV out_proj; dX gets the regenerated attention-dropout factor of the forward value projection
-    {
-      GemmProblem p = X.dx(L.dcats, INTER, P_AOUT_W, L.davv, INTER, 2 * B, nullptr, 0);
-      if (X.drop_on) { p.regen_site = SITE_AV_ATTN; p.drop_shift = 5; }
-      TRY(X.run1(p));
-    }
-    // AV value projection (rows [2E,3E) of in_proj)
-    {
-      GemmProblem p = X.dx(L.davv, INTER, P_AIN_W, L.davin, INTER, 2 * B, nullptr, 0);
-      p.B = X.WT(P_AIN_W) + (size_t)2 * INTER * es;   // columns [2E, 3E) of W^T [256][768]
-      p.K = INTER;
-      TRY(X.run1(p));
-    }
+    TRY(X.ln_bwd(n.avf, n.avp));
+    TRY(X.run1(X.dx(n.avf)));
+    TRY(X.run1(X.dx(n.aout)));
+    TRY(X.run1(X.dx(n.avv)));
   }
-  {
-    add_dw(X.dw(L.dz_a2, INTER, L.cat, f32, 2 * INTER, P_AVF_W, P_AVF_B, G, B));
-    add_dw(X.dw(L.dcats, INTER, L.avv, f32, INTER, P_AOUT_W, P_AOUT_B, G, 2 * B));
-    GemmProblem q = X.dw(L.davv, INTER, L.avin, f32, INTER, P_AIN_W, P_AIN_B, G, 2 * B);
-    q.C = G + kParams[P_AIN_W].off + 2 * INTER * INTER;
-    q.bias_grad = G + kParams[P_AIN_B].off + 2 * INTER;
-    q.M = INTER;
-    X.set_split(q, G);
-    add_dw(q);
-    add_dw(X.dw(L.davin, INTER, a->video, in_f32, VID, P_VID_W, P_VID_B, G, B));                                  // rows [0,B)
-    if (f32) add_dw(X.dw(L.davin + (size_t)B * INTER * es, INTER, a->audio, in_f32, AUD, P_AUD_W, P_AUD_B, G, B));   // rows [B,2B)
-    else add_dw(X.dw(L.davin + (size_t)B * INTER * es, INTER, L.audio_pad, 0, AUD_PAD, P_AUD_W, P_AUD_B, G, B));    // padded copy of F0
-    reduce_ln(rt, L.part_ln_a2, P_AVF_G, INTER, dchain);
-  }
-  if (!dchain) MARK("B13-B17 separate launches");
+  add_dw(n.avf);
+  add_dw(n.aout);
+  add_dw(n.avv);
+  add_dw(n.vid);
+  add_dw(n.aud);
+  X.add_ln_segment(rt, n.avf, G, plan.dchain);
+  if (!plan.dchain) MARK("B13-B17 separate launches");
   // ---- default: all weight gradients in one grouped split-K launch + one deterministic fold of every partial slab
   return finish(phase == 2 ? 2 : 0, 2);
 }
+
 
 // ------------------------------------------------------------------ optimiser step
 int mmdeer_adamw_step(const mmdeer_adamw_args* a) {
@@ -1047,7 +1013,7 @@ int mmdeer_loss_stats(const void* workspace, size_t workspace_bytes, int batch, 
   MMDEER_CHECK(batch > 0, "loss_stats: batch must be > 0 (got %d)", batch);
   const Layout L = make_layout(const_cast<void*>(workspace), nullptr, batch, compute_f32 ? 1 : 0);
   MMDEER_CHECK(workspace_bytes >= L.bytes, "loss_stats: workspace of %zu bytes is smaller than the %zu of this batch", workspace_bytes, L.bytes);
-  return launch_nig_stats_sum(L.stats, batch, out, nig_tail_plan(batch, compute_f32 ? 1 : 0) ? (batch + 15) / 16 : 0, (hipStream_t)stream);
+  return launch_nig_stats_sum(L.stats, batch, out, make_plan(batch, compute_f32 ? 1 : 0, 0, false, false, false).nwp, (hipStream_t)stream);
 }
 
 }  // extern "C"
