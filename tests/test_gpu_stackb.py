@@ -500,3 +500,103 @@ def test_fused_train_step_graph_replay_trains_and_matches_eager():
     with torch.no_grad():
         out = m1(*xs)
     assert torch.isfinite(out["mu_all"]).all()
+
+
+# ---- the two launch plans and the oracle at other geometries: the tables the training path derives from its layer description
+#      (fragment-major images, transposed copies, stacked areas) at other depths and input widths
+SMALL = dict(audio_dim=40, video_dim=128, text_dim=384)     # K0 = 64 for the audio stem; 128 / 384: other widths the chain kernel instantiates
+
+
+def _geometry_model(compute, **cfg):
+    m = stackb.CompleteDEERModel(stackb.ModelConfig(**cfg), compute_dtype=compute)
+    tag = "stackb.g%d.%d" % (m.config.encoder_layers, m.config.video_dim)
+    P = {k: torch.from_numpy(v) for k, v in synth.module_fill(tag, {k: tuple(v.shape) for k, v in m.state_dict().items()}).items()}
+    m.load_state_dict(P)
+    return m.to("cuda:0"), P
+
+
+def _geometry_batch(cfg, B):
+    b = {k: synth.normal(900 + i, B * d).reshape(B, d).astype(np.float32)
+         for i, (k, d) in enumerate(zip(("audio", "video", "text"), (cfg.audio_dim, cfg.video_dim, cfg.text_dim)))}
+    b["targets"] = synth.make_batch(B, seed=36)["targets"]
+    return b
+
+
+GEOMETRIES = [dict(SMALL, encoder_layers=0), dict(SMALL, encoder_layers=1), dict(SMALL, encoder_layers=4),
+              dict(SMALL, video_dim=320, encoder_layers=3)]           # 320: a width the chain kernel does not instantiate
+_geo_id = lambda g: "L%d-v%d" % (g["encoder_layers"], g["video_dim"])
+
+
+@pytest.mark.parametrize("B", [2, 33])
+@pytest.mark.parametrize("geo", GEOMETRIES[:3], ids=_geo_id)
+def test_fused_train_step_plans_agree_at_other_geometries(geo, B):
+    """test_fused_train_step_layer_chains_match_the_launch_by_launch_plan at the smallest shapes that exercise the derived tables: no
+    residual block (nothing to duplicate into the bypass columns), one, and four (the 16 LayerNorm vectors of one chain); a 64-column
+    audio stem; B = 2 (the smallest batch whose uncertainties are a bf16 GEMM operand) and 33 (two full 16-sample workgroups and a row)."""
+    _plans_agree(geo, B, chain=True)
+
+
+def test_fused_train_step_runs_launch_by_launch_on_a_geometry_the_chains_refuse():
+    _plans_agree(GEOMETRIES[3], 33, chain=False)
+
+
+def _plans_agree(geo, B, chain):
+    import copy
+    m1, _ = _geometry_model("bf16", **geo)
+    m2 = copy.deepcopy(m1)
+    m1.train_plan, m2.train_plan = "ops", "auto"
+    xs, y = _batch_dev(_geometry_batch(m1.config, B))
+    m1.train(); m2.train()
+    m1._train_step = m2._train_step = 23
+    l1 = m1.train_step_fused(*xs, y)
+    l2 = m2.train_step_fused(*xs, y)
+    torch.cuda.synchronize()
+    T1, T2 = l1["_keep"][0], l2["_keep"][0]
+    assert not T1["chain"] and bool(T2["chain"]) == chain
+    assert float(l2["total_loss"]) == float(l1["total_loss"]) and np.isfinite(float(l1["total_loss"]))
+    assert torch.equal(l1["ece_bin_counts"], l2["ece_bin_counts"])
+    for key in ("E", "VV", "S", "X", "H1", "H2", "pre", "AV", "T", "r", "w4", "u4", "R2", "G", "fused", "fused32", "H0", "H3", "ev", "planes"):
+        assert torch.equal(T1[key], T2[key]), (key, int((T1[key] != T2[key]).sum()))
+    for name in ("av", "tri"):
+        for a, c in zip(T1[name], T2[name]):
+            assert torch.equal(a, c), name
+    for t1, t2 in zip(T1["enc"], T2["enc"]):
+        assert len(t1["y"]) == len(t2["y"]) == geo["encoder_layers"] and len(t1["h"]) == len(t2["h"]) == geo["encoder_layers"] + 1
+        for a, c in zip(t1["h"] + t1["y"] + [t1["y0"], t1["m0"], t1["r0"]], t2["h"] + t2["y"] + [t2["y0"], t2["m0"], t2["r0"]]):
+            assert torch.equal(a, c)
+        for (ma, ra), (mc, rc) in zip(t1["st"], t2["st"]):
+            assert torch.equal(ma, mc) and torch.equal(ra, rc)
+    seen = 0
+    for (n, p1), (_, p2) in zip(m1.named_parameters(), m2.named_parameters()):
+        assert torch.isfinite(p2.grad).all(), n
+        assert torch.equal(p1.grad, p2.grad), (n, float((p1.grad - p2.grad).abs().max()), float(p1.grad.abs().max()))
+        seen += float(p1.grad.abs().max()) > 0
+    assert seen >= 64 + 12 * geo["encoder_layers"]          # 68 + 12 L parameters carry a gradient (the slack of the test above: 100 of 104)
+
+
+@pytest.mark.parametrize("geo", GEOMETRIES[:3], ids=_geo_id)
+def test_stackb_gradients_match_the_oracle_at_other_geometries(geo):
+    """The launch-by-launch plan (fp32, dropout sites open) against the oracle's autograd, as
+    test_stackb_gradients_other_parameters_and_ragged_batches does at the default geometry -- same bounds.  video_dim = 320 (the
+    geometry of the test above) is not among the cases: at the commit before this test existed, and since, the fp32 gradient of
+    video_encoder.input_projection.0.weight misses these bounds there (4927 of 81920 elements, by up to 1.8e-3 against an allowance
+    of 1.7e-4; every parameter before it in the model's order passes).  Open: not yet looked into."""
+    O = _oracle()
+    m, P = _geometry_model("fp32", **geo)
+    B = 33
+    b = _geometry_batch(m.config, B)
+    xs, y = _batch_dev(b)
+    loss = m.compute_loss(m.forward_train(*xs, dropout=False), y)
+    loss["total_loss"].backward()
+    Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
+    o = O.stackb_forward(Pg, *(torch.from_numpy(b[k]) for k in ("audio", "video", "text")), layers=geo["encoder_layers"])
+    pred = {k: v.unsqueeze(1) for k, v in o.items() if k.split("_")[-1] in ("mu", "nu", "alpha", "beta") and v.dim() == 1}
+    ol = O.multitask_loss(pred, torch.from_numpy(b["targets"]))["total_loss"]
+    ol.backward()
+    assert float(loss["total_loss"]) == pytest.approx(float(ol.detach()), rel=3e-4)
+    for n, p in m.named_parameters():
+        if Pg[n].grad is None:
+            assert p.grad is None, n
+            continue
+        ref = Pg[n].grad.numpy()
+        np.testing.assert_allclose(p.grad.cpu().numpy(), ref, rtol=3e-3, atol=3e-3 * max(float(np.abs(ref).max()), 1e-12), err_msg=f"{n} {_geo_id(geo)}")

@@ -11,12 +11,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .opseq import set_drop
 
 K_OK = (64, 128, 256, 384, 512, 768)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class Chain:
@@ -29,10 +26,7 @@ class Chain:
         a = self.a
         a.X, a.ldx, a.K0, a.rows, a.samples_per_workgroup, a.nseg = X.data_ptr(), ldx, K0, rows, ts, 0
         a.dropout_p = float(p)
-        if ex.drop is not None:
-            a.seed, a.offset = ex.drop[1], ex.drop[2]
-            if len(ex.drop) > 3 and ex.drop[3] is not None:
-                a.offset_dev = ex.drop[3].data_ptr()
+        set_drop(a, ex.drop)
         a.stream = ex.s
         self.keep = [X]
 
@@ -43,9 +37,9 @@ class Chain:
             raise ValueError("chain: too many segments")
         s = a.seg[a.nseg]
         a.nseg += 1
-        s.W, s.bias, s.N, s.K, s.kin_off, s.nout_off, s.relu = W.data_ptr(), _p(bias), N, K, kin, nout_off, relu
+        s.W, s.bias, s.N, s.K, s.kin_off, s.nout_off, s.relu = W.data_ptr(), _lib.ptr(bias), N, K, kin, nout_off, relu
         s.drop_site, s.drop_shift, s.dcol_off = (site if a.dropout_p > 0 else -1), shift, dcol
-        s.mask_y, s.ld_mask, s.mask_col0, s.mask_scale = _p(mask), ldm, mcol, mscale
+        s.mask_y, s.ld_mask, s.mask_col0, s.mask_scale = _lib.ptr(mask), ldm, mcol, mscale
         s.res_add, s.res_dup = res_add, res_dup
         self.keep += [W, bias, mask]
         return self
@@ -54,7 +48,7 @@ class Chain:
         """ln = (gamma, beta, xln, mean, rstd); lnb = (gamma, y, mean, rstd, dz, partial, mask_scale)."""
         s = self.a.seg[self.a.nseg - 1]
         s.end_layer, s.nout = 1, nout
-        s.stash, s.ld_stash, s.stash2, s.stash_split = _p(stash), ld_stash, _p(stash2), split
+        s.stash, s.ld_stash, s.stash2, s.stash_split = _lib.ptr(stash), ld_stash, _lib.ptr(stash2), split
         self.keep += [stash, stash2]
         if ln is not None:
             g, b, xln, mean, rstd = ln

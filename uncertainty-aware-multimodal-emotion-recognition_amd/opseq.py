@@ -13,8 +13,13 @@ import torch
 from . import _lib
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+def set_drop(a, drop) -> None:
+    """The dropout stream of a launch into its argument struct.  drop: None or (p_config, seed, step[, device int64 counter tensor
+    added to the step on the device -- HIP-graph replays])."""
+    if drop is not None:
+        a.seed, a.offset = drop[1], drop[2]
+        if len(drop) > 3 and drop[3] is not None:
+            a.offset_dev = drop[3].data_ptr()
 
 
 class Exec:
@@ -37,7 +42,7 @@ class Exec:
             return Cm
         a = _lib.GemmArgs()
         a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-        a.bias, a.bias_grad, a.Y = _ptr(bias), _ptr(bias_grad), _ptr(Y)
+        a.bias, a.bias_grad, a.Y = _lib.ptr(bias), _lib.ptr(bias_grad), _lib.ptr(Y)
         a.M, a.N, a.K, a.lda, a.ldw, a.ldc, a.ldy = M, N, K, lda, ldw, ldc, ldy
         a.a_f32, a.w_f32, a.c_f32 = int(A.dtype == torch.float32), int(W.dtype == torch.float32), int(Cm.dtype == torch.float32)
         a.y_f32 = int(Y is not None and Y.dtype == torch.float32)
@@ -46,9 +51,8 @@ class Exec:
         a.drop_site, a.drop_shift, a.regen_site = drop_site, drop_shift, regen_site
         a.mask_scale = mask_scale
         if self.drop is not None:
-            a.dropout_p, a.seed, a.offset = p, self.drop[1], self.drop[2]
-            if len(self.drop) > 3 and self.drop[3] is not None:
-                a.offset_dev = self.drop[3].data_ptr()          # device counter added to the offset (HIP-graph replays)
+            a.dropout_p = p
+        set_drop(a, self.drop)
         a.stream = self.s
         slab = None
         if splitk > 1 and Cm.dtype == torch.float32 and Cm.is_contiguous():
@@ -93,7 +97,7 @@ class Exec:
         if self.deferred is not None and gw.is_contiguous() and gw.stride(0) == K:
             # grouped form (mmdeer_gemm_batch): up to 16 weight-gradient problems per launch + one fold, as mmdeer_backward does
             a = _lib.GemmArgs()
-            a.A, a.W, a.C, a.bias_grad = dy.data_ptr(), x.data_ptr(), gw.data_ptr(), _ptr(gb)
+            a.A, a.W, a.C, a.bias_grad = dy.data_ptr(), x.data_ptr(), gw.data_ptr(), _lib.ptr(gb)
             a.M, a.N, a.K, a.lda, a.ldw, a.ldc = N, K, M, ldy_, ldx, K
             a.a_f32, a.w_f32, a.c_f32 = int(dy.dtype == torch.float32), int(x.dtype == torch.float32), 1
             a.trans_a, a.trans_w, a.compute_f32, a.tile = 1, 1, self.f32, -1
@@ -118,11 +122,11 @@ class Exec:
         _lib.check(self.lib.mmdeer_gemm_batch(arr, n, slab.data_ptr(), slab.numel(), self.s))
         self.deferred = []
 
-    def ln_fwd(self, y, gamma, beta):
+    def ln_fwd(self, y, gamma, beta, out=None, mean=None, rstd=None):
         M, N = y.shape
-        out = torch.empty_like(y)
-        mean = torch.empty(M, dtype=torch.float32, device=y.device)
-        rstd = torch.empty_like(mean)
+        out = torch.empty_like(y) if out is None else out
+        mean = torch.empty(M, dtype=torch.float32, device=y.device) if mean is None else mean
+        rstd = torch.empty_like(mean) if rstd is None else rstd
         if M:
             _lib.check(self.lib.mmdeer_layernorm_fwd(y.data_ptr(), out.data_ptr(), None, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
                                                      beta.data_ptr(), M, N, self.f32, self.s))
@@ -149,10 +153,10 @@ class Exec:
         _lib.check(self.lib.mmdeer_reduce_batch(n, src, dst, nparts, cnt, stride, self.s))
         self.folds = []
 
-    def ln_bwd(self, dout, y, mean, rstd, gamma, ggamma, gbeta, mask_scale):
+    def ln_bwd(self, dout, y, mean, rstd, gamma, ggamma, gbeta, mask_scale, dz=None):
         """dz = (y > 0) * mask_scale * LayerNorm'(dout); ggamma / gbeta fp32 (N,)."""
         M, N = y.shape
-        dz = torch.empty_like(y)
+        dz = torch.empty_like(y) if dz is None else dz
         if M and self.folds is not None and N % 4 == 0:
             np_ = self.lib.mmdeer_layernorm_bwd_nparts(M)
             part = torch.empty(np_ * 2 * N, dtype=torch.float32, device=y.device)
@@ -170,6 +174,6 @@ class Exec:
 
     def add(self, out, x, y=None, mask=None, scale=1.0):
         M, N = x.shape
-        _lib.check(self.lib.mmdeer_add_masked(out.data_ptr(), out.stride(0), x.data_ptr(), x.stride(0), _ptr(y), y.stride(0) if y is not None else 0,
-                                              _ptr(mask), mask.stride(0) if mask is not None else 0, scale, M, N, self.f32, self.s))
+        _lib.check(self.lib.mmdeer_add_masked(out.data_ptr(), out.stride(0), x.data_ptr(), x.stride(0), _lib.ptr(y), y.stride(0) if y is not None else 0,
+                                              _lib.ptr(mask), mask.stride(0) if mask is not None else 0, scale, M, N, self.f32, self.s))
         return out

@@ -378,30 +378,11 @@ class CompleteDEERModel(nn.Module):
             by_id[id(p)] = (offs[n], p.numel())
         f32 = self.compute_dtype == "fp32"
         packed = flat_p if f32 else torch.empty(cur, dtype=torch.bfloat16, device=dev)
-        # transposed compute-dtype copies of the matrices whose dX the backward needs, at the same offsets; the three operands
-        # that are concatenations / a column slice of parameters get areas of their own behind the last parameter
-        att, fu, cfgm = self.attention_module, self.fusion_module, self.config
-        sa, ca, wn = att.self_attention, att.cross_attention, att.weight_network
-        nets = [self.prediction_heads[n].evidence_network for n in DIM_NAMES]
-        E_, D3 = cfgm.encoder_dim, 3 * cfgm.encoder_dim
-        extra, tab = {}, []                       # tab: (parameter, dst_off, ld_dst, dst_col)
-        def area(key, elems):
-            nonlocal cur_t
-            extra[key] = cur_t
-            cur_t += (elems + 63) // 64 * 64
-        cur_t = cur
-        area("wv", E_ * 2 * E_); area("wn1", (D3 + 3) * E_); area("wh0", cfgm.fusion_dim * 3 * 256)
-        plain = [e.output_projection.weight for e in (self.audio_encoder, self.video_encoder, self.text_encoder)]
-        plain += [blk.layers[0].weight for e in (self.audio_encoder, self.video_encoder, self.text_encoder) for blk in e.encoder_layers]
-        est = att.uncertainty_estimator.estimator
-        plain += [sa.output_proj.weight, ca.output_proj.weight, est[0].weight, est[3].weight, fu.av_fusion[0].weight, fu.av_fusion[4].weight,
-                  fu.trimodal_fusion[0].weight, fu.trimodal_fusion[4].weight, fu.fusion_gate[0].weight] + [n[3].weight for n in nets]
-        for w in plain:
-            tab.append((w, by_id[id(w)][0], 0, 0))
-        tab.append((sa.value_proj.weight, extra["wv"], 2 * E_, 0)); tab.append((ca.value_proj.weight, extra["wv"], 2 * E_, E_))
-        tab.append((wn[0].weight, extra["wn1"], 0, 0))
-        for d, n in enumerate(nets):
-            tab.append((n[0].weight, extra["wh0"], 3 * 256, d * 256))
+        # transposed compute-dtype copies of the matrices whose dX the backward needs, at the same offsets; the operands that are
+        # concatenations / a column slice of parameters get areas of their own behind the last parameter (stackb_layers.py)
+        from . import stackb_layers
+        layers = stackb_layers.Layers(self)
+        tab, extra, cur_t = layers.transposed_table(lambda w: by_id[id(w)][0], cur)      # tab: (parameter, dst_off, ld_dst, dst_col)
         packed_t = torch.empty(cur_t, dtype=torch.float32 if f32 else torch.bfloat16, device=dev)
         nt = len(tab)
         vp = C.c_void_p
@@ -410,11 +391,10 @@ class CompleteDEERModel(nn.Module):
               "ld": (C.c_int32 * nt)(*[l for _, _, l, _ in tab]), "col": (C.c_int32 * nt)(*[c for _, _, _, c in tab])}
         st = {"dev": dev, "offs": offs, "n": cur, "p": flat_p, "g": flat_g, "packed": packed, "by_id": by_id, "gview": gview,
               "ptrs": [p.data_ptr() for _, p in named], "versions": None, "names": [n for n, _ in named],
-              "packed_t": packed_t, "extra_t": extra, "ttab": tt}
+              "packed_t": packed_t, "extra_t": extra, "ttab": tt, "layers": layers, "views": {}}
         st["frag"] = None
         if not f32:
-            from . import stackb_train
-            st["frag"] = stackb_train.build_frag_images(self, st)
+            st["frag"] = stackb_layers.frag_images(self, st)
         self._flat_state = st
         self._packed = None
         return st
@@ -436,7 +416,7 @@ class CompleteDEERModel(nn.Module):
         t = st["ttab"]
         _lib.check(_lib.load().mmdeer_pack_transposed_batch(t["n"], t["src"], t["rows"], t["cols"], st["packed_t"].data_ptr(), t["off"], t["ld"],
                                                             t["col"], int(st["packed"] is st["p"]), _lib.current_stream()))
-        if st.get("frag") is not None:       # bf16: the fragment-major images the layer chains stream (stackb_train.py), from the copies above
+        if st.get("frag") is not None:       # bf16: the fragment-major images the layer chains stream (stackb_layers.py), from the copies above
             st["frag"].refresh()
 
     def train_step_fused(self, audio, video, text, targets) -> Dict[str, torch.Tensor]:
