@@ -727,6 +727,13 @@ int mmdeer_uncertainty_table(const float* pred, const float* target, const float
  * operators below are the remaining row-wise pieces; mmdeer_stackb_forward (further down) strings everything together.  Activations ("act") are fp32 when act_f32 != 0, else bf16; parameters and
  * the listed outputs are fp32.  encoder_dim 256 / fusion_dim 512 (ModelConfig defaults, complete_project.py:33-56).
  *
+ * Alignment, for every row operator from here to mmdeer_outer_bwd (Stack B eval and training, the fusion row operators):
+ * they read and write 4 elements at a time, so every act pointer -- and with it every row, the leading dimensions being
+ * multiples of 4 -- starts on 4 elements (16 bytes in fp32, 8 bytes in bf16), and so do the fp32 buffers ev, out32,
+ * weights4, unc4 and weights8 (16 bytes).  x1 / dx1 of the outer products (any ld1), logits, g4, the [B][3] outputs and
+ * the parameter vectors carry no such rule.  A misaligned pointer is refused like any other bad argument: on the host,
+ * -1, nothing written, the reason in mmdeer_last_error().
+ *
  * out = x + LayerNorm(y) row by row (ResidualBlock, complete_project.py:60-73); x == NULL: plain LayerNorm (the
  * Linear-ReLU-LayerNorm stems, :84-88, 315-333).  N is 256 or 512; eps 1e-5, biased variance. */
 int mmdeer_stackb_residual_ln(const void* y, int ld_y, const void* x, int ld_x, const float* gamma, const float* beta,
@@ -806,8 +813,9 @@ int mmdeer_stackb_attn_mix_bwd(const mmdeer_stackb_attn_train_args* a);
 int mmdeer_stackb_gate_mix_bwd(const void* dout, int ld_do, const void* gate_logits, int ld_g, const void* tri, int ld_t, const void* av,
                                int ld_av, void* dg, int ld_dg, void* dtri, int ld_dt, void* dav, int ld_dav, int B, int N, int act_f32,
                                void* stream);
-/* g4: fp32 [4][B][3] gradients wrt (mu, nu, alpha, beta); dev: act [B][ld_dev >= 24], dev[b][8 d + k] = gradient wrt
- * head d's raw output k (k < 4), columns 8 d + 4 .. 8 d + 7 written as zeros */
+/* g4: fp32 [4][B][3] gradients wrt (mu, nu, alpha, beta); dev: act [B][ld_dev], ld_dev >= 24 and a multiple of 8 (whole
+ * 8-column blocks: the k-contiguous operand of the weight-gradient GEMM), dev[b][8 d + k] = gradient wrt head d's raw
+ * output k (k < 4), columns 8 d + 4 .. 8 d + 7 written as zeros */
 int mmdeer_stackb_head_bwd(const float* ev, int ld_ev, const float* g4, void* dev, int ld_dev, int B, int act_f32, void* stream);
 /* out = (x + y) * (mask > 0 ? scale : 0) on [M][N] activation views (y, mask optional): gradient joins, residual sums,
  * ReLU / dropout masks that no GEMM epilogue can carry */

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 namespace mmdeer {
 
 // ---------------------------------------------------------------- storage dtypes
@@ -158,6 +160,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// a x + b y with its rounding points fixed: b y is rounded, then one fused multiply-add.  Left as `a * x + b * y` the
+// compiler is free to fuse either product, and it does not choose alike in every kernel; two kernels that must store the same
+// bits (the eval and the training form of one operator) spell the sum this way.
+__device__ __forceinline__ float mad2(float a, float x, float b, float y) { return fmaf(a, x, b * y); }
+__device__ __forceinline__ f32x4 mad2(float a, f32x4 x, float b, f32x4 y) {
+  return f32x4{mad2(a, x.x, b, y.x), mad2(a, x.y, b, y.y), mad2(a, x.z, b, y.z), mad2(a, x.w, b, y.w)};
+}
+
 // ---------------------------------------------------------------- error plumbing
 void set_error(const char* fmt, ...);
 #define MMDEER_CHECK(cond, ...)            \
@@ -191,5 +201,11 @@ void set_error(const char* fmt, ...);
 inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 inline bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// 4 activation elements: the unit of the row operators' vector accesses (16 bytes in fp32, 8 in bf16)
+inline bool al_act4(int act_f32, std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!(act_f32 ? al16(p) : al8(p))) return false;
+  return true;
+}
 
 }  // namespace mmdeer

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void softmax_mix_bwd_kernel(const MixArgs a) {
   for (int s = 0; s < MIX_MAX_S; ++s) dot += w[s] * dw[s];
   float ds[MIX_MAX_S];
 #pragma unroll
-  for (int s = 0; s < MIX_MAX_S; ++s) ds[s] = w[s] * (dw[s] - dot);     // zero beyond S (w = 0)
+  for (int s = 0; s < MIX_MAX_S; ++s) ds[s] = s < a.S ? w[s] * (dw[s] - dot) : 0.f;   // +0 beyond S whatever dot is (0 * x is -0 or a NaN)
   if (lane == 0) {
     st4<F32>(a.dlogits8, 8ll * b, f32x4{ds[0], ds[1], ds[2], ds[3]});
     st4<F32>(a.dlogits8, 8ll * b + 4, f32x4{ds[4], ds[5], ds[6], ds[7]});
@@ -171,6 +171,8 @@ int check_mix(const mmdeer_softmax_mix_args* p, bool bwd) {
   MMDEER_CHECK((p->w_att && p->b_att) || (p->logits && p->ld_logits >= p->S), "softmax_mix: needs w_att + b_att or logits");
   if (!bwd) MMDEER_CHECK(p->out && p->ld_out >= p->D && p->ld_out % 4 == 0, "softmax_mix_fwd: bad out");
   else MMDEER_CHECK(p->dout && p->dP && p->dlogits8 && p->ld_dout >= p->D && p->ld_dout % 4 == 0, "softmax_mix_bwd: bad dout / dP / dlogits8");
+  MMDEER_CHECK(al_act4(p->act_f32, {p->P, bwd ? p->dout : p->out, bwd ? p->dP : nullptr, bwd ? p->dlogits8 : nullptr}) && al16(p->weights8),
+               "softmax_mix: misaligned pointer (activation rows start on 4 elements, weights8 on 16 bytes)");
   return 0;
 }
 MixArgs to_mix(const mmdeer_softmax_mix_args* p) {
@@ -210,6 +212,7 @@ int mmdeer_outer_fwd(const void* x1, int ld1, const void* x2, int ld2, void* z, 
   MMDEER_CHECK(B >= 0 && I >= 1 && J >= 4 && J % 4 == 0, "outer_fwd: bad shape B=%d I=%d J=%d", B, I, J);
   if (B == 0) return 0;
   MMDEER_CHECK(x1 && x2 && z && ld1 >= I && ld2 >= J && ld2 % 4 == 0, "outer_fwd: bad pointer or leading dimension");
+  MMDEER_CHECK(al_act4(act_f32, {x2, z}), "outer_fwd: misaligned pointer (x2 and z rows start on 4 elements)");
   const unsigned grid = grid_for_((long long)B * I * (J / 4));
   MMDEER_LAUNCH_ACT(outer_fwd_kernel, act_f32, dim3(grid), dim3(256), (hipStream_t)stream, x1, ld1, x2, ld2, z, I, J, B);
   return 0;
@@ -221,6 +224,7 @@ int mmdeer_outer_bwd(const void* dz, const void* x1, int ld1, const void* x2, in
   if (B == 0) return 0;
   MMDEER_CHECK(dz && x1 && x2 && dx1 && dx2 && ld1 >= I && ldd1 >= I && ld2 >= J && ldd2 >= J && ld2 % 4 == 0 && ldd2 % 4 == 0,
                "outer_bwd: bad pointer or leading dimension");
+  MMDEER_CHECK(al_act4(act_f32, {dz, x2, dx2}), "outer_bwd: misaligned pointer (dz, x2 and dx2 rows start on 4 elements)");
   MMDEER_LAUNCH_ACT(outer_bwd_kernel, act_f32, dim3(B), dim3(256), (hipStream_t)stream, dz, x1, ld1, x2, ld2, dx1, ldd1, dx2, ldd2, I, J);
   return 0;
 }

@@ -127,13 +127,13 @@ __global__ __launch_bounds__(256) void attn_mix_kernel(const AttnMix a) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float* w = a.w1u + (long long)(col + j) * a.ld_w1u;
-    h[j] = fmaxf(h[j] + u[0] * w[0] + u[1] * w[1] + u[2] * w[2], 0.f);
+    h[j] = fmaxf(fmaf(u[2], w[2], fmaf(u[1], w[1], fmaf(u[0], w[0], h[j]))), 0.f);   // mad2 (common.h): the eval and the training kernel round alike
   }
   float lg[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const f32x4 w = *reinterpret_cast<const f32x4*>(a.w2 + k * 256 + col);
-    lg[k] = wave_sum((h[0] * w.x + h[1] * w.y) + (h[2] * w.z + h[3] * w.w)) + a.b2[k];
+    lg[k] = wave_sum(mad2(h[0], w.x, h[1], w.y) + mad2(h[2], w.z, h[3], w.w)) + a.b2[k];
   }
   const float mx = fmaxf(lg[0], fmaxf(lg[1], lg[2]));
   const float e0 = expf(lg[0] - mx), e1 = expf(lg[1] - mx), e2 = expf(lg[2] - mx);
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void attn_mix_kernel(const AttnMix a) {
   for (int m = 0; m < 3; ++m) {
     const f32x4 s = ld4<F32>(a.self_, (long long)b * 768 + m * 256 + col);
     const f32x4 c = ld4<F32>(a.cross, (long long)b * 768 + m * 256 + col);
-    const f32x4 o = w[m] * s + (1.f - u[m]) * c;                                   // complete_project.py:283-294
+    const f32x4 o = mad2(w[m], s, 1.f - u[m], c);                                  // complete_project.py:283-294
     if (m < 2) st4<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
     else st4<F32>(a.out_text, (long long)b * a.ld_text + col, o);
   }
@@ -448,6 +448,7 @@ int mmdeer_stackb_residual_ln(const void* y, int ld_y, const void* x, int ld_x, 
   MMDEER_CHECK(y && gamma && beta && out, "stackb_residual_ln: NULL pointer");
   MMDEER_CHECK(ld_y >= N && ld_out >= N && ld_y % 4 == 0 && ld_out % 4 == 0 && (!x || (ld_x >= N && ld_x % 4 == 0)),
                "stackb_residual_ln: leading dimensions must be >= N and multiples of 4");
+  MMDEER_CHECK(al_act4(act_f32, {y, x, out}), "stackb_residual_ln: misaligned pointer (y, x, out rows start on 4 elements)");
   return launch_residual_ln(y, ld_y, x, ld_x, gamma, beta, out, ld_out, M, N, M, 0, act_f32, (hipStream_t)stream);
 }
 
@@ -459,6 +460,8 @@ int mmdeer_stackb_attn_mix(const mmdeer_stackb_attn_args* p) {
                p->out_av && p->out_text && p->weights && p->uncertainties, "stackb_attn_mix: NULL pointer");
   MMDEER_CHECK(p->ld_w1_unc >= 3 && p->ld_av >= 512 && p->ld_av % 4 == 0 && p->ld_text >= 256 && p->ld_text % 4 == 0,
                "stackb_attn_mix: bad leading dimension (w1 %d, av %d, text %d)", p->ld_w1_unc, p->ld_av, p->ld_text);
+  MMDEER_CHECK(al_act4(p->act_f32, {p->h2, p->pre, p->self_out, p->cross_out, p->out_av, p->out_text}),
+               "stackb_attn_mix: misaligned pointer (activation rows start on 4 elements)");
   AttnMix a;
   a.h2 = p->h2; a.pre = p->pre; a.self_ = p->self_out; a.cross = p->cross_out;
   a.w3 = p->est_w3; a.b3 = p->est_b3; a.w1u = p->wn_w1_unc; a.w2 = p->wn_w2; a.b2 = p->wn_b2;
@@ -474,6 +477,8 @@ int mmdeer_stackb_gate_mix(const void* gate_logits, int ld_g, const void* tri, i
   MMDEER_CHECK(gate_logits && tri && av && out, "stackb_gate_mix: NULL pointer");
   MMDEER_CHECK(ld_g >= N && ld_t >= N && ld_av >= N && ld_out >= N && !(ld_g % 4) && !(ld_t % 4) && !(ld_av % 4) && !(ld_out % 4),
                "stackb_gate_mix: leading dimensions must be >= N and multiples of 4");
+  MMDEER_CHECK(al_act4(act_f32, {gate_logits, tri, av, out}) && al16(out32),
+               "stackb_gate_mix: misaligned pointer (activation rows start on 4 elements, out32 on 16 bytes)");
   return launch_gate_mix(gate_logits, ld_g, tri, ld_t, av, ld_av, out, ld_out, out32, B, N, act_f32, (hipStream_t)stream);
 }
 
@@ -483,6 +488,7 @@ int mmdeer_stackb_head(const float* ev, int ld_ev, const float* temperature, con
   if (B == 0) return 0;
   MMDEER_CHECK(ev && temperature && w1 && b1 && w2 && b2 && w3 && b3 && out, "stackb_head: NULL pointer");
   MMDEER_CHECK(ld_ev >= 12 && ld_ev % 4 == 0, "stackb_head: ld_ev=%d must be >= 12 and a multiple of 4", ld_ev);
+  MMDEER_CHECK(al16(ev), "stackb_head: misaligned pointer (ev rows start on 16 bytes)");
   return launch_head(ev, ld_ev, Calib{temperature, w1, b1, w2, b2, w3, b3}, out, B, (hipStream_t)stream);
 }
 

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float* w = a.wn_w1_unc + (long long)(col + j) * a.ld_w1_unc;
-    h[j] = fmaxf(h[j] + u[0] * w[0] + u[1] * w[1] + u[2] * w[2], 0.f);
+    h[j] = fmaxf(fmaf(u[2], w[2], fmaf(u[1], w[1], fmaf(u[0], w[0], h[j]))), 0.f);   // mad2 (common.h): the eval and the training kernel round alike
     if (drop_on) h[j] = drop_rand1(key, (unsigned)b, (unsigned)(col + j)) < dc.thresh ? h[j] * dc.scale : 0.f;   // weight_network.2
   }
   tst4<F32>(a.r, (long long)b * 256 + col, f32x4{h[0], h[1], h[2], h[3]});
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const f32x4 w = *reinterpret_cast<const f32x4*>(a.wn_w2 + k * 256 + col);
-    lg[k] = wave_sum((h[0] * w.x + h[1] * w.y) + (h[2] * w.z + h[3] * w.w)) + a.wn_b2[k];
+    lg[k] = wave_sum(mad2(h[0], w.x, h[1], w.y) + mad2(h[2], w.z, h[3], w.w)) + a.wn_b2[k];
   }
   const float mx = fmaxf(lg[0], fmaxf(lg[1], lg[2]));
   const float e0 = expf(lg[0] - mx), e1 = expf(lg[1] - mx), e2 = expf(lg[2] - mx);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
   for (int m = 0; m < 3; ++m) {
     const f32x4 s = tld4<F32>(a.self_out, (long long)b * 768 + m * 256 + col);
     const f32x4 c = tld4<F32>(a.cross_out, (long long)b * 768 + m * 256 + col);
-    const f32x4 o = w[m] * s + (1.f - u[m]) * c;
+    const f32x4 o = mad2(w[m], s, 1.f - u[m], c);
     if (m < 2) tst4<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
     else tst4<F32>(a.out_text, (long long)b * a.ld_text + col, o);
   }
@@ -217,6 +217,11 @@ int check_attn(const mmdeer_stackb_attn_train_args* p, bool bwd) {
   if (!bwd) MMDEER_CHECK(p->pre && p->out_av && p->out_text, "stackb_attn_mix_train_fwd: NULL pointer");
   else MMDEER_CHECK(p->d_av && p->d_text && p->d_self && p->d_cross && p->d_pre && p->d_logits8 && p->d_z8 && p->d_h2, "stackb_attn_mix_bwd: NULL pointer");
   MMDEER_CHECK(p->ld_dcross == 0 || (p->ld_dcross >= 256 && p->ld_dcross % 4 == 0), "stackb_attn_mix: ld_dcross %d", p->ld_dcross);
+  MMDEER_CHECK(al_act4(p->act_f32, {p->h2, p->self_out, p->cross_out, p->r}) && al16(p->weights4) && al16(p->unc4),
+               "stackb_attn_mix_train: misaligned pointer (activation rows start on 4 elements, weights4 / unc4 on 16 bytes)");
+  if (!bwd) MMDEER_CHECK(al_act4(p->act_f32, {p->pre, p->out_av, p->out_text}), "stackb_attn_mix_train_fwd: misaligned pointer (pre, out_av, out_text)");
+  else MMDEER_CHECK(al_act4(p->act_f32, {p->unc8, p->d_av, p->d_text, p->d_self, p->d_cross, p->d_pre, p->d_logits8, p->d_z8, p->d_h2}),
+                    "stackb_attn_mix_bwd: misaligned pointer (gradient rows and unc8 start on 4 elements)");
   return 0;
 }
 
@@ -258,6 +263,7 @@ int mmdeer_stackb_gate_mix_bwd(const void* dout, int ld_do, const void* gate_log
   MMDEER_CHECK(dout && gate_logits && tri && av && dg && dtri && dav, "stackb_gate_mix_bwd: NULL pointer");
   const int lds[7] = {ld_do, ld_g, ld_t, ld_av, ld_dg, ld_dt, ld_dav};
   for (int ld : lds) MMDEER_CHECK(ld >= N && ld % 4 == 0, "stackb_gate_mix_bwd: leading dimensions must be >= N and multiples of 4");
+  MMDEER_CHECK(al_act4(act_f32, {dout, gate_logits, tri, av, dg, dtri, dav}), "stackb_gate_mix_bwd: misaligned pointer (rows start on 4 elements)");
   const unsigned grid = grid_rows((long long)B * (N / 4));
   if (act_f32) hipLaunchKernelGGL(gate_mix_bwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, ld_do, gate_logits, ld_g, tri, ld_t, av, ld_av, dg, ld_dg, dtri, ld_dt, dav, ld_dav, B, N);
   else hipLaunchKernelGGL(gate_mix_bwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, ld_do, gate_logits, ld_g, tri, ld_t, av, ld_av, dg, ld_dg, dtri, ld_dt, dav, ld_dav, B, N);
@@ -268,7 +274,10 @@ int mmdeer_stackb_gate_mix_bwd(const void* dout, int ld_do, const void* gate_log
 int mmdeer_stackb_head_bwd(const float* ev, int ld_ev, const float* g4, void* dev, int ld_dev, int B, int act_f32, void* stream) {
   MMDEER_CHECK(B >= 0, "stackb_head_bwd: batch must be >= 0 (got %d)", B);
   if (B == 0) return 0;
-  MMDEER_CHECK(ev && g4 && dev && ld_ev >= 12 && ld_dev >= 24 && ld_ev % 4 == 0 && ld_dev % 8 == 0, "stackb_head_bwd: bad argument");
+  MMDEER_CHECK(ev && g4 && dev, "stackb_head_bwd: NULL pointer");
+  MMDEER_CHECK(ld_ev >= 12 && ld_ev % 4 == 0, "stackb_head_bwd: ld_ev=%d must be >= 12 and a multiple of 4", ld_ev);
+  MMDEER_CHECK(ld_dev >= 24 && ld_dev % 8 == 0, "stackb_head_bwd: ld_dev=%d must be >= 24 and a multiple of 8", ld_dev);
+  MMDEER_CHECK(al16(ev) && al_act4(act_f32, {dev}), "stackb_head_bwd: misaligned pointer (ev rows start on 16 bytes, dev rows on 4 elements)");
   const dim3 grid((unsigned)((3ll * B + 255) / 256));
   if (act_f32) hipLaunchKernelGGL(head_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ev, ld_ev, g4, dev, ld_dev, B);
   else hipLaunchKernelGGL(head_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ev, ld_ev, g4, dev, ld_dev, B);
@@ -282,6 +291,7 @@ int mmdeer_add_masked(void* out, int ld_out, const void* x, int ld_x, const void
   if (M == 0) return 0;
   MMDEER_CHECK(out && x && ld_out >= N && ld_x >= N && ld_out % 4 == 0 && ld_x % 4 == 0 && (!y || (ld_y >= N && ld_y % 4 == 0)) &&
                (!mask || (ld_mask >= N && ld_mask % 4 == 0)), "add_masked: bad pointer or leading dimension");
+  MMDEER_CHECK(al_act4(act_f32, {out, x, y, mask}), "add_masked: misaligned pointer (rows start on 4 elements)");
   const unsigned grid = grid_rows((long long)M * (N / 4));
   if (act_f32) hipLaunchKernelGGL(add_masked_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, ld_out, x, ld_x, y, ld_y, mask, ld_mask, scale, M, N);
   else hipLaunchKernelGGL(add_masked_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, ld_out, x, ld_x, y, ld_y, mask, ld_mask, scale, M, N);
