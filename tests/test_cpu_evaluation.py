@@ -248,4 +248,4 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
     assert cal(nb=33) != 0 and "n_bins <= 32" in err()
     assert cal(nb=0) != 0
     assert lib.mmdeer_calibration_bins_scratch(3) == 48 and lib.mmdeer_calibration_bins_scratch(4) == 0
-    assert lib.mmdeer_abi_version() == 15
+    assert lib.mmdeer_abi_version() == _lib.ABI_VERSION

@@ -33,7 +33,7 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/mmdeer.h but not exported"
     bound = {n for n, _, _ in _lib.SYMBOLS}
     assert bound == set(declared), (bound ^ set(declared))
-    assert lib.mmdeer_abi_version() == 15
+    assert lib.mmdeer_abi_version() == _lib.ABI_VERSION == header_abi_version()
     assert b"gfx950" in lib.mmdeer_version()
 
 
@@ -46,6 +46,126 @@ def test_ctypes_struct_layouts_match_the_library():
     for name, cls in _lib.STRUCTS.items():
         assert lib.mmdeer_sizeof(name.encode()) == C.sizeof(cls), name
     assert lib.mmdeer_sizeof(b"no_such_struct") == -1
+
+
+def test_derived_struct_layouts_match_the_compiler(tmp_path):
+    """Size of every struct and offset, size and kind (floating point, signed or unsigned integer, pointer, struct) of every
+    field, as ctypes lays the derived classes out, asserted by the compiler that builds the library against include/mmdeer.h
+    itself: two same-sized fields in the wrong order show in their offsets, an int32_t bound as a float in its kind."""
+    import ctypes as C
+    import subprocess
+
+    def kind(t):
+        while issubclass(t, C.Array):
+            t = t._type_
+        if issubclass(t, C.Structure):
+            return "std::is_class<T>::value"
+        if t in (C.c_float, C.c_double):
+            return "std::is_floating_point<T>::value"
+        if t in (C.c_int32, C.c_longlong, C.c_int64):
+            return "std::is_integral<T>::value && std::is_signed<T>::value"
+        if t in (C.c_uint64, C.c_size_t):
+            return "std::is_integral<T>::value && std::is_unsigned<T>::value"
+        assert t is C.c_void_p or issubclass(t, C._Pointer), t
+        return "std::is_pointer<T>::value"
+
+    lines = ["#include <stddef.h>", "#include <type_traits>", '#include "mmdeer.h"',
+             "template <class F> using elem = typename std::remove_all_extents<F>::type;"]
+    for cname, cls in _lib._CLASSES.items():
+        lines.append(f'static_assert(sizeof({cname}) == {C.sizeof(cls)}, "sizeof {cname}");')
+        for field, ftype in cls._fields_:
+            d = getattr(cls, field)
+            lines.append(f'namespace {cname}_{field} {{ using T = elem<decltype({cname}::{field})>; '
+                         f'static_assert({kind(ftype)}, "kind of {cname}.{field}"); }}')
+            lines.append(f'static_assert(offsetof({cname}, {field}) == {d.offset}, "offsetof {cname}.{field}");')
+            lines.append(f'static_assert(sizeof((({cname}*)0)->{field}) == {d.size}, "sizeof {cname}.{field}");')
+    assert len(_lib._CLASSES) == 20 and len(lines) > 3 * 441
+    tu = tmp_path / "layout.cpp"
+    tu.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([build._hipcc(), "-x", "c++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(tu)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+@pytest.mark.parametrize("extra,named", [
+    ("typedef struct mmdeer_bad_args { int32_t n; mmdeer_widget w; } mmdeer_bad_args;", "mmdeer_widget"),
+    ("int mmdeer_bad_call(const void* x, uint16_t flags, void* stream);", "uint16_t"),
+    ("typedef int (*mmdeer_callback)(void* user);", "mmdeer_callback"),
+    ("typedef int32_t mmdeer_handle;", "mmdeer_handle"),
+    ("typedef struct mmdeer_bad_args { int32_t n : 3; } mmdeer_bad_args;", "n : 3"),
+    ("#define MMDEER_BAD_SIZE (3 + 4)", "3 + 4"),
+    ("#define MMDEER_ROUND_UP(x) (((x) + 3) / 4 * 4)", "MMDEER_ROUND_UP"),
+    ("#define OTHER_LIMIT 7", "OTHER_LIMIT"),
+    ("#if MMDEER_ABI_VERSION > 14\nint mmdeer_either(void);\n#else\nlong long mmdeer_either(void);\n#endif", "#if MMDEER_ABI_VERSION"),
+], ids=["struct_base_type", "parameter_type", "typedef_function_pointer", "typedef_scalar", "bit_field", "define_expression",
+        "function_like_macro", "define_without_prefix", "conditional_branch"])
+def test_header_parser_refuses_what_it_cannot_account_for(extra, named):
+    from mmdeer import _header
+    text = _header.read()
+    end = text.rindex("#ifdef __cplusplus")                     # inside the extern "C" block, where declarations live
+    _header.parse(text, _lib._NAMES, _lib._TYPED_POINTERS)      # the header itself parses
+    with pytest.raises(_header.HeaderError) as e:
+        _header.parse(text[:end] + extra + "\n" + text[end:], dict(_lib._NAMES, mmdeer_bad_args="BadArgs"), _lib._TYPED_POINTERS)
+    assert named in str(e.value)
+
+
+def test_header_parser_maps_a_void_return_to_none():
+    from mmdeer import _header
+    text = _header.read()
+    end = text.rindex("#ifdef __cplusplus")
+    symbols = _header.parse(text[:end] + "void mmdeer_reset(void);\n" + text[end:], _lib._NAMES, _lib._TYPED_POINTERS)[2]
+    assert symbols[-1] == ("mmdeer_reset", None, [])
+
+
+def header_declarations():
+    """(struct names, {function: parameter count}, {MMDEER_ constant: text}) by regular expressions of this test's own."""
+    src = open(os.path.join(ROOT, "include", "mmdeer.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    structs = re.findall(r"typedef\s+struct\s*\w*\s*\{[^}]*\}\s*(\w+)\s*;", src)
+    protos = {n: 0 if p.strip() == "void" else p.count(",") + 1 for n, p in re.findall(r"\b(mmdeer_\w+)\s*\(([^)]*)\)\s*;", src)}
+    defines = dict(re.findall(r"#define\s+MMDEER_(\w+)[ \t]+(\S[^\n]*?)\s*$", src, flags=re.M))
+    return structs, protos, defines
+
+
+def header_abi_version():
+    return int(header_declarations()[2]["ABI_VERSION"])
+
+
+def test_binding_covers_the_whole_header():
+    import ctypes as C
+    structs, protos, defines = header_declarations()
+    assert len(structs) == 20 and "mmdeer_loss_cfg" in structs and len(protos) == 108
+    assert set(_lib._CLASSES) == set(structs)
+    for cname, cls in _lib._CLASSES.items():                   # every struct has a class, under its name as an attribute of _lib
+        assert issubclass(cls, C.Structure) and getattr(_lib, cls.__name__) is cls and _lib._NAMES[cname] == cls.__name__
+    assert set(_lib.STRUCTS) == {s[len("mmdeer_"):] for s in structs} - {"loss_cfg"}
+    assert all(_lib.STRUCTS[s[len("mmdeer_"):]] is _lib._CLASSES[s] for s in structs if s != "mmdeer_loss_cfg")
+    assert {n: len(args) for n, _, args in _lib.SYMBOLS} == protos and len(_lib.SYMBOLS) == len(protos)
+    for (cname, field), elem in _lib._TYPED_POINTERS.items():  # every override names an existing pointer field
+        assert dict(_lib._CLASSES[cname]._fields_)[field] is C.POINTER(elem), (cname, field)
+    assert set(_lib.CONSTANTS) == set(defines)
+    assert _lib.CONSTANTS["CHAIN_MAX_SEGS"] == 12 == C.sizeof(_lib.ChainArgs().seg) // C.sizeof(_lib.ChainSeg)
+    assert (_lib.TEMPORAL_POOL_SCRATCH, _lib.TOKEN_POOL_SCRATCH, _lib.LOSS_OUT, _lib.UNC_TABLE, _lib.COMM_ID_BYTES) == \
+        (256 * 256, 1024 * 384, 20, 40, 128)
+    from mmdeer import _header
+    with pytest.raises(_header.HeaderError, match="does not exist"):     # ... and an override of a field the header does not have is refused
+        _header.parse(_header.read(), _lib._NAMES, {**_lib._TYPED_POINTERS, ("mmdeer_gemm_args", "nope"): C.c_float})
+    with pytest.raises(_header.HeaderError, match="does not match"):     # as is one whose element type is not the header's
+        _header.parse(_header.read(), _lib._NAMES, {**_lib._TYPED_POINTERS, ("mmdeer_adamw_args", "lr"): C.c_double})
+
+
+def test_gemm_args_defaults():
+    import ctypes as C
+    a = _lib.gemm_args()
+    assert isinstance(a, _lib.GemmArgs)
+    neutral = {"tile": -1, "drop_site": -1, "regen_site": -1, "mask_scale": 1.0}
+    for field, _ in _lib.GemmArgs._fields_:
+        assert getattr(a, field) == neutral.get(field, 0) or (field not in neutral and getattr(a, field) is None), field
+    b = _lib.gemm_args(A=4096, M=3, tile=2, mask_scale=0.5, drop_site=7, seed=2 ** 40, bias=None)
+    assert (b.A, b.M, b.tile, b.mask_scale, b.drop_site, b.seed, b.bias, b.regen_site, b.N) == (4096, 3, 2, 0.5, 7, 2 ** 40, None, -1, 0)
+    with pytest.raises(TypeError, match="no_such_field"):
+        _lib.gemm_args(M=3, no_such_field=1)
+    assert C.sizeof(a) == _lib.load().mmdeer_sizeof(b"gemm_args")
 
 
 def test_layer_chain_operator_validates_its_table_on_the_host():

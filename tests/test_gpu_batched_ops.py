@@ -110,17 +110,10 @@ def _gemm_args(table, offs, out, pools, f32):
     p32, pbf = pools
     args = []
     for (M, N, K, lda, ldw, ldc, a_off, w_off, a32, w32, bias), (c_off, b_off) in zip(table, offs):
-        a = _lib.GemmArgs()
-        a.A = (p32 if a32 else pbf)[a_off:].data_ptr()
-        a.W = (p32 if w32 else pbf)[w_off:].data_ptr()
-        a.C = out[c_off:].data_ptr()
-        a.bias_grad = out[b_off:].data_ptr() if b_off is not None else None
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = M, N, K, lda, ldw, ldc
-        a.a_f32, a.w_f32, a.c_f32, a.trans_a, a.trans_w = a32, w32, 1, 1, 1
-        a.compute_f32, a.tile = f32, -1
-        a.drop_site = a.regen_site = -1
-        a.mask_scale = 1.0
-        args.append(a)
+        args.append(_lib.gemm_args(
+            A=(p32 if a32 else pbf)[a_off:].data_ptr(), W=(p32 if w32 else pbf)[w_off:].data_ptr(), C=out[c_off:].data_ptr(),
+            bias_grad=out[b_off:].data_ptr() if b_off is not None else None, M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=ldc,
+            a_f32=a32, w_f32=w32, c_f32=1, trans_a=1, trans_w=1, compute_f32=f32))
     return args
 
 

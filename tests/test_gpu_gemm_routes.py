@@ -252,22 +252,15 @@ class Call:
             nk = -(-K // (32 if s["f32"] else 64))
             self.slab_n = min(s["splitk"], nk) * self.slice
             self.slab = _canary((min(s["splitk"], nk) + 1) * max(self.slice, M * self.ldc + M) + 64, 1)
-        a = _lib.GemmArgs()
-        a.A, a.W, a.C = self.A.ptr, self.W.ptr, self.cbuf[self.c_off:].data_ptr()
-        a.bias = self.biasbuf.data_ptr() if self.biasbuf is not None else None
-        a.bias_grad = self.bgbuf[4:].data_ptr() if self.bgbuf is not None else None
-        a.Y = self.Ybuf.data_ptr() if s["Y"] else None
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc, a.ldy = M, N, K, self.lda, self.ldw, self.ldc, self.ldy if s["Y"] else 0
-        a.a_f32, a.w_f32, a.c_f32, a.y_f32 = s["a32"], s["w32"], c32, s["y32"]
-        a.trans_a, a.trans_w, a.relu, a.accumulate = s["ta"], s["tw"], s["relu"], s["accumulate"]
-        a.compute_f32, a.tile = s["f32"], s["tile"]
-        a.drop_site, a.drop_shift, a.regen_site = s["drop_site"], s["drop_shift"], s["regen_site"]
-        a.dropout_p, a.mask_scale, a.seed, a.offset = s["p"], s["mask_scale"], s["seed"], s["offset"]
-        a.offset_dev = s["offset_dev"]
-        a.splitk = s["splitk"]
-        a.slab = self.slab.data_ptr() if self.slab is not None else None
-        a.stream = _stream()
-        self.args = a
+        self.args = _lib.gemm_args(
+            A=self.A.ptr, W=self.W.ptr, C=self.cbuf[self.c_off:].data_ptr(),
+            bias=self.biasbuf.data_ptr() if self.biasbuf is not None else None,
+            bias_grad=self.bgbuf[4:].data_ptr() if self.bgbuf is not None else None, Y=self.Ybuf.data_ptr() if s["Y"] else None,
+            M=M, N=N, K=K, lda=self.lda, ldw=self.ldw, ldc=self.ldc, ldy=self.ldy if s["Y"] else 0,
+            a_f32=s["a32"], w_f32=s["w32"], c_f32=c32, y_f32=s["y32"], trans_a=s["ta"], trans_w=s["tw"], relu=s["relu"],
+            accumulate=s["accumulate"], compute_f32=s["f32"], tile=s["tile"], drop_site=s["drop_site"], drop_shift=s["drop_shift"],
+            regen_site=s["regen_site"], dropout_p=s["p"], mask_scale=s["mask_scale"], seed=s["seed"], offset=s["offset"],
+            offset_dev=s["offset_dev"], splitk=s["splitk"], slab=self.slab.data_ptr() if self.slab is not None else None, stream=_stream())
 
     def cwin(self):
         M, N = self.s["M"], self.s["N"]

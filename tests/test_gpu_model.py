@@ -517,7 +517,7 @@ def test_two_call_backward_reads_nothing_stale_from_the_workspace(B, dtype):
         o = m._launch_forward(a, v, t, y, want_features=False)
         meta = o["_meta"]
         flat = torch.zeros_like(m.flat_grad())
-        loss = torch.empty(20, device=DEV)
+        loss = torch.empty(_lib.LOSS_OUT, device=DEV)
         m._launch_backward(meta, meta["targets"], loss_out=loss, flat=flat, want_views=False, phase=1)
         m._launch_backward(meta, meta["targets"], loss_out=loss, flat=flat, want_views=False, phase=2)
         torch.cuda.synchronize()
@@ -598,10 +598,10 @@ def test_two_phase_backward_equals_single_call():
     meta["offset"] = meta["offset"]            # same dropout step as the forward just run
     # re-run the reference with the SAME dropout step for a bitwise comparison
     flat0 = torch.zeros_like(ref)
-    loss0 = torch.empty(20, device=DEV)
+    loss0 = torch.empty(_lib.LOSS_OUT, device=DEV)
     m._launch_backward(meta, meta["targets"], loss_out=loss0, flat=flat0, want_views=False, phase=0)
     flat = torch.zeros_like(ref)
-    loss = torch.empty(20, device=DEV)
+    loss = torch.empty(_lib.LOSS_OUT, device=DEV)
     m._launch_backward(meta, meta["targets"], loss_out=loss, flat=flat, want_views=False, phase=1)
     torch.cuda.synchronize()
     assert torch.equal(flat[lo:], flat0[lo:])

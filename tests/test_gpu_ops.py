@@ -35,29 +35,17 @@ def run_gemm(A, W, M, N, K, *, bias=None, relu=0, trans_a=0, trans_w=0, compute_
     lib = _lib.load()
     c_dtype = c_dtype or (torch.float32 if compute_f32 else torch.bfloat16)
     Cm = torch.zeros(M, N, dtype=c_dtype, device=dev()) if C_init is None else C_init.clone()
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-    a.bias = _lib.ptr(bias)
-    a.bias_grad = _lib.ptr(bias_grad)
-    a.Y = _lib.ptr(Y)
-    a.M, a.N, a.K = M, N, K
-    a.lda = lda if lda is not None else A.shape[1]
-    a.ldw = ldw if ldw is not None else W.shape[1]
-    a.ldc = N
-    a.ldy = Y.shape[1] if Y is not None else 0
-    a.a_f32 = int(A.dtype == torch.float32)
-    a.w_f32 = int(W.dtype == torch.float32)
-    a.c_f32 = int(c_dtype == torch.float32)
-    a.y_f32 = int(Y is not None and Y.dtype == torch.float32)
-    a.trans_a, a.trans_w, a.relu, a.accumulate = trans_a, trans_w, relu, accumulate
-    a.compute_f32, a.tile = compute_f32, tile
-    a.drop_site, a.drop_shift, a.regen_site = drop_site, drop_shift, regen_site
-    a.dropout_p, a.mask_scale, a.seed, a.offset = p, mask_scale, seed, offset
+    a = _lib.gemm_args(
+        A=A.data_ptr(), W=W.data_ptr(), C=Cm.data_ptr(), bias=_lib.ptr(bias), bias_grad=_lib.ptr(bias_grad), Y=_lib.ptr(Y), M=M, N=N, K=K,
+        lda=lda if lda is not None else A.shape[1], ldw=ldw if ldw is not None else W.shape[1], ldc=N,
+        ldy=Y.shape[1] if Y is not None else 0, a_f32=int(A.dtype == torch.float32), w_f32=int(W.dtype == torch.float32),
+        c_f32=int(c_dtype == torch.float32), y_f32=int(Y is not None and Y.dtype == torch.float32), trans_a=trans_a, trans_w=trans_w,
+        relu=relu, accumulate=accumulate, compute_f32=compute_f32, tile=tile, drop_site=drop_site, drop_shift=drop_shift,
+        regen_site=regen_site, dropout_p=p, mask_scale=mask_scale, seed=seed, offset=offset, stream=stream())
     slab = None
     if splitk > 1:
         slab = torch.full((splitk * ((M * N + M + 3) // 4 * 4),), float("nan"), device=dev())
         a.splitk, a.slab = splitk, slab.data_ptr()
-    a.stream = stream()
     _lib.check(lib.mmdeer_gemm(C.byref(a)))
     torch.cuda.synchronize()
     return Cm
@@ -374,7 +362,7 @@ def test_nig_loss_vs_oracle(golden_dir):
         B = yt.shape[0]
         stats = torch.empty(lib.mmdeer_nig_stats_elems(B), device=dev())
         grads = torch.zeros(4, B, 3, device=dev())
-        loss_out = torch.empty(20, device=dev())
+        loss_out = torch.empty(_lib.LOSS_OUT, device=dev())
         bins = torch.empty(30, dtype=torch.int32, device=dev())
         from mmdeer.model import make_loss_cfg
         cfg = make_loss_cfg()

@@ -10,19 +10,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from mmdeer import _lib  # noqa: E402
+
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 bwd = "--bwd" in sys.argv
 B = int(sys.argv[sys.argv.index("--B") + 1]) if "--B" in sys.argv else 4096
 if "--B" in sys.argv:
     args.remove(str(B))
-vp, ci, cf, u64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64
-libs = []
-for path in args:
-    lib = C.CDLL(os.path.abspath(path))
-    lib.mmdeer_pack_qkv_headmajor.argtypes = [vp] * 3
-    lib.mmdeer_trimodal_fused_fwd.argtypes = [vp] * 8 + [ci, ci, cf, u64, u64, vp]
-    lib.mmdeer_trimodal_fused_bwd.argtypes = [vp] * 6 + [ci, ci, cf, u64, u64, vp]
-    libs.append((os.path.basename(path), lib))
+libs = [(os.path.basename(path), _lib.bind(C.CDLL(os.path.abspath(path)))) for path in args]
 dev = torch.device("cuda:0")
 x = torch.randn(2 * B, 512, device=dev).bfloat16()
 w = torch.randn(1536, 512, device=dev) * 0.05

@@ -26,7 +26,7 @@ bwd = len(sys.argv) > 2 and sys.argv[2] == "bwd"
 o = m._launch_forward(a, v, t, y, want_features=False)
 if bwd:
     meta = o["_meta"]
-    m._launch_backward(meta, meta["targets"], loss_out=torch.empty(20, device=dev), flat=torch.zeros_like(m.flat_grad()), want_views=False, phase=1)
+    m._launch_backward(meta, meta["targets"], loss_out=torch.empty(_lib.LOSS_OUT, device=dev), flat=torch.zeros_like(m.flat_grad()), want_views=False, phase=1)
 torch.cuda.synchronize()
 ws = m._workspace(B, torch.device(dev))
 off = lib.mmdeer_workspace_offset(B, 0, b"davin" if bwd else b"slab")

@@ -22,19 +22,12 @@ def run(tag, M, N, K, trans_a, trans_w, dt, tile, splitk=1):
     A = torch.randn((K, M) if trans_a else (M, K), device=dev).to(dt)
     W = torch.randn((K, N) if trans_w else (N, K), device=dev).to(dt)
     Cm = torch.empty(M, N, device=dev, dtype=torch.float32 if (trans_a or f32) else dt)
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-    a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw, a.ldc = A.shape[1], W.shape[1], N
-    a.a_f32 = a.w_f32 = int(f32)
-    a.c_f32 = int(Cm.dtype == torch.float32)
-    a.trans_a, a.trans_w, a.compute_f32, a.tile = trans_a, trans_w, int(f32), tile
-    a.drop_site = a.regen_site = -1
-    a.mask_scale = 1.0
+    a = _lib.gemm_args(A=A.data_ptr(), W=W.data_ptr(), C=Cm.data_ptr(), M=M, N=N, K=K, lda=A.shape[1], ldw=W.shape[1], ldc=N,
+                       a_f32=int(f32), w_f32=int(f32), c_f32=int(Cm.dtype == torch.float32), trans_a=trans_a, trans_w=trans_w,
+                       compute_f32=int(f32), tile=tile, stream=torch.cuda.current_stream().cuda_stream)
     if splitk > 1:
         slab = torch.empty(splitk * ((M * N + M + 3) // 4 * 4), device=dev)
         a.splitk, a.slab = splitk, slab.data_ptr()
-    a.stream = torch.cuda.current_stream().cuda_stream
     for _ in range(3):
         _lib.check(lib.mmdeer_gemm(C.byref(a)))
     torch.cuda.synchronize()

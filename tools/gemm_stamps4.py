@@ -9,10 +9,7 @@ import torch  # noqa: E402
 
 from mmdeer import _lib, build  # noqa: E402
 
-lib = C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so"))
-lib.mmdeer_gemm.restype = C.c_int
-lib.mmdeer_gemm.argtypes = [C.POINTER(_lib.GemmArgs)]
-lib.mmdeer_last_error.restype = C.c_char_p
+lib = _lib.bind(C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so")))
 dev = torch.device("cuda:0")
 
 
@@ -23,16 +20,8 @@ def run(tag, M, N, K, bias):
     b = torch.randn(N, device=dev) if bias else None
     Cm = torch.empty(M, N, device=dev, dtype=dt)
     st = torch.zeros(1024, dtype=torch.int64, device=dev)
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-    a.bias = b.data_ptr() if bias else None
-    a.M, a.N, a.K, a.lda, a.ldw, a.ldc = M, N, K, K, K, N
-    a.tile = 3
-    a.drop_site = -1
-    a.regen_site = -1
-    a.mask_scale = 1.0
-    a.debug = st.data_ptr()
-    a.stream = torch.cuda.current_stream().cuda_stream
+    a = _lib.gemm_args(A=A.data_ptr(), W=W.data_ptr(), C=Cm.data_ptr(), bias=b.data_ptr() if bias else None, M=M, N=N, K=K, lda=K, ldw=K,
+                       ldc=N, tile=3, debug=st.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
     for _ in range(3):
         assert lib.mmdeer_gemm(C.byref(a)) == 0, lib.mmdeer_last_error()
     torch.cuda.synchronize()

@@ -9,10 +9,7 @@ import torch  # noqa: E402
 
 from mmdeer import _lib, build, synth  # noqa: E402
 
-lib = C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so"))
-for name, res, args in _lib.SYMBOLS:
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = res, args
+lib = _lib.bind(C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so")), require_all=True)
 _lib._LIB = lib                                  # the model below runs on the diagnostic build
 from mmdeer.model import ModelConfig, MultimodalDEER  # noqa: E402
 

@@ -10,15 +10,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from mmdeer import build  # noqa: E402
+from mmdeer import _lib, build  # noqa: E402
 
-lib = C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so"))
-vp, ci, cf, u64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64
-lib.mmdeer_pack_qkv_headmajor.argtypes = [vp] * 3
-lib.mmdeer_trimodal_fused_fwd.argtypes = [vp] * 8 + [ci, ci, cf, u64, u64, vp]
-lib.mmdeer_trimodal_fused_bwd.argtypes = [vp] * 6 + [ci, ci, cf, u64, u64, vp]
-lib.mmdeer_debug_tf_stamps.argtypes = [vp]
-lib.mmdeer_last_error.restype = C.c_char_p
+lib = _lib.bind(C.CDLL(os.path.join(build.PKG_DIR, "libmmdeer_stamps.so")))
+lib.mmdeer_debug_tf_stamps.argtypes = [C.c_void_p]
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 mode = sys.argv[2] if len(sys.argv) > 2 else "fwd"

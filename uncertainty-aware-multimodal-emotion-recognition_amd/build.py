@@ -16,6 +16,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(PKG_DIR, "libmmdeer_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer.h")
 SOURCES = ["gemm_nt.hip", "gemm_nx.hip", "gemm_tt.hip", "gemm_glds.hip", "gemm_ln.hip", "chain.hip", "gemm_tt256.hip", "gemm_nt256.hip", "gemm.hip", "rowops.hip", "attention.hip", "tri_fused.hip", "nig.hip", "nig_tail.hip", "optim.hip", "side.hip", "evalstats.hip", "lstm_seq.hip", "token_pool.hip", "stackb.hip", "stackb_train.hip", "fusions.hip", "comm.hip", "options.hip", "stackc.hip", "api.hip"]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: leading scalar kernel arguments arrive in SGPRs at wave start (gemm_glds.hip)
@@ -32,7 +33,7 @@ def _hipcc() -> str:
 
 def _newest_dep_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))]
-    deps.append(os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer.h"))
+    deps.append(HEADER_PATH)
     return max(os.path.getmtime(d) for d in deps)
 
 

@@ -242,7 +242,7 @@ def calibration_bins(p: torch.Tensor, t: torch.Tensor, u: torch.Tensor, n_bins: 
 
 
 SPARSIFICATION_FRACTIONS = np.linspace(0.1, 1.0, 10)
-UNC_TABLE = 40                         # MMDEER_UNC_TABLE
+UNC_TABLE = _lib.UNC_TABLE
 UNC_LEVELS = (0.5, 0.95)               # np.median, np.percentile(., 95)
 
 

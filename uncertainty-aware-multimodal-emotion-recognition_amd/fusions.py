@@ -224,11 +224,8 @@ def _add32(ex: Exec, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 def _f32_gemm(ex: Exec, A, W, Cm, M, N, K):
     """Cm = A W^T with fp32 operands whatever the module's compute dtype (tiny bookkeeping products)."""
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-    a.M, a.N, a.K, a.lda, a.ldw, a.ldc = M, N, K, A.stride(0), W.stride(0), Cm.stride(0)
-    a.a_f32 = a.w_f32 = a.c_f32 = a.compute_f32 = 1
-    a.tile, a.drop_site, a.regen_site, a.mask_scale, a.stream = -1, -1, -1, 1.0, ex.s
+    a = _lib.gemm_args(A=A.data_ptr(), W=W.data_ptr(), C=Cm.data_ptr(), M=M, N=N, K=K, lda=A.stride(0), ldw=W.stride(0), ldc=Cm.stride(0),
+                       a_f32=1, w_f32=1, c_f32=1, compute_f32=1, stream=ex.s)
     _lib.check(ex.lib.mmdeer_gemm(C.byref(a)))
 
 

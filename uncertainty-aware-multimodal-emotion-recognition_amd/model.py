@@ -144,7 +144,7 @@ class _LossFn(torch.autograd.Function):
         y = targets.contiguous().float()
         stats = torch.empty(lib.mmdeer_nig_stats_elems(B), dtype=torch.float32, device=dev)
         grads = torch.empty(4, B, 3, dtype=torch.float32, device=dev)
-        loss_out = torch.empty(20, dtype=torch.float32, device=dev)
+        loss_out = torch.empty(_lib.LOSS_OUT, dtype=torch.float32, device=dev)
         bins = torch.empty(30, dtype=torch.int32, device=dev)
         _lib.check(lib.mmdeer_nig_loss(g.data_ptr(), n.data_ptr(), a.data_ptr(), b.data_ptr(), y.data_ptr(),
                                        stats.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
@@ -459,7 +459,7 @@ class MultimodalDEER(nn.Module):
                                  want_features=return_features, bump=_bump)
         meta = o["_meta"]
         dev = meta["ws"].device
-        loss_out = torch.empty(20, dtype=torch.float32, device=dev)
+        loss_out = torch.empty(_lib.LOSS_OUT, dtype=torch.float32, device=dev)
         bins = torch.empty(30, dtype=torch.int32, device=dev)
         # the fused path owns ONE persistent flat gradient buffer per device (zeroed once: the alignment gaps stay 0);
         # every step overwrites all live slices, and .grad of each live parameter is a view of it

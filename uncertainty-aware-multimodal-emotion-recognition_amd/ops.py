@@ -50,19 +50,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     if M == 0:
         return y
     lib = _lib.load()
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = xs.data_ptr(), ws.data_ptr(), y.data_ptr()
-    a.bias = _lib.ptr(bs)
-    a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw, a.ldc = K, K, y.stride(0)
     f32 = int(dt == torch.float32)
-    a.a_f32 = a.w_f32 = a.c_f32 = f32
-    a.compute_f32 = f32
-    a.relu = int(relu)
-    a.tile = -1
-    a.drop_site = a.regen_site = -1
-    a.mask_scale = 1.0
-    a.stream = _lib.current_stream()
+    a = _lib.gemm_args(A=xs.data_ptr(), W=ws.data_ptr(), C=y.data_ptr(), bias=_lib.ptr(bs), M=M, N=N, K=K, lda=K, ldw=K, ldc=y.stride(0),
+                       a_f32=f32, w_f32=f32, c_f32=f32, compute_f32=f32, relu=int(relu), stream=_lib.current_stream())
     _lib.check(lib.mmdeer_gemm(C.byref(a)))
     return y
 
@@ -86,19 +76,10 @@ def linear_into(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
         raise ValueError("linear_into: bias must be contiguous fp32")
     if M == 0:
         return out
-    a = _lib.GemmArgs()
-    a.A, a.W, a.C = x.data_ptr(), weight.data_ptr(), out.data_ptr()
-    a.bias = _lib.ptr(bias)
-    a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw, a.ldc = x.stride(0), weight.stride(0), out.stride(0)
     f32 = int(dt == torch.float32)
-    a.a_f32 = a.w_f32 = a.compute_f32 = f32
-    a.c_f32 = int(out.dtype == torch.float32)
-    a.relu = int(relu)
-    a.tile = -1
-    a.drop_site = a.regen_site = -1
-    a.mask_scale = 1.0
-    a.stream = _lib.current_stream()
+    a = _lib.gemm_args(A=x.data_ptr(), W=weight.data_ptr(), C=out.data_ptr(), bias=_lib.ptr(bias), M=M, N=N, K=K,
+                       lda=x.stride(0), ldw=weight.stride(0), ldc=out.stride(0), a_f32=f32, w_f32=f32, compute_f32=f32,
+                       c_f32=int(out.dtype == torch.float32), relu=int(relu), stream=_lib.current_stream())
     _lib.check(_lib.load().mmdeer_gemm(C.byref(a)))
     return out
 

@@ -40,16 +40,11 @@ class Exec:
              drop_site=-1, drop_shift=0, regen_site=-1, p=0.0, splitk=1):
         if M == 0 or N == 0:
             return Cm
-        a = _lib.GemmArgs()
-        a.A, a.W, a.C = A.data_ptr(), W.data_ptr(), Cm.data_ptr()
-        a.bias, a.bias_grad, a.Y = _lib.ptr(bias), _lib.ptr(bias_grad), _lib.ptr(Y)
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc, a.ldy = M, N, K, lda, ldw, ldc, ldy
-        a.a_f32, a.w_f32, a.c_f32 = int(A.dtype == torch.float32), int(W.dtype == torch.float32), int(Cm.dtype == torch.float32)
-        a.y_f32 = int(Y is not None and Y.dtype == torch.float32)
-        a.trans_a, a.trans_w, a.relu = ta, tw, relu
-        a.compute_f32, a.tile = self.f32, -1
-        a.drop_site, a.drop_shift, a.regen_site = drop_site, drop_shift, regen_site
-        a.mask_scale = mask_scale
+        a = _lib.gemm_args(
+            A=A.data_ptr(), W=W.data_ptr(), C=Cm.data_ptr(), bias=_lib.ptr(bias), bias_grad=_lib.ptr(bias_grad), Y=_lib.ptr(Y),
+            M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=ldc, ldy=ldy, a_f32=int(A.dtype == torch.float32), w_f32=int(W.dtype == torch.float32),
+            c_f32=int(Cm.dtype == torch.float32), y_f32=int(Y is not None and Y.dtype == torch.float32), trans_a=ta, trans_w=tw,
+            relu=relu, compute_f32=self.f32, drop_site=drop_site, drop_shift=drop_shift, regen_site=regen_site, mask_scale=mask_scale)
         if self.drop is not None:
             a.dropout_p = p
         set_drop(a, self.drop)
@@ -96,13 +91,9 @@ class Exec:
             dy, ldy_, x, ldx, M = d2, N, x2, K, M + 1
         if self.deferred is not None and gw.is_contiguous() and gw.stride(0) == K:
             # grouped form (mmdeer_gemm_batch): up to 16 weight-gradient problems per launch + one fold, as mmdeer_backward does
-            a = _lib.GemmArgs()
-            a.A, a.W, a.C, a.bias_grad = dy.data_ptr(), x.data_ptr(), gw.data_ptr(), _lib.ptr(gb)
-            a.M, a.N, a.K, a.lda, a.ldw, a.ldc = N, K, M, ldy_, ldx, K
-            a.a_f32, a.w_f32, a.c_f32 = int(dy.dtype == torch.float32), int(x.dtype == torch.float32), 1
-            a.trans_a, a.trans_w, a.compute_f32, a.tile = 1, 1, self.f32, -1
-            a.drop_site = a.regen_site = -1
-            a.mask_scale = 1.0
+            a = _lib.gemm_args(A=dy.data_ptr(), W=x.data_ptr(), C=gw.data_ptr(), bias_grad=_lib.ptr(gb), M=N, N=K, K=M, lda=ldy_, ldw=ldx,
+                               ldc=K, a_f32=int(dy.dtype == torch.float32), w_f32=int(x.dtype == torch.float32), c_f32=1,
+                               trans_a=1, trans_w=1, compute_f32=self.f32)
             self.deferred.append((a, (dy, x, gw, gb)))
             return gw
         # few output tiles, deep reduction over the batch: split it into K-slices (fp32 slabs, folded by the library in index order)

@@ -32,8 +32,8 @@ class RcclCommunicator:
     def __init__(self, rank: int, world: int, unique_id: bytes):
         import ctypes as C
         from . import _lib
-        if len(unique_id) != 128:
-            raise ValueError("unique_id must be the 128 bytes of mmdeer_comm_unique_id")
+        if len(unique_id) != _lib.COMM_ID_BYTES:
+            raise ValueError(f"unique_id must be the {_lib.COMM_ID_BYTES} bytes of mmdeer_comm_unique_id")
         self._lib = _lib.load()
         self.rank, self.world = rank, world
         handle = C.c_void_p()
@@ -44,7 +44,7 @@ class RcclCommunicator:
     def unique_id() -> bytes:
         import ctypes as C
         from . import _lib
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(_lib.COMM_ID_BYTES)
         _lib.check(_lib.load().mmdeer_comm_unique_id(buf))
         return buf.raw
 

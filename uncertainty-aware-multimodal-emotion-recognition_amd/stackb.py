@@ -459,7 +459,7 @@ class CompleteDEERModel(nn.Module):
         planes = T["planes"]
         lib = _lib.load()
         f32o = dict(dtype=torch.float32, device=dev)
-        g4, loss_out = torch.empty(4, B, 3, **f32o), torch.empty(20, **f32o)
+        g4, loss_out = torch.empty(4, B, 3, **f32o), torch.empty(_lib.LOSS_OUT, **f32o)
         bins = torch.empty(30, dtype=torch.int32, device=dev)
         stats = torch.empty(int(lib.mmdeer_nig_stats_elems(B)), **f32o)
         y = targets.detach().float().contiguous()
