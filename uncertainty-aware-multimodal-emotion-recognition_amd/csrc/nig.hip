@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void nig_loss_grad_kernel(const float* gamma, 
   const long long o = (long long)b * 3 + d;
   const Nig n{gamma[o], nu[o], alpha[o], beta[o]};
   const Terms t = loss_terms(n, targets[o]);
-  const f32x4 g = loss_grad(n, t, d, B, cfg, F);
+  const f32x4 g = loss_grad<true>(n, t, d, B, cfg, F);
   dgamma[o] = g.x; dnu[o] = g.y; dalpha[o] = g.z; dbeta[o] = g.w;
 }
 

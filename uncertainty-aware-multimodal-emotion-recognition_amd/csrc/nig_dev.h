@@ -234,7 +234,13 @@ __device__ __forceinline__ void write_loss(const Finals& F, float* loss_out, int
     for (int i = 0; i < 30; ++i) bin_counts[i] = F.counts[i / 10][i % 10];
 }
 
-// d loss / d (mu, nu, alpha, beta) of one (sample, dim)
+// d loss / d (mu, nu, alpha, beta) of one (sample, dim).
+// kAnyInput: the stand-alone operator (mmdeer_nig_loss) takes NIG parameters from anywhere.  alpha == 1.0f with a beta above 3.4e30
+// makes u = beta / 1e-8 inf (conf == 0: the sample is in no bin), its du_da -inf and the mean of u -- hence dcross -- inf; the
+// products below would then be 0 * inf.  There a sample outside every bin carries no ECE gradient, and without the cross term
+// (losses.py:308: weight > 0) nothing flows through the mean of u.  The head kernels form alpha and beta as softplus of a stored
+// evidence (u = inf would take an evidence of 3.4e30) and keep the plain products: their arithmetic is untouched.
+template <bool kAnyInput = false>
 __device__ __forceinline__ f32x4 loss_grad(const Nig& n, const Terms& t, int d, int B, const LossCfg& cfg, const Finals& F) {
 #pragma clang fp contract(off)   // one rounding per operation in every kernel that includes this file (see nig_dx)
   const float invN = 1.f / (float)B;
@@ -253,14 +259,24 @@ __device__ __forceinline__ f32x4 loss_grad(const Nig& n, const Terms& t, int d, 
                      + cfg.ece_w * sg * (-serr));
   // nu
   g.y = cd * invN * (-(0.5f / n.nu - ah * 0.5f * e2 / t.A) + cfg.reg_w * e2 * e2);
-  // alpha
-  g.z = cd * invN * (-(t.lb - digamma(n.alpha + kEps) - logf(t.A)) + cfg.kl_w * 2.f * (n.alpha - 1.f)
-                     + cfg.ece_w * sg * dconf_du * du_da)
-        + gu * du_da;
-  // beta
-  g.w = cd * invN * (-(n.alpha / (n.beta + kEps) - ah / t.A) + cfg.reg_w * 2.f * e2
-                     + cfg.kl_w * 0.2f * t.lb / (n.beta + kEps) + cfg.ece_w * sg * dconf_du * du_db)
-        + gu * du_db;
+  if constexpr (!kAnyInput) {
+    // alpha
+    g.z = cd * invN * (-(t.lb - digamma(n.alpha + kEps) - logf(t.A)) + cfg.kl_w * 2.f * (n.alpha - 1.f)
+                       + cfg.ece_w * sg * dconf_du * du_da)
+          + gu * du_da;
+    // beta
+    g.w = cd * invN * (-(n.alpha / (n.beta + kEps) - ah / t.A) + cfg.reg_w * 2.f * e2
+                       + cfg.kl_w * 0.2f * t.lb / (n.beta + kEps) + cfg.ece_w * sg * dconf_du * du_db)
+          + gu * du_db;
+  } else {
+    // the same sums with the two guards (for every other input the terms replaced are +-0 or equal: the same bits)
+    const bool in_bin = t.bin >= 0, cross_on = cfg.cross_w > 0.f;
+    const float ece_a = in_bin ? cfg.ece_w * sg * dconf_du * du_da : 0.f, ece_b = in_bin ? cfg.ece_w * sg * dconf_du * du_db : 0.f;
+    const float cross_a = cross_on ? gu * du_da : 0.f, cross_b = cross_on ? gu * du_db : 0.f;
+    g.z = cd * invN * (-(t.lb - digamma(n.alpha + kEps) - logf(t.A)) + cfg.kl_w * 2.f * (n.alpha - 1.f) + ece_a) + cross_a;
+    g.w = cd * invN * (-(n.alpha / (n.beta + kEps) - ah / t.A) + cfg.reg_w * 2.f * e2
+                       + cfg.kl_w * 0.2f * t.lb / (n.beta + kEps) + ece_b) + cross_b;
+  }
   return g;
 }
 

@@ -171,12 +171,15 @@ def make_loss_cfg(reg_weight=0.1, kl_weight=0.01, ece_weight=0.05, cross_dim_wei
     return cfg
 
 
-def loss_dict_from(loss_out: torch.Tensor, batch_size: int) -> Dict[str, torch.Tensor]:
-    """Reference key layout of MultiTaskDEERLoss.forward (losses.py:303-318)."""
+def loss_dict_from(loss_out: torch.Tensor, batch_size: int, ece_weight: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    """Reference key layout of MultiTaskDEERLoss.forward (losses.py:303-318).  ``ece_weight`` <= 0: the reference does not
+    evaluate the ECE then and reports 0 for ``<dim>_ece_loss`` (losses.py:118); the kernel always computes it."""
     d: Dict[str, torch.Tensor] = {}
     for i, dim in enumerate(DIM_NAMES):
         for j, k in enumerate(LOSS_KEYS):
             d[f"{dim}_{k}"] = loss_out[i * 5 + j]
+        if ece_weight is not None and not ece_weight > 0:
+            d[f"{dim}_ece_loss"] = torch.zeros((), dtype=loss_out.dtype, device=loss_out.device)
         d[f"{dim}_batch_size"] = batch_size
     d["cross_dim_loss"] = loss_out[15]
     d["total_loss"] = loss_out[16]
@@ -496,7 +499,7 @@ class MultimodalDEER(nn.Module):
                 if p.grad is not g:
                     p.grad = g
             self._grads_bound = True
-        d = loss_dict_from(loss_out, meta["B"])
+        d = loss_dict_from(loss_out, meta["B"], self.loss_cfg.ece_weight)
         d["ece_bin_counts"] = bins.view(3, 10)
         d["_outputs"] = o
         return d
@@ -642,7 +645,7 @@ def multitask_deer_loss(predictions: Dict[str, torch.Tensor], targets: torch.Ten
     if targets.dim() != 2 or targets.shape[1] != 3:
         raise ValueError("targets must be (B, 3)")
     loss_out, bins = _LossFn.apply(gamma, nu, alpha, beta, targets, cfg)
-    d = loss_dict_from(loss_out, gamma.shape[0])
+    d = loss_dict_from(loss_out, gamma.shape[0], cfg.ece_weight)
     d["ece_bin_counts"] = bins.view(3, 10)
     return d
 
