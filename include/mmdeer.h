@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MMDEER_ABI_VERSION 15
+#define MMDEER_ABI_VERSION 16
 
 /* ---- fixed geometry of the path (reference fusion.py:47-50, deer.py:201-202, configs/config.yaml:13-20).
  * RESTRICTION: mmdeer_forward / mmdeer_backward / mmdeer_adamw_step (the Stack C entry points) are compiled for exactly this
@@ -272,6 +272,13 @@ typedef struct mmdeer_gemm_args {
  * weight-gradient DMA kernel (tile 3 or 4, or tile 2 under option dw_tile = 2; both operands bf16, K % 32 == 0, a 16-byte aligned
  * fp32 C, no epilogue but bias_grad / accumulate), so such an A is accepted there and refused elsewhere. */
 int mmdeer_gemm(const mmdeer_gemm_args* a);
+/* Dry run of mmdeer_gemm: everything it does before its first launch (argument checks, split decision, tile, operand source modes,
+ * kernel route), touching no GPU and dereferencing no operand pointer.  Writes one line per launch the call would make into
+ * out[cap] (NUL-terminated, lines separated by '\n'; truncated to fit), "<kernel> <BM>x<BN>[ <variant>] a=<mode> b=<mode> tiles=<workgroups>":
+ * kernel nt_reg / nx_reg / tt_reg (register-staged), nt_glds (LDS-DMA, variant w4 / w8 = waves), nt256 (256-row forward), tt_dma
+ * (weight-gradient LDS-DMA, variant k1 / k2 = K halves per stage); mode f32 / v16 / v8 as mmdeer_gemm's comment lists them.  Returns the
+ * number of launches (M = 0: 0), or -1 with the message of mmdeer_last_error() exactly where mmdeer_gemm would refuse. */
+int mmdeer_gemm_route(const mmdeer_gemm_args* a, char* out, int cap);
 
 /* n weight-gradient problems (every one trans_a = trans_w = 1, fp32 C, no epilogue; the same compute dtype) as grouped
  * launches of up to 16 problems each + one deterministic fold of their split-K slabs per group -- the form in which

@@ -14,6 +14,8 @@ from mmdeer.model import CompleteDEERModel, ModelConfig, MultimodalDEER, loss_di
 from mmdeer.parallel import shard_rows
 from mmdeer.spec import gate_param_table, n_live_params, param_offsets, param_table
 
+from . import gemm_route_table as G
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -134,7 +136,7 @@ def header_abi_version():
 def test_binding_covers_the_whole_header():
     import ctypes as C
     structs, protos, defines = header_declarations()
-    assert len(structs) == 20 and "mmdeer_loss_cfg" in structs and len(protos) == 108
+    assert len(structs) == 20 and "mmdeer_loss_cfg" in structs and len(protos) == 109
     assert set(_lib._CLASSES) == set(structs)
     for cname, cls in _lib._CLASSES.items():                   # every struct has a class, under its name as an attribute of _lib
         assert issubclass(cls, C.Structure) and getattr(_lib, cls.__name__) is cls and _lib._NAMES[cname] == cls.__name__
@@ -166,6 +168,60 @@ def test_gemm_args_defaults():
     with pytest.raises(TypeError, match="no_such_field"):
         _lib.gemm_args(M=3, no_such_field=1)
     assert C.sizeof(a) == _lib.load().mmdeer_sizeof(b"gemm_args")
+
+
+def _route_args(s):
+    """The argument struct of a gemm_route_table spec over plausible, aligned buffer addresses: the dry run dereferences none."""
+    mb = 1 << 24
+    return G.Layout(s).args(s, A=1 * mb, W=2 * mb, C=3 * mb, bias=4 * mb, bias_grad=5 * mb, Y=6 * mb, slab=7 * mb)
+
+
+def _route_of(s):
+    rc, lines = G.dry_run(_route_args(s))
+    return rc, [G.without_tiles(x) for x in lines], _lib.load().mmdeer_last_error().decode()
+
+
+@pytest.mark.parametrize("route", sorted(G.ROUTES))
+def test_gemm_route_names_the_kernel_of_every_route(route):
+    """mmdeer_gemm_route (no GPU: everything mmdeer_gemm does before its first launch) answers, for every shape and epilogue of the
+    route under the route's own options, the one line the table states by hand; M = 0 is no launch."""
+    with _lib.options(**G.ROUTES[route].get("opts", {})):
+        for s, i, ename in G.route_cases(route):
+            assert _route_of(s)[:2] == (1, [G.route_line(route, i, ename)]), (route, s["M"], s["N"], s["K"], ename, _route_of(s))
+            assert _route_of(dict(s, M=0))[:2] == (0, []), (route, ename)
+    rc, lines = G.dry_run(_route_args(G.spec("glds_128x64_8w", 1031, 196, 64)))
+    assert (rc, lines) == (1, ["nt_glds 128x64 w8 a=v16 b=v16 tiles=36"])         # tiles= counts the workgroups: 9 x 4
+
+
+@pytest.mark.parametrize("plan", G.PLANS, ids=lambda d: "-".join(f"{k}{v}" for k, v in d.items()))
+def test_gemm_route_under_every_launch_plan(plan):
+    with _lib.options(**plan):
+        for route in G.PLAN_ROUTES:
+            for s, i, ename in G.plan_cases(route):
+                assert _route_of(s)[:2] == (1, [G.plan_route_line(plan, route, i, s)]), (plan, route, s["M"], s["N"], s["K"], ename, _route_of(s))
+
+
+def test_gemm_route_refuses_what_the_call_refuses():
+    import ctypes as C
+    for name in sorted(G.REFUSALS):
+        s, post, words = G.refusal_spec(name)
+        a = _route_args(s)
+        if post:
+            post(a)
+        out = C.create_string_buffer(64)
+        assert _lib.load().mmdeer_gemm_route(C.byref(a), out, len(out)) == -1, f"{name}: accepted"
+        assert words in _lib.load().mmdeer_last_error().decode(), (name, _lib.load().mmdeer_last_error())
+    for name, (route, kw) in sorted(G.UNSPLITTABLE.items()):      # a split request the fold cannot take: accepted, and runs unsplit
+        for sk in (3, 8):
+            s = G.spec(route, splitk=sk, bias_grad=1, **kw)
+            rc, lines = G.dry_run(_route_args(s))
+            assert rc == 1 and G.without_tiles(lines[0]) == G.route_line(route), (name, sk, lines)
+            assert lines == G.dry_run(_route_args(dict(s, splitk=1)))[1], (name, sk, lines)
+    assert _lib.load().mmdeer_gemm_route(None, None, 0) == -1 and b"NULL" in _lib.load().mmdeer_last_error()
+    a = _route_args(G.spec("nt_f32_t0", 64, 68, 64))
+    assert _lib.load().mmdeer_gemm_route(C.byref(a), None, 0) == 1               # the count alone
+    out = C.create_string_buffer(8)
+    assert _lib.load().mmdeer_gemm_route(C.byref(a), out, len(out)) == 1 and out.value == b"nt_reg "   # truncated, NUL-terminated
 
 
 def test_layer_chain_operator_validates_its_table_on_the_host():

@@ -40,7 +40,9 @@ def run(tag, M, N, K, trans_a, trans_w, dt, tile, splitk=1):
     us = e0.elapsed_time(e1) * 1e3 / ITER
     tf = 2.0 * M * N * K / us / 1e6
     tag = f"{tag} sk={splitk}"
-    print(f"{tag:28s} M={M:5d} N={N:5d} K={K:5d} ta={trans_a} tw={trans_w} {str(dt)[6:]:8s} tile={tile}: {us:8.1f} us  {tf:7.1f} TFLOP/s", flush=True)
+    route = C.create_string_buffer(128)
+    lib.mmdeer_gemm_route(C.byref(a), route, len(route))
+    print(f"{tag:28s} M={M:5d} N={N:5d} K={K:5d} ta={trans_a} tw={trans_w} {str(dt)[6:]:8s} tile={tile}: {us:8.1f} us  {tf:7.1f} TFLOP/s  [{route.value.decode()}]", flush=True)
 
 
 shapes = [

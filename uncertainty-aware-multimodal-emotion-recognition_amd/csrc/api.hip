@@ -74,11 +74,12 @@ bool batch_may_split(const mmdeer_gemm_args& q) {
   return q.ldc == q.N && (long long)q.M * q.N % 4 == 0 && ((uintptr_t)q.C % 16) == 0 &&
          (!q.bias_grad || (q.M % 4 == 0 && ((uintptr_t)q.bias_grad % 16) == 0));
 }
-}  // namespace
 
-int mmdeer_gemm(const mmdeer_gemm_args* a) {
+// Everything mmdeer_gemm does before its first launch, shared with the dry run mmdeer_gemm_route: the argument mapping, the split
+// decision, the tile and every check of the group launcher.  Touches no GPU and dereferences no operand pointer.
+int gemm_front(const mmdeer_gemm_args* a, GemmGroup& g, GemmTile& t, int& f32) {
   MMDEER_CHECK(a != nullptr, "args is NULL");
-  GemmGroup g{};
+  g = GemmGroup{};
   g.nprob = 1;
   GemmProblem& p = g.p[0];
   gemm_problem_defaults(p);
@@ -104,10 +105,20 @@ int mmdeer_gemm(const mmdeer_gemm_args* a) {
   }
   g.drop = make_drop(a->dropout_p, a->seed, a->offset, a->offset_dev);
   g.stamps = reinterpret_cast<unsigned long long*>(a->debug);
-  GemmTile t = (a->tile >= 0 && a->tile <= 4) ? (GemmTile)a->tile : pick_tile(g);
-  const int f32 = a->compute_f32 ? 1 : 0;
+  t = (a->tile >= 0 && a->tile <= 4) ? (GemmTile)a->tile : pick_tile(g);
+  f32 = a->compute_f32 ? 1 : 0;
   TRY(prepare_gemm_group(g, f32, t));   // every check before the first launch (prepare also clamps splitk to the K-tile count)
-  const int sk = g.p[0].splitk;
+  return 0;
+}
+}  // namespace
+
+int mmdeer_gemm(const mmdeer_gemm_args* a) {
+  GemmGroup g;
+  GemmTile t;
+  int f32;
+  TRY(gemm_front(a, g, t, f32));
+  const GemmProblem& p = g.p[0];
+  const int sk = p.splitk;
   TRY(launch_gemm_group(g, f32, t, (hipStream_t)a->stream));
   if (sk > 1) {   // fold the K-slices into C (and bias_grad); batch_may_split: dense C, M*N and M multiples of 4
     ReduceTable rt{};
@@ -121,6 +132,14 @@ int mmdeer_gemm(const mmdeer_gemm_args* a) {
     TRY(launch_reduce_partials(rt, (hipStream_t)a->stream));
   }
   return 0;
+}
+
+int mmdeer_gemm_route(const mmdeer_gemm_args* a, char* out, int cap) {
+  GemmGroup g;
+  GemmTile t;
+  int f32;
+  TRY(gemm_front(a, g, t, f32));
+  return describe_gemm_group(g, f32, t, out, cap);
 }
 
 namespace {
@@ -153,7 +172,7 @@ int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {
       long long wgs = 0, slab_tiles = 0;
       int longest = 0;
       for (int i = 0; i < n; ++i) {
-        const long long tiles = (long long)((a[i].M + 127) / 128) * ((a[i].N + 127) / 128);
+        const long long tiles = gemm_tiles(a[i].M, a[i].N, 128, 128);
         const int nk = gemm_ktiles(a[i].K, f32), sk = batch_problem_splitk(a[i], f32, -L), len = (nk + sk - 1) / sk;
         wgs += tiles * sk;
         if (sk > 1) slab_tiles += tiles * sk;
@@ -168,7 +187,7 @@ int batch_boost(const mmdeer_gemm_args* a, int n, int f32) {
   const int t = (!f32 && opt(OPT_DW_TILE) == 2) ? 128 : 256;
   long long wgs = 0;
   for (int i = 0; i < n; ++i)
-    wgs += (long long)((a[i].M + t - 1) / t) * ((a[i].N + t - 1) / t) * batch_problem_splitk(a[i], f32, 1);
+    wgs += gemm_tiles(a[i].M, a[i].N, t, t) * batch_problem_splitk(a[i], f32, 1);
   int boost = 1;
   while (boost < 4 && wgs * boost * 2 <= 256) boost *= 2;
   return boost;

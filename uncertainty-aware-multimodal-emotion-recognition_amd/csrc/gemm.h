@@ -58,11 +58,33 @@ struct GemmGroup {
 enum GemmTile { TILE_64x64 = 0, TILE_128x64 = 1, TILE_128x128 = 2, TILE_256x256 = 3, TILE_256x128 = 4 };   // 256x256: bf16 LDS-DMA kernels only; 256x128: bf16 weight gradients only
 
 // compute_f32 = 1: fp32 operands in LDS, v_mfma_f32_16x16x4_f32 (exact fp32); 0: bf16 operands, v_mfma_f32_16x16x32_bf16.
-// Enqueues on `stream`, never synchronises.  Returns 0 / -1 (message via mmdeer_last_error()).
-// The checks of launch_gemm_group and the source mode of every operand (a_mode / b_mode), without launching anything.
-// (launch_gemm_group also refuses a source-mode pair that no kernel instantiates, for every problem before its first launch.)
+// prepare_gemm_group: every argument check, the clamp of splitk and the source mode of every operand (a_mode / b_mode).
+// launch_gemm_group: prepare, then one launch per distinct (a_mode, b_mode) pair of the group -- a pair that no kernel instantiates
+// is refused for every problem before the first launch.  Enqueues on `stream`, never synchronises.  Returns 0 / -1 (message via
+// mmdeer_last_error()).  describe_gemm_group walks the group the same way and writes one line per launch into out[cap] instead of
+// launching ("<kernel> <BM>x<BN>[ <variant>] a=<mode> b=<mode> tiles=<total>", lines separated by '\n'); returns the launch count.
 int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile);
 int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile, hipStream_t stream);
+int describe_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile, char* out, int cap);
+
+// The kernel one launch runs: a pure function (gemm.hip: gemm_route) of a homogeneous sub-group (one (a_mode, b_mode) pair), the compute
+// dtype, the requested tile and the options.  `variant`: waves per workgroup of the LDS-DMA NT kernel (4 / 8; the ring depth follows from
+// tile and waves, gemm_glds.hip), KG of the weight-gradient DMA kernel (1 / 2), 0 for the others.
+enum GemmKernel { GEMM_NT_REG = 0, GEMM_NX_REG, GEMM_TT_REG, GEMM_NT_GLDS, GEMM_NT256, GEMM_TT_DMA, GEMM_KERNEL_COUNT };
+struct GemmRoute { GemmKernel kernel; int BM, BN, variant; };
+GemmRoute gemm_route(const GemmGroup& sub, int compute_f32, GemmTile tile);
+
+// One launcher per GemmKernel (gemm_nt / _nx / _tt / _glds / _nt256 / _tt256.hip), looked up by route.kernel in gemm.hip.  `total` =
+// workgroups; the caller has filled tiles_m / tiles_n / tile_start for (r.BM, r.BN) and guarantees what the kernel's predicate
+// (gemm.hip) states.
+typedef int GemmLauncher(const GemmGroup& g, int total, const GemmRoute& r, int compute_f32, hipStream_t s);
+GemmLauncher gemm_launch_nt_reg, gemm_launch_nx_reg, gemm_launch_tt_reg, gemm_launch_nt_glds, gemm_launch_nt256, gemm_launch_tt_dma;
+
+// The bf16-compute (A mode, B mode) pairs the register-staged kernels instantiate, per transposition (fp32 compute: (F32, F32) only).
+// gemm_modes_instantiated (gemm.hip) and the three dispatchers (GEMM_REG_LAUNCHER, gemm_kernel.inc) expand these lists.
+#define GEMM_MODE_PAIRS_NT(X) X(SRC_BF16_V16, SRC_BF16_V16) X(SRC_F32, SRC_BF16_V16) X(SRC_F32, SRC_BF16_V8) X(SRC_BF16_V8, SRC_BF16_V8)
+#define GEMM_MODE_PAIRS_NX(X) X(SRC_BF16_V16, SRC_BF16_V16) X(SRC_BF16_V16, SRC_BF16_V8)
+#define GEMM_MODE_PAIRS_TT(X) X(SRC_BF16_V16, SRC_BF16_V16) X(SRC_BF16_V16, SRC_F32) X(SRC_BF16_V16, SRC_BF16_V8)
 
 void gemm_problem_defaults(GemmProblem& p);
 
@@ -76,6 +98,9 @@ GemmTile pick_tile(const GemmGroup& g);
 // target number of K-tiles per split-K slice of a weight-gradient problem (gemm.hip)
 int ksteps_target(int compute_f32);
 
+// tiles of one M x N matrix at tile size BM x BN (gemm.hip: group_tiles sums them over a group)
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline long long gemm_tiles(int M, int N, int BM, int BN) { return (long long)ceil_div(M, BM) * ceil_div(N, BN); }
 // K-tile count of a problem for the given compute dtype (64 bf16 / 32 fp32 elements of K per tile)
 inline int gemm_ktiles(int K, int compute_f32) { const int kt = compute_f32 ? 32 : 64; return (K + kt - 1) / kt; }
 

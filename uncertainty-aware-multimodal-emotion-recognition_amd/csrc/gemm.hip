@@ -1,21 +1,11 @@
-// Host side of the grouped GEMM: validation, loader-mode selection, partition of a group by (A mode, B mode)
-// and dispatch to the instantiations in gemm_nt.hip / gemm_nx.hip / gemm_tt.hip.
+// Host side of the grouped GEMM: validation, loader-mode selection, partition of a group by (A mode, B mode), the choice of the
+// kernel each sub-group runs (gemm_route) and the walk that launches -- or only describes -- a group.
 #include "gemm.h"
 #include "options.h"
 
-#include <cstdlib>
+#include <cstdio>
 
 namespace mmdeer {
-
-int gemm_dispatch_nt(const GemmGroup& g, int total, int compute_f32, GemmTile tile, int am, int bm, hipStream_t s);
-int gemm_dispatch_nx(const GemmGroup& g, int total, int compute_f32, GemmTile tile, int am, int bm, hipStream_t s);
-int gemm_dispatch_tt(const GemmGroup& g, int total, int compute_f32, GemmTile tile, int am, int bm, hipStream_t s);
-int gemm_dispatch_nt_glds(const GemmGroup& g, int total, GemmTile tile, hipStream_t s);
-int gemm_dispatch_tt256(const GemmGroup& g, int total, hipStream_t s);
-int gemm_dispatch_tt128(const GemmGroup& g, int total, hipStream_t s);
-int gemm_dispatch_tt256x128(const GemmGroup& g, int total, hipStream_t s);
-int gemm_dispatch_tt128k2(const GemmGroup& g, int total, hipStream_t s);
-int gemm_dispatch_nt256(const GemmGroup& g, int total, int bn, hipStream_t s);
 
 // target number of K-tiles per split-K slice of a weight-gradient problem (option "ksteps" overrides)
 // in units of 64 batch rows.  Defaults: bf16 (256x256 LDS-DMA kernel) 16 = 1024 rows per slice -- the slab
@@ -27,60 +17,130 @@ int ksteps_target(int f32) {
   return f32 ? 8 : 16;
 }
 
+namespace {
+const int TILE_BM[5] = {64, 128, 128, 256, 256}, TILE_BN[5] = {64, 64, 128, 256, 128};
+
+// workgroups of a group at tile size BM x BN, split-K slices not counted
+long long group_tiles(const GemmGroup& g, int BM, int BN) {
+  long long t = 0;
+  for (int i = 0; i < g.nprob; ++i) t += gemm_tiles(g.p[i].M, g.p[i].N, BM, BN) * g.p[i].batch;
+  return t;
+}
+
+template <typename Pred>
+bool every_problem(const GemmGroup& g, Pred pred) {
+  for (int i = 0; i < g.nprob; ++i)
+    if (!pred(g.p[i])) return false;
+  return true;
+}
+
+// ---- what each LDS-DMA kernel takes, per problem.  All three also need bf16 compute, option glds and both operands in whole
+// 16-byte chunks (a_mode = b_mode = SRC_BF16_V16): gemm_route checks that once per sub-group.
+// Weight-gradient DMA kernel (gemm_tt256.hip; trans_a = trans_b = 1).  Used twice: by prepare_gemm_group BEFORE the source modes
+// exist -- when the whole group meets it, a transposed operand may end in a half-valid chunk and still be read as V16 -- and by
+// gemm_route per sub-group.  The storage conditions (bf16, ld and batch stride % 8) are what V16 itself requires, so they only
+// decide anything in prepare; the output conditions matter in both (a half-valid chunk read by the register-staged fallback
+// would be dropped).  splitk is compared with <= 1 because prepare asks before it has normalised a 0 to 1.
+bool dw_dma_takes(const GemmProblem& q) {
+  return !q.a_f32 && !q.b_f32 && q.lda % 8 == 0 && q.ldb % 8 == 0 && q.sA % 8 == 0 && q.sB % 8 == 0 &&
+         q.K % 32 == 0 && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 &&
+         (uintptr_t)q.C % 16 == 0 && q.sC % 4 == 0 && (q.splitk <= 1 || ((uintptr_t)q.slab_c % 16 == 0 && q.slab_stride % 4 == 0));
+}
+// ... and the tile requests that ask for it: 256x256 and 256x128 tiles exist only there, 128x128 under option dw_tile = 2
+bool dw_dma_requested(const GemmGroup& g, int compute_f32, GemmTile tile_req) {
+  return g.p[0].trans_a && g.p[0].trans_b && !compute_f32 && opt(OPT_GLDS) &&
+         (tile_req == TILE_256x256 || tile_req == TILE_256x128 || (tile_req == TILE_128x128 && opt(OPT_DW_TILE) == 2));
+}
+// 256-row forward kernel (gemm_nt256.hip; no transposition, tile 256x256 requested): bias / ReLU / dropout epilogue, no mask, no split-K
+bool nt256_takes(const GemmProblem& q) {
+  return q.K % 32 == 0 && q.splitk == 1 && !q.bias_grad && !q.Y && (uintptr_t)q.C % 16 == 0 && q.sC % 8 == 0 && q.ldc % 8 == 0 &&
+         (!q.bias || ((uintptr_t)q.bias % 16 == 0 && q.sBias % 4 == 0));
+}
+// LDS-DMA NT kernel (gemm_glds.hip; no transposition): whole 64-element K tiles, no split-K
+bool nt_glds_takes(const GemmProblem& q) { return q.K % 64 == 0 && q.splitk == 1 && !q.bias_grad; }
+}  // namespace
+
 // smallest tile that still gives the chip >= ~2 workgroups per CU; otherwise the largest tile count wins
 // (the Stack C and Stack B executors and mmdeer_gemm / mmdeer_gemm_batch share this policy)
 GemmTile pick_tile(const GemmGroup& g) {
   const int ft = opt(OPT_TILE);
   if (ft >= 0 && ft <= 4) return (GemmTile)ft;
-  static const int bm[3] = {64, 128, 128}, bn[3] = {64, 64, 128};
-  long long tiles[3];
-  for (int t = 0; t < 3; ++t) {
-    tiles[t] = 0;
-    for (int i = 0; i < g.nprob; ++i) {
-      const GemmProblem& p = g.p[i];
-      tiles[t] += (long long)((p.M + bm[t] - 1) / bm[t]) * ((p.N + bn[t] - 1) / bn[t]) * p.batch;
-    }
-  }
   // weight-gradient groups (both operands transposed): the strided loads and the packing LDS store cost the same per
   // K-tile whatever the tile size, so the largest tile wins; split-K supplies the parallelism
   if (g.p[0].trans_a) { const int t = opt(OPT_DW_TILE); return (GemmTile)(t < 2 ? 2 : t > 4 ? 4 : t); }   // 256x256 (falls back to 128x128 per sub-group where the kernel does not apply)
   // bf16: 128x64 and 64x64 run on the LDS-DMA kernel, 128x128 only on the register-staged one (measured on the
   // trimodal in_proj, 768 tiles of 128x128: 28.5 us against 17 us as 1536 tiles of 128x64)
   const bool f32 = g.p[0].a_f32 && g.p[0].b_f32;
-  if (f32 && tiles[2] >= 512) return TILE_128x128;
+  if (f32 && group_tiles(g, 128, 128) >= 512) return TILE_128x128;
   if (!f32) {   // big forward problems: 256x256 tiles when they fill most of the chip in one round (in_proj: 192)
-    long long t256 = 0;
-    bool plain = true;
-    for (int i = 0; i < g.nprob; ++i) {
-      const GemmProblem& p = g.p[i];
-      t256 += (long long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.batch;
-      plain = plain && !p.Y && !p.trans_b;
-    }
+    const long long t256 = group_tiles(g, 256, 256);
+    const bool plain = every_problem(g, [](const GemmProblem& p) { return !p.Y && !p.trans_b; });
     if (plain && t256 >= 160 && t256 <= 256) return TILE_256x256;
   }
-  // ~one 128x64 tile per CU: the 8-wave 128x64 kernel (launcher) moves 25 % fewer operand bytes than two 64x64
+  // ~one 128x64 tile per CU: the 8-wave 128x64 kernel (gemm_route) moves 25 % fewer operand bytes than two 64x64
   // workgroups per CU, and the K loop of those is bound by the CU's vector-memory path
-  if (!f32 && !g.p[0].trans_a && !g.p[0].trans_b && tiles[1] >= 200 && tiles[1] <= 320) return TILE_128x64;
-  if (tiles[1] >= opt(OPT_T128)) return TILE_128x64;   // option "t128": smallest 128x64 tile count that selects that kernel
+  const long long t128x64 = group_tiles(g, 128, 64);
+  if (!f32 && !g.p[0].trans_a && !g.p[0].trans_b && t128x64 >= 200 && t128x64 <= 320) return TILE_128x64;
+  if (t128x64 >= opt(OPT_T128)) return TILE_128x64;   // option "t128": smallest 128x64 tile count that selects that kernel
   return TILE_64x64;
 }
 
-// the (A mode, B mode) pairs gemm_dispatch_nt / _nx / _tt instantiate (fp32 compute: (F32, F32) only)
+// The kernel a homogeneous sub-group runs, and its tile.
+GemmRoute gemm_route(const GemmGroup& sub, int compute_f32, GemmTile tile_req) {
+  const GemmProblem& p0 = sub.p[0];
+  // every LDS-DMA kernel: bf16 compute on operands read in whole 16-byte chunks
+  const bool dma = !compute_f32 && p0.a_mode == SRC_BF16_V16 && p0.b_mode == SRC_BF16_V16 && opt(OPT_GLDS);
+  const bool big = tile_req == TILE_256x256 || tile_req == TILE_256x128;   // tiles the register-staged kernels do not have
+  if (p0.trans_a) {   // weight gradient.  256-row tiles exist only as the LDS-DMA kernel; anything else of such a group runs 128x128
+    if (dma && dw_dma_requested(sub, compute_f32, tile_req) && every_problem(sub, dw_dma_takes)) {
+      // 128x128: the K-split form (KG = 2) needs 64-row stages
+      const bool k2 = tile_req == TILE_128x128 && opt(OPT_DW_KG) == 2 &&
+                      every_problem(sub, [](const GemmProblem& q) { return q.K % 64 == 0; });
+      return {GEMM_TT_DMA, TILE_BM[tile_req], TILE_BN[tile_req], k2 ? 2 : 1};
+    }
+    const GemmTile t = big ? TILE_128x128 : tile_req;
+    return {GEMM_TT_REG, TILE_BM[t], TILE_BN[t], 0};
+  }
+  const GemmTile t = big ? TILE_128x64 : tile_req;
+  if (p0.trans_b) return {GEMM_NX_REG, TILE_BM[t], TILE_BN[t], 0};
+  if (dma && tile_req == TILE_256x256 && every_problem(sub, nt256_takes)) {
+    // 256x192 tiles when they fill the chip in one round and 256x256 tiles do not
+    const long long t192 = group_tiles(sub, 256, 192);
+    const bool n192 = opt(OPT_NT192) && every_problem(sub, [](const GemmProblem& q) { return q.N % 192 == 0; }) && t192 <= 256 &&
+                      t192 > group_tiles(sub, 256, 256);
+    return {GEMM_NT256, 256, n192 ? 192 : 256, 0};
+  }
+  if (dma && every_problem(sub, nt_glds_takes)) {
+    const long long t64 = group_tiles(sub, 128, 64), t128 = group_tiles(sub, 128, 128);
+    // These launches are bound by the bytes a CU pulls through its vector-memory path (~40 B/clk of LDS-DMA): when 128x64
+    // tiles need two workgroups per CU (in_proj dX: 512 tiles x 576 KB) and 128x128 tiles cover the problems with about one
+    // 8-wave workgroup per CU (256 x 768 KB), the square tile moves a third fewer bytes per CU
+    if (t == TILE_128x64 && opt(OPT_NT128) && every_problem(sub, [](const GemmProblem& q) { return q.N % 128 == 0; }) && t64 > 320 &&
+        t128 >= 160 && t128 <= 320)
+      return {GEMM_NT_GLDS, 128, 128, 8};
+    if (t == TILE_64x64) return {GEMM_NT_GLDS, 64, 64, 4};
+    // up to ~one workgroup per CU: the 8-wave form (96 KiB ring, one per CU); more tiles: 4 waves, 72 KiB ring, two per CU
+    if (t == TILE_128x64) return {GEMM_NT_GLDS, 128, 64, (t64 <= 320 && opt(OPT_NT8)) ? 8 : 4};
+    // (other 128x128 launches keep the register-staged kernel: its 74 KiB of LDS allow two workgroups per CU)
+  }
+  return {GEMM_NT_REG, TILE_BM[t], TILE_BN[t], 0};
+}
+
+// whether a kernel instantiates the (A mode, B mode) pair (gemm.h: GEMM_MODE_PAIRS_*)
 bool gemm_modes_instantiated(int ta, int tb, int compute_f32, int am, int bm) {
   if (compute_f32) return am == SRC_F32 && bm == SRC_F32;
-  const bool vv = am == SRC_BF16_V16 && bm == SRC_BF16_V16;
-  if (!ta && !tb) return vv || (am == SRC_F32 && (bm == SRC_BF16_V16 || bm == SRC_BF16_V8)) || (am == SRC_BF16_V8 && bm == SRC_BF16_V8);
-  if (!ta && tb) return vv || (am == SRC_BF16_V16 && bm == SRC_BF16_V8);
-  if (ta && tb) return vv || (am == SRC_BF16_V16 && (bm == SRC_F32 || bm == SRC_BF16_V8));
+#define X(a, b) || (am == a && bm == b)
+  if (!ta && !tb) return false GEMM_MODE_PAIRS_NT(X);
+  if (!ta && tb) return false GEMM_MODE_PAIRS_NX(X);
+  if (ta && tb) return false GEMM_MODE_PAIRS_TT(X);
+#undef X
   return false;
 }
 
 void gemm_problem_defaults(GemmProblem& p) {
   p = GemmProblem{};
-  p.batch = 1;
-  p.splitk = 1;
-  p.drop_site = -1;
-  p.regen_site = -1;
+  p.batch = p.splitk = 1;
+  p.drop_site = p.regen_site = -1;
   p.mask_scale = 1.f;
 }
 
@@ -89,18 +149,8 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   MMDEER_CHECK((int)tile_req >= 0 && (int)tile_req <= 4, "gemm: bad tile id %d", (int)tile_req);
   const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
   MMDEER_CHECK(!ta || tb, "gemm: (trans_a=1, trans_b=0) is not instantiated");
-  // the whole group can run on the 256x256 weight-gradient kernel (it alone tolerates padded, half-valid row ends)
-  // the weight-gradient DMA kernel on 128x128 / 256x128 tiles (option dw_tile)
-  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && opt(OPT_GLDS) && opt(OPT_DW_TILE) == 2;
-  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && opt(OPT_GLDS);
-  bool pad256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && opt(OPT_GLDS);
-  for (int i = 0; i < g.nprob && pad256; ++i) {
-    const GemmProblem& q = g.p[i];
-    // (the output conditions of the DMA kernel too: a half-valid chunk read by the register-staged fallback would be dropped)
-    pad256 = !q.a_f32 && !q.b_f32 && q.K % 32 == 0 && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 &&
-             q.lda % 8 == 0 && q.ldb % 8 == 0 && q.sA % 8 == 0 && q.sB % 8 == 0 && (uintptr_t)q.C % 16 == 0 && q.sC % 4 == 0 &&
-             (q.splitk <= 1 || ((uintptr_t)q.slab_c % 16 == 0 && q.slab_stride % 4 == 0));
-  }
+  // the whole group runs on the weight-gradient DMA kernel (it alone tolerates padded, half-valid row ends)
+  const bool pad256 = dw_dma_requested(g, compute_f32, tile_req) && every_problem(g, dw_dma_takes);
   for (int i = 0; i < g.nprob; ++i) {
     GemmProblem& p = g.p[i];
     MMDEER_CHECK((p.trans_a ? 1 : 0) == ta && (p.trans_b ? 1 : 0) == tb, "gemm[%d]: all problems of a launch must share trans flags", i);
@@ -134,7 +184,7 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
       p.a_mode = p.b_mode = SRC_F32;
     } else {
       // 16-byte loads of a bf16 source need 16-byte aligned rows AND no half-valid chunk (extent multiple of 8).
-      // Exception, 256x256 weight-gradient kernel only (pad256): a transposed operand may end in a half-valid chunk
+      // Exception, weight-gradient DMA kernel only (pad256): a transposed operand may end in a half-valid chunk
       // when its rows are padded -- the extra columns are read from inside the row and only feed outputs that are
       // never stored (the padded audio block: 84 valid columns in 128-element rows).
       const bool av16 = p.lda % 8 == 0 && p.sA % 8 == 0 &&
@@ -148,111 +198,71 @@ int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req) {
   return 0;
 }
 
-int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream) {
-  static const int bm_of[5] = {64, 128, 128, 256, 256}, bn_of[5] = {64, 64, 128, 256, 128};
+namespace {
+struct KernelEntry { const char* name; GemmLauncher* launch; };
+const KernelEntry KERNELS[GEMM_KERNEL_COUNT] = {   // indexed by GemmKernel
+    {"nt_reg", gemm_launch_nt_reg}, {"nx_reg", gemm_launch_nx_reg}, {"tt_reg", gemm_launch_tt_reg},
+    {"nt_glds", gemm_launch_nt_glds}, {"nt256", gemm_launch_nt256}, {"tt_dma", gemm_launch_tt_dma}};
+
+struct DryRun { char* out; int cap, len; };   // describe_gemm_group: the lines written so far (always NUL-terminated within cap)
+void describe_launch(DryRun& d, const GemmRoute& r, const GemmGroup& sub, int total) {
+  static const char* const mode[3] = {"f32", "v16", "v8"};   // SrcMode
+  char var[8] = "";   // w<waves> / k<KG>
+  if (r.variant) snprintf(var, sizeof var, " %c%d", r.kernel == GEMM_NT_GLDS ? 'w' : 'k', r.variant);
+  if (d.len >= d.cap) return;
+  const int n = snprintf(d.out + d.len, d.cap - d.len, "%s%s %dx%d%s a=%s b=%s tiles=%d", d.len ? "\n" : "", KERNELS[r.kernel].name,
+                         r.BM, r.BN, var, mode[sub.p[0].a_mode], mode[sub.p[0].b_mode], total);
+  d.len = d.len + n < d.cap ? d.len + n : d.cap;
+}
+
+// Runs (dry == null) or describes a group; returns the number of launches, -1 when refused.
+int walk_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream, DryRun* dry) {
   if (prepare_gemm_group(g, compute_f32, tile_req) != 0) return -1;
   g.xcd_remap = opt(OPT_XCD);
   const int ta = g.p[0].trans_a ? 1 : 0, tb = g.p[0].trans_b ? 1 : 0;
-  const bool dw128 = tile_req == TILE_128x128 && ta && tb && !compute_f32 && opt(OPT_GLDS) && opt(OPT_DW_TILE) == 2;
-  const bool dw256x128 = tile_req == TILE_256x128 && ta && tb && !compute_f32 && opt(OPT_GLDS);
-  // One launch per distinct (A mode, B mode) pair: the kernels are specialised on the pair so that their K loop
-  // has no data-dependent control flow.  Most groups are homogeneous (one launch).
   // every problem's source-mode pair before the first launch of the group: a refused group writes nothing
   for (int i = 0; i < g.nprob; ++i)
     MMDEER_CHECK(gemm_modes_instantiated(ta, tb, compute_f32, g.p[i].a_mode, g.p[i].b_mode),
                  "gemm[%d]: source-mode pair (%d,%d) is not instantiated for trans=(%d,%d)", i, g.p[i].a_mode, g.p[i].b_mode, ta, tb);
+  // One launch per distinct (A mode, B mode) pair: the kernels are specialised on the pair so that their K loop
+  // has no data-dependent control flow.  Most groups are homogeneous (one launch).
+  int launches = 0;
   bool done[GEMM_MAX_PROBLEMS] = {};
   for (int i = 0; i < g.nprob; ++i) {
     if (done[i]) continue;
     GemmGroup sub{};
-    sub.stamps = g.stamps;
-    sub.xcd_remap = g.xcd_remap;
-    sub.drop = g.drop;
-    const int am = g.p[i].a_mode, bm = g.p[i].b_mode;
+    sub.stamps = g.stamps; sub.xcd_remap = g.xcd_remap; sub.drop = g.drop;
     for (int j = i; j < g.nprob; ++j) {
-      if (done[j] || g.p[j].a_mode != am || g.p[j].b_mode != bm) continue;
+      if (done[j] || g.p[j].a_mode != g.p[i].a_mode || g.p[j].b_mode != g.p[i].b_mode) continue;
       done[j] = true;
       sub.p[sub.nprob++] = g.p[j];
     }
-    // 256x256 tiles exist only as the LDS-DMA weight-gradient kernel; anything else of such a group runs 128x128
-    bool tt256 = (tile_req == TILE_256x256 || dw128 || dw256x128) && ta && tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 &&
-                 opt(OPT_GLDS);
-    for (int j = 0; j < sub.nprob && tt256; ++j) {
-      const GemmProblem& q = sub.p[j];
-      tt256 = q.K % 32 == 0 && q.c_f32 && !q.bias && !q.relu && !q.Y && q.drop_site < 0 && q.regen_site < 0 &&
-              (uintptr_t)q.C % 16 == 0 && q.sC % 4 == 0 && (q.splitk == 1 || ((uintptr_t)q.slab_c % 16 == 0 && q.slab_stride % 4 == 0));
-    }
-    // ... and as the LDS-DMA forward kernel (bias / ReLU / dropout epilogue, no mask, no split-K)
-    bool nt256 = tile_req == TILE_256x256 && !ta && !tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 &&
-                 opt(OPT_GLDS);
-    for (int j = 0; j < sub.nprob && nt256; ++j) {
-      const GemmProblem& q = sub.p[j];
-      nt256 = q.K % 32 == 0 && q.splitk == 1 && !q.bias_grad && !q.Y && (uintptr_t)q.C % 16 == 0 && q.sC % 8 == 0 &&
-              q.ldc % 8 == 0 &&
-              (!q.bias || ((uintptr_t)q.bias % 16 == 0 && q.sBias % 4 == 0));
-    }
-    GemmTile tile = (tt256 && dw128) ? TILE_128x128 : (tt256 && dw256x128) ? TILE_256x128 : (tt256 || nt256) ? TILE_256x256 :
-                    ((tile_req == TILE_256x256 || tile_req == TILE_256x128) ? (ta ? TILE_128x128 : TILE_128x64) : tile_req);
-    // LDS-DMA fast path: bf16 NT problems whose operands are 16-byte aligned, row-contiguous and K % 64 == 0
-    bool glds_ok = !ta && !tb && !compute_f32 && am == SRC_BF16_V16 && bm == SRC_BF16_V16 && opt(OPT_GLDS);
-    for (int j = 0; j < sub.nprob && glds_ok; ++j)
-      glds_ok = sub.p[j].K % 64 == 0 && sub.p[j].splitk == 1 && !sub.p[j].bias_grad;
-    // These launches are bound by the bytes a CU pulls through its vector-memory path (~40 B/clk of LDS-DMA): when 128x64
-    // tiles need two workgroups per CU (in_proj dX: 512 tiles x 576 KB) and 128x128 tiles cover the problems with about one
-    // 8-wave workgroup per CU (256 x 768 KB), the square tile moves a third fewer bytes per CU
-    bool glds128 = false;
-    if (glds_ok && tile == TILE_128x64 && opt(OPT_NT128)) {
-      long long t64 = 0, t128 = 0;
-      bool ok = true;
-      for (int j = 0; j < sub.nprob; ++j) {
-        const GemmProblem& q = sub.p[j];
-        ok = ok && q.N % 128 == 0;
-        t64 += (long long)((q.M + 127) / 128) * ((q.N + 63) / 64) * q.batch;
-        t128 += (long long)((q.M + 127) / 128) * ((q.N + 127) / 128) * q.batch;
-      }
-      glds128 = ok && t64 > 320 && t128 >= 160 && t128 <= 320;
-      if (glds128) tile = TILE_128x128;
-    }
-    int BM = bm_of[tile], BN = bn_of[tile];
-    if (nt256 && opt(OPT_NT192)) {   // 256x192 tiles when they fill the chip in one round and 256x256 tiles do not
-      long long t256 = 0, t192 = 0;
-      bool ok = true;
-      for (int j = 0; j < sub.nprob; ++j) {
-        const GemmProblem& q = sub.p[j];
-        ok = ok && q.N % 192 == 0;
-        t256 += (long long)((q.M + 255) / 256) * ((q.N + 255) / 256) * q.batch;
-        t192 += (long long)((q.M + 255) / 256) * ((q.N + 191) / 192) * q.batch;
-      }
-      if (ok && t192 <= 256 && t192 > t256) BN = 192;
-    }
+    const GemmRoute r = gemm_route(sub, compute_f32, tile_req);
     int total = 0;
     for (int j = 0; j < sub.nprob; ++j) {
       GemmProblem& q = sub.p[j];
-      q.tiles_m = (q.M + BM - 1) / BM;
-      q.tiles_n = (q.N + BN - 1) / BN;
+      q.tiles_m = ceil_div(q.M, r.BM); q.tiles_n = ceil_div(q.N, r.BN);
       sub.tile_start[j] = total;
-      total += q.tiles_m * q.tiles_n * q.batch * q.splitk;
+      total += (int)gemm_tiles(q.M, q.N, r.BM, r.BN) * q.batch * q.splitk;
     }
     for (int j = sub.nprob; j <= GEMM_MAX_PROBLEMS; ++j) sub.tile_start[j] = total;
     if (total == 0) continue;  // empty batch: nothing to do
-    int rc;
-    // (other 128x128 launches keep the register-staged kernel: its 74 KiB of LDS allow two workgroups per CU)
-    const bool glds = glds_ok && (tile != TILE_128x128 || glds128);
-    bool k64 = opt(OPT_DW_KG) == 2;     // 128x128: the K-split form needs 64-row stages
-    for (int j = 0; j < sub.nprob && k64; ++j) k64 = sub.p[j].K % 64 == 0;
-    if (tt256 && dw128 && k64) rc = gemm_dispatch_tt128k2(sub, total, stream);
-    else if (tt256 && dw128) rc = gemm_dispatch_tt128(sub, total, stream);
-    else if (tt256 && dw256x128) rc = gemm_dispatch_tt256x128(sub, total, stream);
-    else if (tt256) rc = gemm_dispatch_tt256(sub, total, stream);
-    else if (nt256) rc = gemm_dispatch_nt256(sub, total, BN, stream);
-    else if (glds) rc = gemm_dispatch_nt_glds(sub, total, tile, stream);
-    else if (!ta && !tb) rc = gemm_dispatch_nt(sub, total, compute_f32, tile, am, bm, stream);
-    else if (!ta && tb) rc = gemm_dispatch_nx(sub, total, compute_f32, tile, am, bm, stream);
-    else if (ta && tb) rc = gemm_dispatch_tt(sub, total, compute_f32, tile, am, bm, stream);
-    else { set_error("gemm: (trans_a=1, trans_b=0) is not instantiated"); rc = -1; }
-    if (rc != 0) return rc;
+    ++launches;
+    if (dry) describe_launch(*dry, r, sub, total);
+    else TRY(KERNELS[r.kernel].launch(sub, total, r, compute_f32, stream));
   }
-  return 0;
+  return launches;
+}
+}  // namespace
+
+int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_t stream) {
+  return walk_gemm_group(g, compute_f32, tile_req, stream, nullptr) < 0 ? -1 : 0;
+}
+
+int describe_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, char* out, int cap) {
+  DryRun d{out, out && cap > 0 ? cap : 0, 0};
+  if (d.cap) out[0] = 0;
+  return walk_gemm_group(g, compute_f32, tile_req, nullptr, &d);
 }
 
 }  // namespace mmdeer

@@ -15,7 +15,6 @@
 // s_barrier -- which also proves every wave finished reading tile t-1 -- and only then re-issues into the stage tile
 // t-1 occupied.
 #include "gemm_kernel.inc"
-#include "options.h"
 
 namespace mmdeer {
 namespace {
@@ -176,17 +175,12 @@ int launch_glds(const GemmGroup& g, int total, hipStream_t stream) {
 }  // namespace
 
 // caller guarantees: bf16 compute, both operands bf16 with ld % 8 == 0 and 16-byte aligned bases, K % 64 == 0,
-// no transposition, no split-K
-int gemm_dispatch_nt_glds(const GemmGroup& g, int total, GemmTile tile, hipStream_t s) {
-  switch (tile) {
-    case TILE_64x64: return launch_glds<64, 64, 4, 4>(g, total, s);
-    case TILE_128x64:
-      // up to ~one workgroup per CU: the 8-wave form (96 KiB ring, one per CU); more tiles: 4 waves, 72 KiB ring, two per CU
-      if (total <= 320 && opt(OPT_NT8)) return launch_glds<128, 64, 4, 8>(g, total, s);
-      return launch_glds<128, 64, 3, 4>(g, total, s);
-    default: return launch_glds<128, 128, 4, 8>(g, total, s);   // one 8-wave workgroup per CU (128 KiB ring), 32x64 per wave
-  }
+// no transposition, no split-K.  Ring depth per (tile, waves): what fits the LDS with the workgroups per CU the form is meant for.
+int gemm_launch_nt_glds(const GemmGroup& g, int total, const GemmRoute& r, int, hipStream_t s) {
+  if (r.BM == 64) return launch_glds<64, 64, 4, 4>(g, total, s);
+  if (r.BN == 64 && r.variant == 8) return launch_glds<128, 64, 4, 8>(g, total, s);   // 96 KiB ring, one workgroup per CU
+  if (r.BN == 64) return launch_glds<128, 64, 3, 4>(g, total, s);                     // 72 KiB ring, two per CU
+  return launch_glds<128, 128, 4, 8>(g, total, s);   // one 8-wave workgroup per CU (128 KiB ring), 32x64 per wave
 }
-
 
 }  // namespace mmdeer

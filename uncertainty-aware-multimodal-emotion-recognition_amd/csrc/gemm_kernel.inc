@@ -592,13 +592,25 @@ int launch_variant(const GemmGroup& g, int total, hipStream_t stream) {
 
 // dispatch over the three tile shapes for one (transposition, mode pair)
 template <typename CT, bool TA, bool TB, int AM, int BMODE>
-int launch_tiles(const GemmGroup& g, int total, GemmTile tile, hipStream_t stream) {
-  switch (tile) {
-    case TILE_64x64: return launch_variant<CT, 64, 64, TA, TB, AM, BMODE>(g, total, stream);
-    case TILE_128x64: return launch_variant<CT, 128, 64, TA, TB, AM, BMODE>(g, total, stream);
-    default: return launch_variant<CT, 128, 128, TA, TB, AM, BMODE>(g, total, stream);
-  }
+int launch_tiles(const GemmGroup& g, int total, const GemmRoute& r, hipStream_t stream) {
+  if (r.BM == 64) return launch_variant<CT, 64, 64, TA, TB, AM, BMODE>(g, total, stream);
+  if (r.BN == 64) return launch_variant<CT, 128, 64, TA, TB, AM, BMODE>(g, total, stream);
+  return launch_variant<CT, 128, 128, TA, TB, AM, BMODE>(g, total, stream);
 }
+
+// The launcher of one transposition's register-staged kernels: fp32 compute, or one instantiation per bf16 source-mode pair of
+// PAIRS (gemm.h: GEMM_MODE_PAIRS_*; launch_gemm_group has refused every other pair)
+#define GEMM_REG_LAUNCH_PAIR(a, b) \
+  if (am == a && bm == b) return launch_tiles<bf16_t, TA, TB, a, b>(g, total, r, s);
+#define GEMM_REG_LAUNCHER(name, ta, tb, PAIRS)                                                                        \
+  int name(const GemmGroup& g, int total, const GemmRoute& r, int compute_f32, hipStream_t s) {                       \
+    constexpr bool TA = ta, TB = tb;                                                                                  \
+    const int am = g.p[0].a_mode, bm = g.p[0].b_mode;                                                                 \
+    if (compute_f32) return launch_tiles<float, TA, TB, SRC_F32, SRC_F32>(g, total, r, s);                            \
+    PAIRS(GEMM_REG_LAUNCH_PAIR)                                                                                       \
+    set_error("gemm: source-mode pair (%d,%d) is not instantiated for trans=(%d,%d)", am, bm, (int)TA, (int)TB);      \
+    return -1;                                                                                                        \
+  }
 
 }  // namespace
 }  // namespace mmdeer

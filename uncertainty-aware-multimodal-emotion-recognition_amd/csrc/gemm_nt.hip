@@ -3,15 +3,6 @@
 
 namespace mmdeer {
 
-// bf16-compute source-mode pairs instantiated here: (BF16_V16, BF16_V16), (F32, BF16_V16), (F32, BF16_V8), (BF16_V8, BF16_V8)
-int gemm_dispatch_nt(const GemmGroup& g, int total, int compute_f32, GemmTile tile, int am, int bm, hipStream_t s) {
-  if (compute_f32) return launch_tiles<float, false, false, SRC_F32, SRC_F32>(g, total, tile, s);
-  if (am == SRC_BF16_V16 && bm == SRC_BF16_V16) return launch_tiles<bf16_t, false, false, SRC_BF16_V16, SRC_BF16_V16>(g, total, tile, s);
-  if (am == SRC_F32 && bm == SRC_BF16_V16) return launch_tiles<bf16_t, false, false, SRC_F32, SRC_BF16_V16>(g, total, tile, s);
-  if (am == SRC_F32 && bm == SRC_BF16_V8) return launch_tiles<bf16_t, false, false, SRC_F32, SRC_BF16_V8>(g, total, tile, s);
-  if (am == SRC_BF16_V8 && bm == SRC_BF16_V8) return launch_tiles<bf16_t, false, false, SRC_BF16_V8, SRC_BF16_V8>(g, total, tile, s);
-  set_error("gemm: source-mode pair (%d,%d) is not instantiated for trans=(false,false)", am, bm);
-  return -1;
-}
+GEMM_REG_LAUNCHER(gemm_launch_nt_reg, false, false, GEMM_MODE_PAIRS_NT)
 
 }  // namespace mmdeer

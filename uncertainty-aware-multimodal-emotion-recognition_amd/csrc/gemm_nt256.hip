@@ -204,9 +204,9 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* A0, const
 }  // namespace
 
 // caller guarantees: bf16 compute, no transposition, both operands bf16 with ld % 8 == 0 and 16-byte aligned, K % 32 == 0,
-// no split-K / bias_grad / Y mask, tiles counted 256 x bn (bn = 256 or 192)
-int gemm_dispatch_nt256(const GemmGroup& g, int total, int bn, hipStream_t s) {
-  return launch_nt_preloaded(bn == 192 ? gemm_nt256_kernel<192> : gemm_nt256_kernel<256>, g, total, 5, 512, s);
+// no split-K / bias_grad / Y mask, tiles counted 256 x BN (BN = 256 or 192)
+int gemm_launch_nt256(const GemmGroup& g, int total, const GemmRoute& r, int, hipStream_t s) {
+  return launch_nt_preloaded(r.BN == 192 ? gemm_nt256_kernel<192> : gemm_nt256_kernel<256>, g, total, 5, 512, s);
 }
 
 }  // namespace mmdeer

@@ -287,32 +287,23 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
   TSTAMP(4);
 }
 
+template <int BM, int BN, int KG>
+int launch_dma(const GemmGroup& g, int total, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_tt_dma_kernel<BM, BN, KG>), dim3(total), dim3(512), 0, s, g);
+  MMDEER_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 // caller guarantees: bf16 compute, trans_a = trans_b = 1, both operands bf16 with ld % 8 == 0 and 16-byte aligned,
-// K (the reduction = batch rows) % 32 == 0, fp32 C, no bias / ReLU / dropout / mask epilogue, tiles counted 256x256
-int gemm_dispatch_tt256(const GemmGroup& g, int total, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_tt_dma_kernel<256, 256>), dim3(total), dim3(512), 0, s, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
-}
-// the same with tiles counted 128x128
-int gemm_dispatch_tt128(const GemmGroup& g, int total, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_tt_dma_kernel<128, 128>), dim3(total), dim3(512), 0, s, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
-}
-// ... 128x128 with the stage's 64 rows of K split between the two halves of the workgroup (every K % 64 == 0)
-int gemm_dispatch_tt128k2(const GemmGroup& g, int total, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_tt_dma_kernel<128, 128, 2>), dim3(total), dim3(512), 0, s, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
-}
-// ... 256x128
-int gemm_dispatch_tt256x128(const GemmGroup& g, int total, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_tt_dma_kernel<256, 128>), dim3(total), dim3(512), 0, s, g);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
+// K (the reduction = batch rows) % 32 == 0 (% 64 with KG = 2: the stage's 64 rows of K split between the two halves of the
+// workgroup), fp32 C, no bias / ReLU / dropout / mask epilogue, tiles counted r.BM x r.BN
+int gemm_launch_tt_dma(const GemmGroup& g, int total, const GemmRoute& r, int, hipStream_t s) {
+  if (r.BM == 256 && r.BN == 256) return launch_dma<256, 256, 1>(g, total, s);
+  if (r.BM == 128 && r.variant == 1) return launch_dma<128, 128, 1>(g, total, s);
+  if (r.BM == 128) return launch_dma<128, 128, 2>(g, total, s);
+  return launch_dma<256, 128, 1>(g, total, s);
 }
 
 }  // namespace mmdeer
