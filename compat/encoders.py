@@ -1,9 +1,11 @@
 """`from encoders import AudioEncoder, VideoEncoder, TextEncoder` (run_multimodal_deer.py:77).  The raw-signal front ends
 (librosa / cv2 / BERT) are out of scope; the pre-extracted-feature branch of EnhancedAudioEncoder (row a14) is real,
 and EnhancedTextEncoder is the reference's no-BERT configuration on token ids and a mask (mmdeer.text; its
-``forward_embeddings`` takes the caller's own contextual embeddings in place of BERT's last_hidden_state)."""
+``forward_embeddings`` takes the caller's own contextual embeddings in place of BERT's last_hidden_state).  EnhancedVideoEncoder is
+the reference's encoder downstream of its spatial CNN, on (B, T, 512) per-frame features (mmdeer.video; frame tensors raise)."""
 from mmdeer.side import EnhancedAudioEncoder  # noqa: F401
 from mmdeer.text import TemporalTextEncoder as EnhancedTextEncoder  # noqa: F401
+from mmdeer.video import TemporalVideoEncoder as EnhancedVideoEncoder  # noqa: F401
 
 
 def _out_of_scope(name):

@@ -1017,7 +1017,7 @@ int mmdeer_allgather(const void* send, void* recv, long long send_count, int dty
 /* sizeof() of an argument struct of this header by its name without the mmdeer_ prefix ("gemm_args", "chain_args", "chain_seg",
  * "repack_job", "forward_args", "backward_args", "adamw_args", "adamw_flat_args", "stackb_attn_train_args", "stackb_attn_args",
  * "stackb_forward_args", "stackb_weights", "softmax_mix_args", "lstm_seq_args", "temporal_pool_args", "evidence_tail_args",
- * "token_embed_args", "token_pool_args", "token_stats_args"); -1 for an unknown name.  A binding in another language checks its
+ * "token_embed_args", "token_pool_args", "token_stats_args"; of mmdeer_video.h: "conv3_time_args", "bn_time_args"); -1 for an unknown name.  A binding in another language checks its
  * own layout against it at load time (mmdeer/_lib.py does). */
 long long mmdeer_sizeof(const char* struct_name);
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mmdeer.h"
+#include "../../include/mmdeer_video.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -533,6 +534,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(gemm_args) SZ(chain_args) SZ(chain_seg) SZ(repack_job) SZ(forward_args) SZ(backward_args) SZ(adamw_args) SZ(adamw_flat_args)
   SZ(stackb_attn_train_args) SZ(stackb_attn_args) SZ(stackb_forward_args) SZ(stackb_weights) SZ(softmax_mix_args)
   SZ(lstm_seq_args) SZ(temporal_pool_args) SZ(evidence_tail_args) SZ(token_embed_args) SZ(token_pool_args) SZ(token_stats_args)
+  SZ(conv3_time_args) SZ(bn_time_args)   // mmdeer_video.h
 #undef SZ
   return -1;
 }
