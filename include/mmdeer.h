@@ -308,19 +308,24 @@ int mmdeer_reduce_batch(int n, const float* const* src, float* const* dst, const
 int mmdeer_pack_transposed_batch(int n, const float* const* src, const int32_t* rows, const int32_t* cols, void* dst,
                                  const long long* dst_off, const int32_t* ld_dst, const int32_t* dst_col, int dst_f32, void* stream);
 
-/* nn.LayerNorm(N), eps 1e-5 (fusion.py:102, 220, 305) */
+/* nn.LayerNorm(N), eps 1e-5 (fusion.py:102, 220, 305); out32 (fp32 copy of out) is optional.  Refuses (-1, before any launch) N <= 0,
+ * N % 4 != 0, N > 1024, M < 0 and, when M > 0, a NULL y / out / mean / rstd / gamma / beta.  M = 0 writes nothing. */
 int mmdeer_layernorm_fwd(const void* y, void* out, float* out32, float* mean, float* rstd, const float* gamma,
                          const float* beta, int M, int N, int act_f32, void* stream);
 int mmdeer_layernorm_bwd_nparts(int M);   /* ceil(M / 16): one partial slab per 16 consecutive rows */
 /* dz = (y > 0) * mask_scale * LayerNorm'(dout): the ReLU (+ dropout, mask_scale = 1 / (1 - p)) of the Linear-ReLU-Dropout-LayerNorm
  * blocks folded in; mask_scale <= 0: no mask (a LayerNorm behind a plain Linear, encoders.py:113-114).  partial: scratch of
  * mmdeer_layernorm_bwd_nparts(M) * 2 * N floats ([part][d gamma row | d beta row]); with dgamma = dbeta = NULL the fold of
- * the partials is left to the caller (mmdeer_reduce_batch: nparts = mmdeer_layernorm_bwd_nparts(M), stride = 2 N). */
+ * the partials is left to the caller (mmdeer_reduce_batch: nparts = mmdeer_layernorm_bwd_nparts(M), stride = 2 N).
+ * Refuses (-1, before any launch) N <= 0, N % 4 != 0, N > 1024, M < 0, a NULL partial, one of dgamma / dbeta without the other and,
+ * when M > 0, a NULL dout / y / mean / rstd / gamma / dz.  M = 0 zeroes the one partial slab (and so dgamma, dbeta) and touches nothing else. */
 int mmdeer_layernorm_bwd(const void* dout, const void* y, const float* mean, const float* rstd, const float* gamma,
                          void* dz, float* dgamma, float* dbeta, float* partial, int M, int N, int act_f32,
                          float mask_scale, void* stream);
 
-/* 2-token, 8-head self-attention of TrimodalFusion (fusion.py:325-335) on a [2B,1536] q|k|v matrix */
+/* 2-token, 8-head self-attention of TrimodalFusion (fusion.py:325-335) on a [2B,1536] q|k|v matrix; attn_w [B][2][2] and av_w [B][2]
+ * are optional.  Both refuse (-1, before any launch) B < 0 and, when B > 0, a NULL qkv / obar / probs (backward: qkv / dobar / probs /
+ * dqkv).  B = 0 writes nothing. */
 int mmdeer_trimodal_attn_fwd(const void* qkv, void* obar, float* probs, float* attn_w, float* av_w, int B,
                              int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream);
 int mmdeer_trimodal_attn_bwd(const void* qkv, const void* dobar, const float* probs, void* dqkv, int B,
@@ -375,7 +380,8 @@ int mmdeer_calibration_loss_bins(const float* gamma, const float* alpha, const f
                                  const float* edges, int n_bins, float* loss_out, int32_t* bin_counts, float* dgamma, float* dalpha,
                                  float* dbeta, void* stream);
 
-/* keep-mask of one dropout site, for test harnesses: out[r*cols + c] in {0,1} */
+/* keep-mask of one dropout site, for test harnesses: out[r*cols + c] in {0,1}.  Refuses (-1, before any launch) a NULL out and a
+ * negative rows or cols; rows * cols = 0 writes nothing. */
 int mmdeer_dropout_mask(int site, int rows, int cols, float dropout_p, uint64_t seed, uint64_t offset,
                         unsigned char* out, void* stream);
 

@@ -769,3 +769,103 @@ def test_chain_weight_ring_registers_are_never_touched_by_the_compiler():
     problems, seen = mod.check(mod.device_asm())
     assert not problems, "\n".join(problems[:20])
     assert all(n > 0 for n in seen.values()) and len(seen) >= 2
+
+
+_FAKE = 0x7000          # a non-NULL, 16-byte aligned address that a refused call never dereferences
+
+
+def _ln_fwd_args(**kw):
+    a = dict(y=_FAKE, out=_FAKE, out32=None, mean=_FAKE, rstd=_FAKE, gamma=_FAKE, beta=_FAKE, M=4, N=256, act_f32=1)
+    a.update(kw)
+    return (a["y"], a["out"], a["out32"], a["mean"], a["rstd"], a["gamma"], a["beta"], a["M"], a["N"], a["act_f32"], None)
+
+
+def _ln_bwd_args(**kw):
+    a = dict(dout=_FAKE, y=_FAKE, mean=_FAKE, rstd=_FAKE, gamma=_FAKE, dz=_FAKE, dgamma=_FAKE, dbeta=_FAKE, partial=_FAKE, M=4, N=256,
+             act_f32=1)
+    a.update(kw)
+    return (a["dout"], a["y"], a["mean"], a["rstd"], a["gamma"], a["dz"], a["dgamma"], a["dbeta"], a["partial"], a["M"], a["N"],
+            a["act_f32"], 1.0, None)
+
+
+@pytest.mark.parametrize("fn,args,words", [
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(N=0), "layernorm_fwd: N=0"),
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(N=-256), "layernorm_fwd: N=-256"),
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(N=1028), "layernorm_fwd: N=1028"),
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(N=6), "layernorm_fwd: N=6"),
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(M=-1), "layernorm_fwd: M must be >= 0"),
+    ("mmdeer_layernorm_fwd", _ln_fwd_args(M=0, N=0), "layernorm_fwd: N=0"),
+] + [("mmdeer_layernorm_fwd", _ln_fwd_args(**{k: None}), "layernorm_fwd: NULL") for k in ("y", "out", "mean", "rstd", "gamma", "beta")] + [
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(N=0), "layernorm_bwd: N=0"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(N=-4), "layernorm_bwd: N=-4"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(N=1028), "layernorm_bwd: N=1028"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(M=-16), "layernorm_bwd: M must be >= 0"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(partial=None), "layernorm_bwd: partial is NULL"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(M=0, partial=None), "layernorm_bwd: partial is NULL"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(dbeta=None), "layernorm_bwd: pass both dgamma and dbeta"),
+    ("mmdeer_layernorm_bwd", _ln_bwd_args(dgamma=None), "layernorm_bwd: pass both dgamma and dbeta"),
+] + [("mmdeer_layernorm_bwd", _ln_bwd_args(**{k: None}), "layernorm_bwd: NULL") for k in ("dout", "y", "mean", "rstd", "gamma", "dz")] + [
+    ("mmdeer_trimodal_attn_fwd", (_FAKE, _FAKE, _FAKE, None, None, -1, 1, 0, 0.0, 0, 0, None), "trimodal_attn_fwd: batch must be >= 0"),
+    ("mmdeer_trimodal_attn_fwd", (None, _FAKE, _FAKE, None, None, 4, 1, 0, 0.0, 0, 0, None), "trimodal_attn_fwd: NULL"),
+    ("mmdeer_trimodal_attn_fwd", (_FAKE, None, _FAKE, None, None, 4, 1, 0, 0.0, 0, 0, None), "trimodal_attn_fwd: NULL"),
+    ("mmdeer_trimodal_attn_fwd", (_FAKE, _FAKE, None, _FAKE, _FAKE, 4, 0, 1, 0.3, 0, 0, None), "trimodal_attn_fwd: NULL"),
+    ("mmdeer_trimodal_attn_bwd", (_FAKE, _FAKE, _FAKE, _FAKE, -2147483648, 1, 0, 0.0, 0, 0, None), "trimodal_attn_bwd: batch must be >= 0"),
+    ("mmdeer_trimodal_attn_bwd", (None, _FAKE, _FAKE, _FAKE, 4, 1, 0, 0.0, 0, 0, None), "trimodal_attn_bwd: NULL"),
+    ("mmdeer_trimodal_attn_bwd", (_FAKE, None, _FAKE, _FAKE, 4, 1, 0, 0.0, 0, 0, None), "trimodal_attn_bwd: NULL"),
+    ("mmdeer_trimodal_attn_bwd", (_FAKE, _FAKE, None, _FAKE, 4, 0, 1, 0.3, 0, 0, None), "trimodal_attn_bwd: NULL"),
+    ("mmdeer_trimodal_attn_bwd", (_FAKE, _FAKE, _FAKE, None, 4, 0, 1, 0.3, 0, 0, None), "trimodal_attn_bwd: NULL"),
+    ("mmdeer_dropout_mask", (1, -1, 8, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),
+    ("mmdeer_dropout_mask", (1, 8, -1, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),
+    ("mmdeer_dropout_mask", (1, -8, -8, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),     # a positive product
+    ("mmdeer_dropout_mask", (1, -65536, -65536, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),   # ... of 2^32
+    ("mmdeer_dropout_mask", (1, 8, 8, 0.3, 0, 0, None, None), "dropout_mask: out is NULL"),
+])
+def test_row_operators_refuse_before_any_launch(fn, args, words):
+    """LayerNorm, the trimodal attention and the dropout mask check their shapes and pointers on the host: N = 0 would divide by zero in
+    the kernel, a negative count gives a negative grid or -- two of them -- a positive product and stores out of range.  There is no GPU
+    here and the pointers are fake: the message must be the operator's own refusal, not a HIP error from an attempted launch."""
+    lib = _lib.load()
+    assert getattr(lib, fn)(*args) == -1, f"{fn}{args}: accepted"
+    msg = lib.mmdeer_last_error().decode()
+    assert words in msg and "hip" not in msg.lower(), (fn, msg)
+
+
+def test_row_operators_accept_empty_problems_without_a_launch():
+    """M = 0, B = 0, rows * cols = 0: nothing to do, no pointer is looked at (LayerNorm backward still needs `partial`: it is zeroed --
+    that one call needs a device and is made by tests/test_gpu_rowkernels.py)."""
+    lib = _lib.load()
+    assert lib.mmdeer_layernorm_fwd(None, None, None, None, None, None, None, 0, 256, 1, None) == 0
+    assert lib.mmdeer_trimodal_attn_fwd(None, None, None, None, None, 0, 1, 1, 0.3, 0, 0, None) == 0
+    assert lib.mmdeer_trimodal_attn_bwd(None, None, None, None, 0, 0, 1, 0.3, 0, 0, None) == 0
+    assert lib.mmdeer_dropout_mask(1, 0, 8, 0.3, 0, 0, _FAKE, None) == 0 and lib.mmdeer_dropout_mask(1, 8, 0, 0.3, 0, 0, _FAKE, None) == 0
+
+
+_F = _FAKE
+
+
+@pytest.mark.parametrize("fn,args,words", [
+    ("mmdeer_cross_modal_attn_fwd", (_F, _F, _F, _F, _F, 256, _F, _F, _F, -1, 1, None), "cross_modal_attn: batch must be >= 0"),
+    ("mmdeer_cross_modal_attn_fwd", (_F, _F, None, _F, _F, 256, _F, _F, _F, 4, 1, None), "cross_modal_attn: NULL pointer"),
+    ("mmdeer_cross_modal_attn_fwd", (_F, _F, _F, _F, _F, 256, None, _F, _F, 4, 0, None), "cross_modal_attn: NULL pointer"),
+    ("mmdeer_cross_modal_attn_fwd", (_F, _F, _F, _F, _F, 252, _F, _F, _F, 4, 1, None), "cross_modal_attn: ld=252"),
+    ("mmdeer_cross_modal_attn_fwd", (_F, _F, _F, _F, _F, 258, _F, _F, _F, 4, 0, None), "cross_modal_attn: ld=258"),
+    ("mmdeer_cross_modal_attn_bwd", (_F, _F, _F, _F, _F, 256, _F, _F, _F, _F, _F, _F, _F, _F, _F, -3, 1, None), "cross_modal_attn_bwd: batch must be >= 0"),
+    ("mmdeer_cross_modal_attn_bwd", (_F, _F, _F, _F, _F, 256, _F, _F, _F, _F, _F, _F, _F, _F, None, 4, 1, None), "cross_modal_attn_bwd: NULL pointer"),
+    ("mmdeer_cross_modal_attn_bwd", (_F, _F, _F, _F, _F, 256, _F, None, _F, _F, _F, _F, _F, _F, _F, 4, 0, None), "cross_modal_attn_bwd: NULL pointer"),
+    ("mmdeer_cross_modal_attn_bwd", (_F, _F, _F, _F, _F, 128, _F, _F, _F, _F, _F, _F, _F, _F, _F, 4, 1, None), "cross_modal_attn_bwd: ld=128"),
+    ("mmdeer_lstm_cell_t1", (_F, 512, _F, 128, -1, 128, 1, 1, None), "lstm_cell_t1: bad shape"),
+    ("mmdeer_lstm_cell_t1", (_F, 512, _F, 128, 4, 0, 1, 1, None), "lstm_cell_t1: bad shape"),
+    ("mmdeer_lstm_cell_t1", (_F, 512, _F, 128, 4, 128, 3, 1, None), "lstm_cell_t1: bad shape"),
+    ("mmdeer_lstm_cell_t1", (None, 512, _F, 128, 4, 128, 1, 1, None), "lstm_cell_t1: NULL pointer"),
+    ("mmdeer_lstm_cell_t1", (_F, 511, _F, 128, 4, 128, 1, 0, None), "lstm_cell_t1: leading dimensions too small"),
+    ("mmdeer_lstm_cell_t1", (_F, 1024, _F, 255, 4, 128, 2, 0, None), "lstm_cell_t1: leading dimensions too small"),
+    ("mmdeer_lstm_cell_t1_bwd", (_F, 512, _F, 128, _F, 4, -128, 1, 1, None), "lstm_cell_t1_bwd: bad shape"),
+    ("mmdeer_lstm_cell_t1_bwd", (_F, 512, _F, 128, None, 4, 128, 1, 1, None), "lstm_cell_t1_bwd: NULL pointer"),
+    ("mmdeer_lstm_cell_t1_bwd", (_F, 1023, _F, 256, _F, 4, 128, 2, 0, None), "lstm_cell_t1_bwd: leading dimensions too small"),
+])
+def test_side_row_operators_refuse_before_any_launch(fn, args, words):
+    """the side rows' own host checks (csrc/side.hip), by their messages: no launch is attempted (there is no GPU here)"""
+    lib = _lib.load()
+    assert getattr(lib, fn)(*args) == -1, f"{fn}{args}: accepted"
+    msg = lib.mmdeer_last_error().decode()
+    assert words in msg and "hip" not in msg.lower(), (fn, msg)

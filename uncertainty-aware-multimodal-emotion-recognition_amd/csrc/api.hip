@@ -359,9 +359,9 @@ int mmdeer_layernorm_bwd(const void* dout, const void* y, const float* mean, con
                          void* dz, float* dgamma, float* dbeta, float* partial, int M, int N, int act_f32,
                          float mask_scale, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  MMDEER_CHECK((dgamma != nullptr) == (dbeta != nullptr), "layernorm_bwd: pass both dgamma and dbeta, or neither");   // before the launch
   TRY(launch_ln_bwd(dout, y, mean, rstd, gamma, dz, partial, M, N, act_f32, mask_scale, s));
   if (!dgamma && !dbeta) return 0;      // the caller folds the partials (mmdeer_reduce_batch)
-  MMDEER_CHECK(dgamma && dbeta, "layernorm_bwd: pass both dgamma and dbeta, or neither");
   ReduceTable t{};
   t.nseg = 2;
   t.src[0] = partial; t.dst[0] = dgamma; t.nparts[0] = ln_bwd_nparts(M); t.n[0] = N; t.stride[0] = 2 * N;
@@ -371,11 +371,15 @@ int mmdeer_layernorm_bwd(const void* dout, const void* y, const float* mean, con
 
 int mmdeer_trimodal_attn_fwd(const void* qkv, void* obar, float* probs, float* attn_w, float* av_w, int B,
                              int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream) {
+  MMDEER_CHECK(B >= 0, "trimodal_attn_fwd: batch must be >= 0 (got %d)", B);
+  MMDEER_CHECK(B == 0 || (qkv && obar && probs), "trimodal_attn_fwd: NULL pointer (qkv / obar / probs)");
   const DropCtx dc = make_drop(dropout_p, seed, offset);
   return launch_tri_attn_fwd(qkv, obar, probs, attn_w, av_w, B, act_f32, (training && dropout_p > 0.f) ? 1 : 0, dc, (hipStream_t)stream);
 }
 int mmdeer_trimodal_attn_bwd(const void* qkv, const void* dobar, const float* probs, void* dqkv, int B,
                              int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream) {
+  MMDEER_CHECK(B >= 0, "trimodal_attn_bwd: batch must be >= 0 (got %d)", B);
+  MMDEER_CHECK(B == 0 || (qkv && dobar && probs && dqkv), "trimodal_attn_bwd: NULL pointer (qkv / dobar / probs / dqkv)");
   const DropCtx dc = make_drop(dropout_p, seed, offset);
   return launch_tri_attn_bwd(qkv, dobar, probs, dqkv, B, act_f32, (training && dropout_p > 0.f) ? 1 : 0, dc, (hipStream_t)stream);
 }

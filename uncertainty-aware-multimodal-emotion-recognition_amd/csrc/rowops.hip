@@ -224,12 +224,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* dout, const voi
     dg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     db[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  // RPT rows per trip: all their loads are in flight before the first reduction.  A wave owns M / (4 gridDim.x) rows --
-  // four at B = 4096 -- and every trip is one full memory round trip (load -> reduce -> store): one row at a time the
-  // kernel was a chain of them, two at a time it still made two (6.0 us per launch against 4.8 us for the forward).
-  constexpr int RPT = 4;
-  const int stride = gridDim.x * 4;
-  for (int row0 = blockIdx.x * 4 + wave; row0 < M; row0 += RPT * stride) {
+  // Workgroup b owns the 16 consecutive rows 16 b .. 16 b + 15 -- its slab is the partial sum over exactly those rows, as
+  // mmdeer.h states it and as the bf16 kernel above and the layer chains form theirs --; wave w takes rows 16 b + w + 4 r,
+  // r < RPT.  All RPT rows' loads are in flight before the first reduction: the trip is one full memory round trip
+  // (load -> reduce -> store); one row at a time the kernel was a chain of them, two at a time it still made two (6.0 us
+  // per launch against 4.8 us for the forward).
+  constexpr int RPT = 4, stride = 4;
+  const int row0 = blockIdx.x * 16 + wave;
+  if (row0 < M) {
     f32x4 yv[RPT][NV], d[RPT][NV];
     float mu[RPT], rs[RPT];
     bool live[RPT];
@@ -417,8 +419,11 @@ int launch_pack_transposed(PackTTable& t, void* wtdst, int w_f32, hipStream_t s)
 
 int launch_ln_fwd(const void* y, void* out, float* out32, float* mean, float* rstd, const float* gamma,
                   const float* beta, int M, int N, int act_f32, hipStream_t s) {
-  MMDEER_CHECK(N % 4 == 0 && N <= LN_MAX_VEC * 256, "layernorm: N=%d unsupported (multiple of 4, <= 1024)", N);
+  // every refusal before the launch: N = 0 would divide by zero in the kernel, a negative M gives a negative grid
+  MMDEER_CHECK(N > 0 && N % 4 == 0 && N <= LN_MAX_VEC * 256, "layernorm_fwd: N=%d unsupported (positive multiple of 4, <= 1024)", N);
+  MMDEER_CHECK(M >= 0, "layernorm_fwd: M must be >= 0 (got %d)", M);
   if (M == 0) return 0;
+  MMDEER_CHECK(y && out && mean && rstd && gamma && beta, "layernorm_fwd: NULL pointer (y / out / mean / rstd / gamma / beta)");
   if (!act_f32 && (N == 256 || N == 512)) {
     MMDEER_CHECK(((uintptr_t)y % 16) == 0 && ((uintptr_t)out % 16) == 0 && (!out32 || ((uintptr_t)out32 % 16) == 0) && ((uintptr_t)gamma % 16) == 0 &&
                      ((uintptr_t)beta % 16) == 0, "layernorm: 16-byte aligned rows / vectors");
@@ -447,9 +452,16 @@ int ln_bwd_nparts(int M) {
 
 int launch_ln_bwd(const void* dout, const void* y, const float* mean, const float* rstd, const float* gamma,
                   void* dz, float* partial, int M, int N, int act_f32, float mask_scale, hipStream_t s) {
-  MMDEER_CHECK(N % 4 == 0 && N <= LN_MAX_VEC * 256, "layernorm: N=%d unsupported (multiple of 4, <= 1024)", N);
+  MMDEER_CHECK(N > 0 && N % 4 == 0 && N <= LN_MAX_VEC * 256, "layernorm_bwd: N=%d unsupported (positive multiple of 4, <= 1024)", N);
+  MMDEER_CHECK(M >= 0, "layernorm_bwd: M must be >= 0 (got %d)", M);
+  MMDEER_CHECK(partial != nullptr, "layernorm_bwd: partial is NULL");
+  if (M == 0) {   // no rows: the one slab is all zeros (d gamma = d beta = 0); nothing else is read or written
+    MMDEER_HIP(hipMemsetAsync(partial, 0, sizeof(float) * 2 * N, s));
+    return 0;
+  }
+  MMDEER_CHECK(dout && y && mean && rstd && gamma && dz, "layernorm_bwd: NULL pointer (dout / y / mean / rstd / gamma / dz)");
   const int grid = ln_bwd_nparts(M);
-  if (!act_f32 && (N == 256 || N == 512) && M > 0) {
+  if (!act_f32 && (N == 256 || N == 512)) {
     MMDEER_CHECK(((uintptr_t)dout % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)dz % 16) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)partial % 16) == 0,
                  "layernorm backward: 16-byte aligned rows / vectors");
     const bf16_t* db = reinterpret_cast<const bf16_t*>(dout);
@@ -499,6 +511,7 @@ int launch_pad_cols(PadTable& t, hipStream_t s) {
 }
 
 int launch_dropout_mask(const DropCtx& d, int site, int rows, int cols, unsigned char* out, hipStream_t s) {
+  MMDEER_CHECK(rows >= 0 && cols >= 0, "dropout_mask: rows and cols must be >= 0 (got %d x %d)", rows, cols);
   if ((long long)rows * cols == 0) return 0;
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for((long long)rows * cols)), dim3(256), 0, s, d, site, rows, cols, out);
   MMDEER_HIP(hipGetLastError());
