@@ -89,6 +89,9 @@ size_t mmdeer_weights_bytes(int compute_f32);
  *   chain_in (1)       0: the input projections as a pad launch + one 3-problem GEMM launch also where the first chain could run them
  *   chain_nigf (0)     1: the NIG head as the tail of the forward head chain (bit-identical, one launch fewer, measured slower)
  *   chain_ts (0)       16 / 32: force the samples per chain workgroup (0: 16 up to B = 4096, 32 above)
+ *   dw_fold (1)        bf16 mode, all weight gradients in ONE launch of the DMA kernel: that launch adds its own K-slices (the tile's
+ *                      last-arriving slice, in the fold's order), folds the row partials in workgroups behind its tiles and advances
+ *                      the dropout counter -- bit-identical, one launch fewer; 0: the reduce_partials launch behind it
  *   adam_fused (1)     bf16 mode: mmdeer_adamw_step's update writes every derived weight image itself (0: element-wise update + repack launch)
  *   xcd, nt128, nt192, glds, nt8 (1), t128 (512), tile (-1), ksteps (0), splitk_max (8)   GEMM tile / split-K selection
  * mmdeer_set_option / mmdeer_get_option return -1 for an unknown name, mmdeer_set_option also for a value outside the option's
@@ -175,7 +178,8 @@ int mmdeer_forward(const mmdeer_forward_args* a);
  *   chain mode (targets == NULL): g_mu/g_nu/g_alpha/g_beta [B,3] are upstream gradients (each may be NULL).
  * grads: flat fp32 buffer of mmdeer_flat_elems() elements, ZERO-INITIALISED ONCE by the caller: every slice that
  * receives a gradient is overwritten by each call; the 64-element alignment gaps and the q/k thirds of the AV
- * in_proj (which the reference also leaves at exactly zero: L = S = 1) are never written and keep those zeros. */
+ * in_proj (which the reference also leaves at exactly zero: L = S = 1) are never written and keep those zeros.  The never-written
+ * q/k words are also the weight-gradient launch's tile counters (option dw_fold) and are zero again when that launch ends. */
 typedef struct mmdeer_backward_args {
   int32_t batch;
   int32_t compute_f32;

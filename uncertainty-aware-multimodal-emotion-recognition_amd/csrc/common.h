@@ -18,6 +18,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // `nt` stores gave the same 21.6 us but slowed the consumer down by 0.7 us).  Only for stores that cover whole cache
 // lines: the lane-direct epilogues of the small GEMMs write 8-byte pieces of a row per instruction, and as
 // write-through those cost MORE (128x64 kernel 6.4 -> 7.0 us, step 0.323 -> 0.334 ms) -- they keep plain stores.
+__device__ __forceinline__ void store_wt4(float* p, float v) {   // 4 bytes: what another workgroup of the same launch reads (sc1 loads)
+  asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+}
 template <typename V2>
 __device__ __forceinline__ void store_wt8(void* p, V2 v) {    // 8 bytes
   static_assert(sizeof(V2) == 8, "store_wt8 writes 8 bytes");

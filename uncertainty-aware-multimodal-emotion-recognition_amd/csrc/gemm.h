@@ -13,8 +13,8 @@ namespace mmdeer {
 //
 // split-K (splitk > 1, weight-gradient problems): slice s reduces K-tiles [s*ceil(nk/S), ...) and writes its
 // partial tile (and partial bias gradient) with plain stores to  slab + s*slab_stride + (offset of the final
-// destination inside the flat gradient buffer); launch_reduce_slabs() folds the S slices.  No atomics: the
-// result is deterministic and the partial traffic is streamed at store bandwidth.
+// destination inside the flat gradient buffer); launch_reduce_partials() folds the S slices, or the tile's last-arriving
+// slice does inside the launch (GemmFold below).  The sums are never atomic: the result is deterministic either way.
 struct GemmProblem {
   const void* A;
   const void* B;
@@ -46,6 +46,27 @@ enum SrcMode { SRC_F32 = 0, SRC_BF16_V16 = 1, SRC_BF16_V8 = 2 };
 
 constexpr int GEMM_MAX_PROBLEMS = 16;   // all weight-gradient problems of a backward pass fit one launch
 
+// In-launch fold of the weight-gradient DMA kernel (gemm_tt256.hip), all zero = off: the launch leaves nothing for
+// launch_reduce_partials.  With `cnt`, the workgroups of a split-K tile count their arrivals in one word per tile and the last
+// arriver adds the slices (rowops.h: the fold's order) and writes the final tile and bias gradient; the words are ZERO before the
+// launch and zero again when it ends (the last arriver resets its word), so they need no launch of their own.  The segments are
+// row partials complete before the launch (ReduceTable's field meanings, rowops.h): `nseg` of them are folded by extra workgroups
+// behind the tiles, two 256-element blocks each.  `bump`: as ReduceTable's.
+constexpr int GEMM_FOLD_SEGMENTS = 8;
+constexpr int GEMM_FOLD_SLICES = 8;         // most K-slices a counted tile may have
+struct GemmFold {
+  unsigned* cnt;
+  int cnt_n;                                // words at cnt: the launch is refused when it has more workgroups
+  int nseg;
+  unsigned long long* bump;
+  const float* src[GEMM_FOLD_SEGMENTS];
+  float* dst[GEMM_FOLD_SEGMENTS];
+  long long stride[GEMM_FOLD_SEGMENTS];
+  int nparts[GEMM_FOLD_SEGMENTS];
+  int n[GEMM_FOLD_SEGMENTS];
+  int bstart[GEMM_FOLD_SEGMENTS + 1];       // filled by the launcher
+};
+
 struct GemmGroup {
   unsigned long long* stamps;   // diagnostic builds (-DMMDEER_STAMPS) only: s_memtime samples of workgroup 0; else null
   int nprob;
@@ -53,7 +74,9 @@ struct GemmGroup {
   int tile_start[GEMM_MAX_PROBLEMS + 1];
   DropCtx drop;
   GemmProblem p[GEMM_MAX_PROBLEMS];
+  GemmFold fold;   // (behind p: the preloaded-form kernels and locate_tile address what lies in front by offset)
 };
+static_assert(sizeof(GemmGroup) + 64 + 256 <= 4096, "the kernel-argument segment (leading scalars of the preloaded form, hidden arguments) stays under 4 KiB");
 
 enum GemmTile { TILE_64x64 = 0, TILE_128x64 = 1, TILE_128x128 = 2, TILE_256x256 = 3, TILE_256x128 = 4 };   // 256x256: bf16 LDS-DMA kernels only; 256x128: bf16 weight gradients only
 
@@ -66,6 +89,9 @@ enum GemmTile { TILE_64x64 = 0, TILE_128x64 = 1, TILE_128x128 = 2, TILE_256x256 
 int prepare_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile);
 int launch_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile, hipStream_t stream);
 int describe_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile, char* out, int cap);
+
+// Whether the whole group runs as ONE launch of kernel `k` (prepare and route on a copy: nothing is launched, nothing written).
+bool gemm_group_single_launch(const GemmGroup& g, int compute_f32, GemmTile tile, int k);
 
 // The kernel one launch runs: a pure function (gemm.hip: gemm_route) of a homogeneous sub-group (one (a_mode, b_mode) pair), the compute
 // dtype, the requested tile and the options.  `variant`: waves per workgroup of the LDS-DMA NT kernel (4 / 8; the ring depth follows from

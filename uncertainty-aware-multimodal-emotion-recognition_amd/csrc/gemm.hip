@@ -137,6 +137,14 @@ bool gemm_modes_instantiated(int ta, int tb, int compute_f32, int am, int bm) {
   return false;
 }
 
+bool gemm_group_single_launch(const GemmGroup& g, int compute_f32, GemmTile tile_req, int k) {
+  GemmGroup c = g;
+  if (prepare_gemm_group(c, compute_f32, tile_req) != 0) return false;   // (the launch itself will refuse it, with this message)
+  for (int i = 1; i < c.nprob; ++i)
+    if (c.p[i].a_mode != c.p[0].a_mode || c.p[i].b_mode != c.p[0].b_mode) return false;
+  return gemm_route(c, compute_f32, tile_req).kernel == k;
+}
+
 void gemm_problem_defaults(GemmProblem& p) {
   p = GemmProblem{};
   p.batch = p.splitk = 1;
@@ -238,6 +246,11 @@ int walk_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_
       sub.p[sub.nprob++] = g.p[j];
     }
     const GemmRoute r = gemm_route(sub, compute_f32, tile_req);
+    if (g.fold.cnt || g.fold.nseg || g.fold.bump) {
+      // the caller asked gemm_group_single_launch first: a group that splits, or runs another kernel, has no in-launch fold
+      MMDEER_CHECK(sub.nprob == g.nprob && r.kernel == GEMM_TT_DMA, "gemm: the in-launch fold needs the whole group in one tt_dma launch");
+      sub.fold = g.fold;
+    }
     int total = 0;
     for (int j = 0; j < sub.nprob; ++j) {
       GemmProblem& q = sub.p[j];
@@ -247,6 +260,19 @@ int walk_gemm_group(GemmGroup& g, int compute_f32, GemmTile tile_req, hipStream_
     }
     for (int j = sub.nprob; j <= GEMM_MAX_PROBLEMS; ++j) sub.tile_start[j] = total;
     if (total == 0) continue;  // empty batch: nothing to do
+    if (sub.fold.cnt) MMDEER_CHECK(total <= sub.fold.cnt_n, "gemm: %d workgroups but %d tile counters", total, sub.fold.cnt_n);
+    if (sub.fold.nseg) {
+      GemmFold& f = sub.fold;
+      MMDEER_CHECK(f.nseg > 0 && f.nseg <= GEMM_FOLD_SEGMENTS, "gemm: bad fold segment count %d", f.nseg);
+      int blocks = 0;
+      for (int j = 0; j < f.nseg; ++j) {
+        MMDEER_CHECK(f.src[j] && f.dst[j] && f.n[j] % 4 == 0 && f.nparts[j] >= 1 && f.stride[j] % 4 == 0,
+                     "gemm: fold segment %d: n and stride must be multiples of 4", j);
+        f.bstart[j] = blocks;
+        blocks += (f.n[j] + 255) / 256;
+      }
+      for (int j = f.nseg; j <= GEMM_FOLD_SEGMENTS; ++j) f.bstart[j] = blocks;
+    }
     ++launches;
     if (dry) describe_launch(*dry, r, sub, total);
     else TRY(KERNELS[r.kernel].launch(sub, total, r, compute_f32, stream));

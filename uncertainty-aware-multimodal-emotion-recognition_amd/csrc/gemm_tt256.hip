@@ -23,11 +23,43 @@
 // that the small tile's K loop is slower per MAC (LDS-bandwidth-bound) costs less than the slabs did: -6 us per step at
 // B = 4096, -43 us at 8192.
 #include "gemm_kernel.inc"
+#include "rowops.h"
 
 #include <type_traits>
 
 namespace mmdeer {
 namespace {
+
+// Loads of what ANOTHER workgroup of this launch stored (write-through, drained before it drew its ticket): sc1, so that no line
+// this CU or this XCD's L2 holds from before is read instead.  Untracked (pipe.h rule 4): the vmcnt(0) behind a round of them is followed by statements that name the registers.
+__device__ __forceinline__ void gload16_sc1(f32x4& dst, const void* p) {
+  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void gload4_sc1(float& dst, const void* p) {
+  asm volatile("global_load_dword %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory");
+}
+
+// accumulators per round of the last arriver's combine: the largest power of two <= want, at least 1, at most all of them
+constexpr int fold_round(int want, int all) {
+  int r = 1;
+  while (2 * r <= want && 2 * r <= all) r *= 2;
+  return r;
+}
+
+// A tail workgroup (behind the tiles) of a launch that folds row partials: two 256-element blocks of the group's fold table, one per
+// half of the workgroup, in the ring's LDS.  The table is read through the kernarg segment (runtime index: gemm_tile.h).
+__device__ __forceinline__ void fold_tail(int tb, unsigned char* lds) {
+  const __attribute__((address_space(4))) GemmFold& F =
+      *(const __attribute__((address_space(4))) GemmFold*)((karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(GemmGroup, fold));
+  const int half = threadIdx.x >> 8, b = 2 * tb + half;
+  int sg = 0;
+#pragma unroll
+  for (int i = 1; i < GEMM_FOLD_SEGMENTS; ++i)
+    if (i < F.nseg && b >= F.bstart[i]) sg = i;
+  const int n = b < F.bstart[GEMM_FOLD_SEGMENTS] ? F.n[sg] : 0;
+  fold_block((const float*)F.src[sg], (float*)F.dst[sg], n, F.nparts[sg], F.stride[sg], b - F.bstart[sg], threadIdx.x & 255,
+             reinterpret_cast<f32x4(*)[64]>(lds + half * 4096));
+}
 
 // stamps.h: wave 0 of workgroup 0
 #define TSTAMP(slot) MMDEER_STAMP(g.stamps, slot, blockIdx.x == 0 && threadIdx.x == 0 && (slot) < 128)
@@ -62,7 +94,9 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
   const int li = lane & 15, lg = lane >> 4;
 
   int bid = blockIdx.x;
-  if (g.xcd_remap) bid = xcd_contiguous(bid, gridDim.x);
+  const int ntiles = g.tile_start[GEMM_MAX_PROBLEMS];   // workgroups behind the tiles fold row partials (GemmFold) and are done
+  if (bid >= ntiles) { fold_tail(bid - ntiles, lds); return; }
+  if (g.xcd_remap) bid = xcd_contiguous(bid, ntiles);
   TileAt at;
   const __attribute__((address_space(4))) GemmProblem& p = *locate_tile(g, bid, 0, at);
   const int z = at.z, slice = at.slice, tmb = at.tmb, tnb = at.tnb;
@@ -262,7 +296,11 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int r = row0 + wm * (16 * TM) + i * 16 + li;
-      if (lg == 0 && r < M) bg[(long long)z * p.sBiasGrad + r] = bsum[i].x;
+      if (lg == 0 && r < M) {
+        // a slice's partial is read by the tile's last arriver, maybe on another XCD: written through like the tile (store_wt4)
+        if (sliced) store_wt4(bg + (long long)z * p.sBiasGrad + r, bsum[i].x);
+        else bg[(long long)z * p.sBiasGrad + r] = bsum[i].x;
+      }
     }
   }
   float* dst = (sliced ? p.slab_c + (long long)slice * p.slab_stride : reinterpret_cast<float*>(p.C)) + (long long)z * p.sC;
@@ -285,11 +323,115 @@ __global__ __launch_bounds__(512) void gemm_tt_dma_kernel(const GemmGroup g) {
   TSTAMP(3);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   TSTAMP(4);
+  // the step's last launch advances the dropout step counter (this kernel draws no mask)
+  if (g.fold.bump && blockIdx.x == 0 && tid == 0) *g.fold.bump += 1;
+  if (!sliced || !g.fold.cnt) return;
+
+  // ---- in-launch fold (GemmFold).  Every wave's slab stores are write-through and have landed (the wait above); behind the
+  //      barrier one lane draws the tile's ticket, the value reaches the workgroup through the (idle) ring, and whoever drew the
+  //      last one adds the slices: the others' from their slabs (sc1 loads, every one of them), its own from its accumulators --
+  //      the very fp32 values it stored -- in the fold's order (rowops.h), and resets the counter.  Nobody waits for anybody.
+  __builtin_amdgcn_s_barrier();
+  const int np = p.splitk;
+  unsigned* cnt = g.fold.cnt + (bid - slice * (p.tiles_m * p.tiles_n));   // the tile's slice-0 workgroup number
+  volatile unsigned* ticket = reinterpret_cast<volatile unsigned*>(lds);
+  if (tid == 0) *ticket = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (*ticket != (unsigned)(np - 1)) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // no instruction: keeps the slab loads below the ticket
+  const long long sst = p.slab_stride;
+  const float* slab0 = p.slab_c + (long long)z * p.sC;
+  float* fin = reinterpret_cast<float*>(p.C) + (long long)z * p.sC;
+  const long long safe = (long long)row0 * ldc + col0;   // an element of the tile that always exists: read in place of one outside M x N
+  // R accumulators per round: all loads of a round are in flight together, (NP - 1) R float4 registers -- as many as fit beside
+  // the accumulators without spilling or costing the 32-row 128 x 128 form its second workgroup per CU (128 registers)
+  constexpr int INFLIGHT = TM * TN == 32 ? 4 : TM * TN == 8 ? 8 : 32;
+  auto combine = [&](auto ntag) __attribute__((always_inline)) {
+    constexpr int NP = decltype(ntag)::value;
+    constexpr int R = fold_round(INFLIGHT / (NP - 1), TM * TN);
+    static_assert((TM * TN) % R == 0 && NP >= 2, "rounds cover the accumulators");
+    if (do_bsum) {
+      float lb[NP - 1][TM];
+#pragma unroll
+      for (int s = 0; s < NP - 1; ++s) {
+        const int sq = s + (s >= slice ? 1 : 0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const int r = row0 + wm * (16 * TM) + i * 16 + li;
+          gload4_sc1(lb[s][i], p.slab_b + sq * sst + (long long)z * p.sBiasGrad + (r < M ? r : row0));
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int s = 0; s < NP - 1; ++s)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(lb[s][i]));
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int r = row0 + wm * (16 * TM) + i * 16 + li;
+        const float own = bsum[i].x;
+        const float v = fold_all<float>(NP, [&](int pt) {
+          float x = own;
+#pragma unroll
+          for (int s = 0; s < NP - 1; ++s) x = pt == s + (s >= slice ? 1 : 0) ? lb[s][i] : x;
+          return x;
+        });
+        if (lg == 0 && r < M) p.bias_grad[(long long)z * p.sBiasGrad + r] = v;
+      }
+    }
+#pragma unroll
+    for (int rd = 0; rd < TM * TN / R; ++rd) {
+      f32x4 ld[NP - 1][R];
+#pragma unroll
+      for (int s = 0; s < NP - 1; ++s) {
+        const float* sl = slab0 + (s + (s >= slice ? 1 : 0)) * sst;
+#pragma unroll
+        for (int a = 0; a < R; ++a) {
+          const int i = (rd * R + a) / TN, j = (rd * R + a) % TN;
+          const int m = row0 + wm * (16 * TM) + i * 16 + li, n = col0 + wn * (16 * TN) + j * 16 + 4 * lg;
+          gload16_sc1(ld[s][a], sl + (m < M && n < N ? (long long)m * ldc + n : safe));
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int s = 0; s < NP - 1; ++s)
+#pragma unroll
+        for (int a = 0; a < R; ++a) asm volatile("" : "+v"(ld[s][a]));
+#pragma unroll
+      for (int a = 0; a < R; ++a) {
+        const int i = (rd * R + a) / TN, j = (rd * R + a) % TN;
+        const int m = row0 + wm * (16 * TM) + i * 16 + li, n = col0 + wn * (16 * TN) + j * 16 + 4 * lg;
+        const f32x4 own = acc[i][j];
+        const f32x4 v = fold_all<f32x4>(NP, [&](int pt) {
+          f32x4 x = own;
+#pragma unroll
+          for (int s = 0; s < NP - 1; ++s) x = pt == s + (s >= slice ? 1 : 0) ? ld[s][a] : x;
+          return x;
+        });
+        if (m < M && n < N) store_wt16(fin + (long long)m * ldc + n, v);
+      }
+    }
+  };
+  using std::integral_constant;
+  switch (np) {   // hoisted over the whole reduction: the slice count is a constant of each copy
+    case 2: combine(integral_constant<int, 2>{}); break;
+    case 3: combine(integral_constant<int, 3>{}); break;
+    case 4: combine(integral_constant<int, 4>{}); break;
+    case 5: combine(integral_constant<int, 5>{}); break;
+    case 6: combine(integral_constant<int, 6>{}); break;
+    case 7: combine(integral_constant<int, 7>{}); break;
+    default: combine(integral_constant<int, 8>{}); break;   // the launcher holds splitk to GEMM_FOLD_SLICES
+  }
+  if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <int BM, int BN, int KG>
 int launch_dma(const GemmGroup& g, int total, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_tt_dma_kernel<BM, BN, KG>), dim3(total), dim3(512), 0, s, g);
+  if (g.fold.cnt)
+    for (int i = 0; i < g.nprob; ++i)
+      MMDEER_CHECK(g.p[i].splitk <= GEMM_FOLD_SLICES, "gemm[%d]: the in-launch fold adds at most %d K-slices (splitk = %d)", i, GEMM_FOLD_SLICES, g.p[i].splitk);
+  const int tail = g.fold.nseg ? (g.fold.bstart[GEMM_FOLD_SEGMENTS] + 1) / 2 : 0;   // two 256-element blocks per workgroup
+  hipLaunchKernelGGL((gemm_tt_dma_kernel<BM, BN, KG>), dim3(total + tail), dim3(512), 0, s, g);
   MMDEER_HIP(hipGetLastError());
   return 0;
 }

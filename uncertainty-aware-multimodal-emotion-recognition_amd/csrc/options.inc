@@ -33,3 +33,5 @@ X(OPT_CHAIN_NIGF, "chain_nigf", 0, 0, 1)        // 1 (with chain = 1; default 0)
                                                 // fetch than the 64 block partials, the tail itself 5k (DESIGN.md)
 X(OPT_ADAM_FUSED, "adam_fused", 1, 0, 1)        // 1 (bf16 mode): mmdeer_adamw_step writes every derived weight image from the update itself, tile by tile (optim.h);
                                                 // 0: element-wise update + one repack launch
+X(OPT_DW_FOLD, "dw_fold", 1, 0, 1)              // 1 (bf16 mode, all weight gradients in one launch of the DMA kernel): that launch adds its own K-slices, folds the row
+                                                // partials in workgroups behind its tiles and bumps the dropout counter; 0: the reduce_partials launch behind it

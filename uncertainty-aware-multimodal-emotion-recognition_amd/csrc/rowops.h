@@ -60,6 +60,42 @@ struct ReduceTable {
 // split-K weight-gradient slabs into the flat gradient buffer.
 int launch_reduce_partials(ReduceTable& t, hipStream_t s);
 
+// ---- the fold's arithmetic, stated once: element e of a segment = its np parts summed in THIS order, whoever adds them
+// (reduce_partials_kernel; the weight-gradient DMA kernel's last arriver and tail workgroups, gemm_tt256.hip).  V = f32x4 or float;
+// get(p) = part p of the element.  Lane pl of four sums parts pl, pl + 4, ... from zero (four at a time while at least 13 remain
+// for it, then one by one); the four lane sums join as (r0 + r1) + (r2 + r3).  A lane without a part contributes its + 0.f: a sum
+// of -0.0 comes out as +0.0.
+template <typename V, typename Get>
+__device__ __forceinline__ V fold_lane(int pl, int np, Get get) {
+  V acc = V{};
+  int p = pl;
+  for (; p + 12 < np; p += 16) {
+    const V a0 = get(p), a1 = get(p + 4), a2 = get(p + 8), a3 = get(p + 12);
+    acc += (a0 + a1) + (a2 + a3);
+  }
+  for (; p < np; p += 4) acc += get(p);
+  return acc;
+}
+template <typename V>
+__device__ __forceinline__ V fold_join(V r0, V r1, V r2, V r3) { return (r0 + r1) + (r2 + r3); }
+// all four lanes by one thread (the parts are in its registers)
+template <typename V, typename Get>
+__device__ __forceinline__ V fold_all(int np, Get get) {
+  return fold_join(fold_lane<V>(0, np, get), fold_lane<V>(1, np, get), fold_lane<V>(2, np, get), fold_lane<V>(3, np, get));
+}
+// 256 threads (t = 0 .. 255; a whole workgroup, or each aligned half of a 512-thread one: the barrier is the workgroup's) fold block
+// `blk` = 256 consecutive elements of one segment (n elements, np parts `st` apart): 64 float4 columns x 4 lanes, joined through
+// red = 4 KiB of LDS.  n = 0: a block past the last segment (it only takes part in the barrier).
+__device__ __forceinline__ void fold_block(const float* src, float* dst, int n, int np, long long st, int blk, int t, f32x4 (*red)[64]) {
+  const int e = (blk * 64 + (t & 63)) * 4;
+  const int pl = t >> 6;
+  f32x4 acc{0.f, 0.f, 0.f, 0.f};
+  if (e < n) acc = fold_lane<f32x4>(pl, np, [&](int p) { return *reinterpret_cast<const f32x4*>(src + (long long)p * st + e); });
+  red[pl][t & 63] = acc;
+  __syncthreads();
+  if (pl == 0 && e < n) store_wt16(dst + e, fold_join(red[0][t], red[1][t], red[2][t], red[3][t]));
+}
+
 // dst[r][0..ld_dst) (bf16) = src[r][0..cols) converted, zero-padded to ld_dst (a multiple of 8): gives the 84-wide
 // audio feature block / audio projection weight 16-byte aligned 128-element rows for the LDS-DMA GEMM kernels.
 constexpr int PAD_MAX_SEGMENTS = 2;

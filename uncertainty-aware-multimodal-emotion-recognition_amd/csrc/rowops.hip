@@ -304,8 +304,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* dout, const voi
 }
 
 // ------------------------------------------------------------------ partial-sum reduction
-// One block = 256 consecutive output elements of one segment: 64 float4 columns x 4 part-lanes; each lane sums
-// parts pl, pl+4, ... (4 independent loads in flight), then the 4 lanes combine through LDS in a fixed order.
+// One block = 256 consecutive output elements of one segment, folded in the order rowops.h states (fold_block).
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const ReduceTable t) {
   __shared__ f32x4 red[4][64];
   const auto& T = karg<ReduceTable>();
@@ -315,29 +314,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const ReduceTable 
 #pragma unroll
   for (int i = 1; i < REDUCE_MAX_SEGMENTS; ++i)
     if (i < T.nseg && b >= T.bstart[i]) sgm = i;
-  const int n = T.n[sgm], np = T.nparts[sgm];
-  const long long st = T.stride[sgm];
-  const float* src = (const float*)T.src[sgm];
-  const int e = ((b - T.bstart[sgm]) * 64 + (threadIdx.x & 63)) * 4;
-  const int pl = threadIdx.x >> 6;
-  f32x4 acc{0.f, 0.f, 0.f, 0.f};
-  if (e < n) {
-    int p = pl;
-    for (; p + 12 < np; p += 16) {
-      const f32x4 a0 = *reinterpret_cast<const f32x4*>(src + (long long)p * st + e);
-      const f32x4 a1 = *reinterpret_cast<const f32x4*>(src + (long long)(p + 4) * st + e);
-      const f32x4 a2 = *reinterpret_cast<const f32x4*>(src + (long long)(p + 8) * st + e);
-      const f32x4 a3 = *reinterpret_cast<const f32x4*>(src + (long long)(p + 12) * st + e);
-      acc += (a0 + a1) + (a2 + a3);
-    }
-    for (; p < np; p += 4) acc += *reinterpret_cast<const f32x4*>(src + (long long)p * st + e);
-  }
-  red[pl][threadIdx.x & 63] = acc;
-  __syncthreads();
-  if (pl == 0 && e < n) {
-    const int c = threadIdx.x;
-    store_wt16((float*)T.dst[sgm] + e, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
-  }
+  fold_block((const float*)T.src[sgm], (float*)T.dst[sgm], T.n[sgm], T.nparts[sgm], T.stride[sgm], b - T.bstart[sgm], threadIdx.x, red);
 }
 
 __global__ __launch_bounds__(256) void pad_cols_kernel(const PadTable t) {

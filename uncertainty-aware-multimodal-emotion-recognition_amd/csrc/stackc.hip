@@ -817,15 +817,34 @@ int mmdeer_backward(const mmdeer_backward_args* a) {
   // the events of buckets [first_bucket, last_bucket], which are final now.  Per-bucket launches, also on a side stream beside the dX
   // chain, were measured slower: a bucket alone is 30-180 workgroups of 16-32 sequential K-steps on a mostly idle chip.
   auto finish = [&](int first_bucket, int last_bucket) -> int {
+    // the last launch of the pass (of phase 2 in the two-call mode) advances the dropout step counter
+    unsigned long long* const bump = X.bump && (phase == 0 || phase == 2) ? reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(a->offset_dev)) : nullptr;
+    // Option dw_fold: the weight-gradient launch folds for itself -- its last-arriving K-slice adds a tile's slices, workgroups behind
+    // the tiles fold the row partials collected so far, it bumps the counter -- when the whole group is ONE launch of the DMA kernel
+    // (asked on the host, before anything runs: a group that splits by source mode, or takes a register-staged kernel, keeps the fold
+    // launch for everything).  The tile counters are words of the q/k thirds of the AV in_proj gradient, which nothing writes: zero by
+    // the caller's one-time initialisation of `grads` (include/mmdeer.h), and zero again when the launch ends.
+    dwg.drop = X.dc;
+    const bool fold_in = opt(OPT_DW_FOLD) && dwg.nprob > 0 && rt.nseg <= GEMM_FOLD_SEGMENTS &&
+                         gemm_group_single_launch(dwg, f32, pick_tile(dwg), GEMM_TT_DMA);
+    if (fold_in) {
+      GemmFold& f = dwg.fold;
+      f.cnt = reinterpret_cast<unsigned*>(G + kParams[P_AIN_W].off);
+      f.cnt_n = 2 * INTER * INTER;
+      f.bump = bump;
+      f.nseg = rt.nseg;
+      for (int i = 0; i < rt.nseg; ++i) { f.src[i] = rt.src[i]; f.dst[i] = rt.dst[i]; f.stride[i] = rt.stride[i]; f.nparts[i] = rt.nparts[i]; f.n[i] = rt.n[i]; }
+    }
     if (dwg.nprob > 0) {
       TRY(X.run(dwg));
       MARK("weight gradients (all problems, one launch)");
       for (int i = 0; i < dwg.nprob; ++i) Exec::add_slab_segments(rt, dwg.p[i]);
     }
-    // the last launch of the pass (of phase 2 in the two-call mode) advances the dropout step counter
-    if (X.bump && (phase == 0 || phase == 2)) rt.bump = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(a->offset_dev));
-    TRY(launch_reduce_partials(rt, s));
-    MARK("reduce_partials (fold)");
+    if (!fold_in) {
+      rt.bump = bump;
+      TRY(launch_reduce_partials(rt, s));
+      MARK("reduce_partials (fold)");
+    }
     for (int b = first_bucket; b <= last_bucket; ++b)
       if (a->bucket_events[b]) MMDEER_HIP(hipEventRecord((hipEvent_t)a->bucket_events[b], s));
     return 0;
