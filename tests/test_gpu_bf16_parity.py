@@ -39,14 +39,14 @@ def batch(B, seed, zero=()):
     return {k: torch.from_numpy(v) for k, v in b.items()}
 
 
-def run_pair(B, dropout, seed, zero=(), init="reference"):
+def run_pair(B, dropout, seed, zero=(), init="reference", step=None):
     """One HIP train step (bf16 compute, bf16 feature blocks) and the bf16-emulating oracle step on the same inputs,
-    parameters and dropout masks."""
+    parameters and dropout masks.  `step(model, audio, video, text, targets)` performs the HIP step (default: train_step)."""
     b = batch(B, seed=seed, zero=zero)
     m = MultimodalDEER(ModelConfig(compute_dtype="bf16", dropout=dropout, seed=seed + 1), init=init).to(DEV).train()
     a, v, t = (b[k].to(DEV).bfloat16() for k in ("audio", "video", "text"))
     y = b["targets"].to(DEV)
-    ld = m.train_step(a, v, t, y)
+    ld = m.train_step(a, v, t, y) if step is None else step(m, a, v, t, y)
     masks = dump_masks(m, B, m._step) if dropout > 0 else None
     P = O.to_params({k: w.detach().cpu() for k, w in m.state_dict().items()}, torch.float32, requires_grad=True)
     args = (a.float().cpu(), v.float().cpu(), t.float().cpu(), b["targets"])

@@ -150,6 +150,44 @@ def test_step_capture_with_a_live_process_group_and_an_in_graph_exchange():
         dist.destroy_process_group()
 
 
+def test_overlapped_train_step_with_the_real_exchange_equals_the_manual_two_calls():
+    """train_step(comm=BucketedAllReduce): the all-reduce of buckets 0-1 runs on the communicator's side stream, in place in the flat
+    gradient buffer, beside the second call of the backward (B = 512: both calls end in the weight-gradient launch's own fold).  The
+    mean over one rank is the identity: with the fp32 payload the buffer is the manual two-call result of the same dropout step bit
+    for bit; with the bf16 payload every element is within the payload's round trips."""
+    import torch.distributed as dist
+
+    from mmdeer.parallel import BucketedAllReduce
+
+    from .test_gpu_dw_fold import _inputs, _model
+    from .test_gpu_two_call import backward
+
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_free_port()}", rank=0, world_size=1,
+                            device_id=torch.device("cuda", 0))
+    try:
+        B = 512
+        dev = torch.device("cuda", 0)
+        manual = backward(B, 1)
+        assert float(manual["flat"].abs().sum()) > 0.0
+        for payload in ("fp32", "bf16"):
+            comm = BucketedAllReduce(device=dev, force=True, payload=payload)
+            assert comm.active and comm.world == 1
+            m = _model()
+            d = m.train_step(*_inputs(B, seed=11), comm=comm)
+            torch.cuda.synchronize()
+            assert comm._side is not None                     # the side-stream range form ran
+            assert float(d["total_loss"]) == float(manual["loss"][16])
+            if payload == "fp32":
+                assert torch.equal(m.flat_grad().view(torch.int32), manual["flat"].view(torch.int32))
+            else:
+                assert torch.allclose(m.flat_grad(), manual["flat"], rtol=2 ** -7, atol=0)        # two bf16 round trips
+            if comm._rccl is not None:
+                comm._rccl.close()
+    finally:
+        dist.destroy_process_group()
+
+
 def test_stack_b_trainer_with_a_gradient_exchange(tmp_path):
     """Data parallel for Stack B's fused training step: DEERTrainer exchanges the model's flat gradient buffer between the (replayed)
     step and FlatAdamW.  On a 1-rank group the mean over ranks is the identity, so the trainer with the communicator (both exchange
