@@ -394,17 +394,23 @@ int mmdeer_dropout_mask(int site, int rows, int cols, float dropout_p, uint64_t 
  * gradient buffer of mmdeer_backward.  Updates the fp32 master parameters in place and refreshes, in `weights`,
  * the packed copies mmdeer_forward / mmdeer_backward read -- so the next mmdeer_forward may pass repack = 0.
  * `lr` is a HOST array with one learning rate per live parameter (ABI order): the reference's three parameter
- * groups (0.5 lr for names containing "encoder", lr otherwise) reduce to that.  No host synchronisation. */
+ * groups (0.5 lr for names containing "encoder", lr otherwise) reduce to that.  No host synchronisation.
+ * The 64-element alignment gaps between the parameters in the flat buffers are NEITHER READ NOR WRITTEN, in every launch plan:
+ * whatever `grads` holds there does not enter the norm, and the gaps of exp_avg / exp_avg_sq keep their values.
+ * In `weights` the call writes what mmdeer_pack_weights would write for the updated parameters, byte for byte, and the
+ * wscratch field (its sum-of-squares partials); bytes that belong to no image (vector positions of wpack, matrix positions of
+ * vpack, W^T positions of matrices without a dX, the padding between fields) are left alone.  With pack_transposed = 0 the
+ * two fields that hold W^T -- wtpack and wtfpack -- are left alone entirely and every other field is written as with 1. */
 typedef struct {
   int32_t compute_f32;        /* dtype of the packed matrices, as in mmdeer_forward */
-  int32_t pack_transposed;    /* 1: also refresh the W^T copies used by mmdeer_backward */
+  int32_t pack_transposed;    /* 1: also refresh the W^T copies used by mmdeer_backward (fields wtpack, wtfpack); 0: leave both alone */
   int32_t step;               /* 1-based step count t (bias corrections 1 - beta^t) */
   float beta1, beta2, eps, weight_decay;
   float max_grad_norm;        /* > 0: gradients *= min(1, max_grad_norm / (||g||_2 + 1e-6)); <= 0: no clipping */
   float grad_scale;           /* gradients are multiplied by this first (dataset weight); 1 = none */
   const float* lr;            /* host array [mmdeer_num_params()] */
   void** params;              /* fp32 master parameters (device), canonical order, updated in place */
-  const float* grads;         /* flat gradient buffer, mmdeer_flat_elems() floats */
+  const float* grads;         /* flat gradient buffer, mmdeer_flat_elems() floats; the gaps are not read */
   float* exp_avg;             /* flat first moments  (mmdeer_flat_elems() floats, zero before the first step) */
   float* exp_avg_sq;          /* flat second moments */
   float* grad_norm;           /* device scalar out (may be NULL): global gradient norm before clipping */

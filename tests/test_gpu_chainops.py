@@ -163,17 +163,7 @@ def test_repack_operator_writes_the_documented_layouts():
     F.finish(); F.refresh()
     torch.cuda.synchronize()
 
-    def frag(M):                                                            # numpy restatement of the fragment-major order
-        R, K = M.shape
-        out = np.zeros(R * K, dtype=M.dtype)
-        for wt in range(R // 16):
-            for kt in range(K // 64):
-                for c in range(2):
-                    for lane in range(64):
-                        l = ((wt * (K // 64) + kt) * 2 + c) * 64 + lane
-                        r, k0 = 16 * wt + (lane & 15), 64 * kt + 32 * c + 8 * (lane >> 4)
-                        out[8 * l:8 * l + 8] = M[r, k0:k0 + 8]
-        return out
+    from .optim_ref import frag                                             # numpy restatement of the fragment-major order
     raw = lambda t: t.cpu().view(torch.int16).numpy()
     assert np.array_equal(raw(F("S")), frag(raw(S)))
     assert np.array_equal(raw(F("S.T")), frag(np.ascontiguousarray(raw(S).T)))

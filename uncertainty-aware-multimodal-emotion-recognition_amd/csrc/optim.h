@@ -16,7 +16,7 @@ struct AdamTable {
   int chunk_start[ADAM_MAX_SEGMENTS + 1];  // filled by the launcher
   float lr[ADAM_MAX_SEGMENTS];             // learning rate of the tensor's parameter group
   unsigned char is_vec[ADAM_MAX_SEGMENTS]; // 1: bias / LayerNorm vector -> fp32 pack, 0: matrix -> compute-dtype pack
-  const float* grads;                      // flat gradient buffer (gaps are zeros)
+  const float* grads;                      // flat gradient buffer (the gaps between the tensors are not read)
   float* exp_avg;                          // flat first / second moments
   float* exp_avg_sq;
   float* partials;                         // scratch, ADAM_NPART floats

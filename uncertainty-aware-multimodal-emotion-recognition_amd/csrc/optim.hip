@@ -3,6 +3,9 @@
 // the forward / backward kernels read (compute-dtype matrices, fp32 vectors), so a training step needs no separate
 // weight pack.  Two launches: sum-of-squares partials, then the update (every block folds the partials itself, in
 // a fixed order: deterministic, no host round trip for the norm).
+#include <algorithm>
+#include <climits>
+
 #include "optim.h"
 
 namespace mmdeer {
@@ -15,22 +18,10 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T& karg() {
   return *(const __attribute__((address_space(4))) T*)__builtin_amdgcn_kernarg_segment_ptr();
 }
 
-__global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* g, long long n4, float* partials) {
-  __shared__ float sm[4];
-  float acc = 0.f;
-  for (long long c = blockIdx.x * 256ll + threadIdx.x; c < n4; c += gridDim.x * 256ll) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(g + c * 4);
-    acc += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
-
-// The same partials over the segments of an AdamTable only (launch_adamw_pack): values outside every segment do not enter the norm.
-// A chunk goes to the thread the flat pass above would give it (flat chunk index mod the grid's threads), so over a table sorted by
-// offset whose gaps hold zeros the partials are bit for bit those of the flat pass.
+// Sum-of-squares partials over the segments of an AdamTable only: values outside every segment are not read and do not enter the norm.
+// A chunk goes to the thread a pass over the whole flat buffer would give it (flat chunk index mod the grid's threads), so over a table
+// sorted by offset the partials are bit for bit those of such a pass over a buffer whose gaps hold zeros -- and the same whichever way
+// the tensors are split into segments (launch_adamw_pack: one per tensor; launch_adamw_pack_images: runs of neighbours).
 __global__ __launch_bounds__(256) void sumsq_segments_kernel(const AdamTable t) {
   __shared__ float sm[4];
   const auto& T = karg<AdamTable>();
@@ -290,7 +281,27 @@ int launch_adamw_pack_images(AdamTable& t, AdamImagedTable& im, bf16_t* wdst, fl
   }
   im.total_tiles = tiles;
   if (c == 0 && tiles == 0) return 0;
-  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(ADAM_NPART), dim3(256), 0, s, t.grads, t.flat_elems / 4, t.partials);
+  // the norm over the tensors of both tables only: the gaps of the flat buffer between them are not read (sumsq_segments_kernel: the
+  // partials of a flat pass over zero gaps, bit for bit).  Neighbouring ranges merge into runs -- three for Stack C's parameters.
+  AdamTable nt{};
+  {
+    struct Run { long long off, n; } run[ADAM_MAX_SEGMENTS + ADAM_MAX_IMAGED];
+    int nr = 0;
+    for (int i = 0; i < t.nseg; ++i) run[nr++] = {t.off[i], t.n[i]};
+    for (int i = 0; i < im.n; ++i) run[nr++] = {im.m[i].off, (long long)im.m[i].rows * im.m[i].cols};
+    std::sort(run, run + nr, [](const Run& a, const Run& b) { return a.off < b.off; });
+    for (int i = 0; i < nr; ++i) {
+      if (nt.nseg > 0 && nt.off[nt.nseg - 1] + nt.n[nt.nseg - 1] == run[i].off && nt.n[nt.nseg - 1] + run[i].n <= INT_MAX) {
+        nt.n[nt.nseg - 1] += (int)run[i].n;
+        continue;
+      }
+      MMDEER_CHECK(nt.nseg < ADAM_MAX_SEGMENTS, "adamw: more than %d runs of neighbouring tensors", ADAM_MAX_SEGMENTS);
+      MMDEER_CHECK(nt.nseg == 0 || nt.off[nt.nseg - 1] + nt.n[nt.nseg - 1] <= run[i].off, "adamw: tensors overlap at flat offset %lld", run[i].off);
+      nt.off[nt.nseg] = run[i].off; nt.n[nt.nseg] = (int)run[i].n; ++nt.nseg;
+    }
+    nt.grads = t.grads; nt.partials = t.partials;
+  }
+  hipLaunchKernelGGL(sumsq_segments_kernel, dim3(ADAM_NPART), dim3(256), 0, s, nt);
   MMDEER_HIP(hipGetLastError());
   AdamFusedArgs a{};
   a.t = t; a.im = im; a.wdst = wdst; a.vdst = vdst; a.nblk_elem = (c + 1023) / 1024;
