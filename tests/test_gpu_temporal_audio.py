@@ -165,6 +165,67 @@ def test_pool_operators_match_float64(B, T, compute):
     assert float(b2r.grad.abs().max()) == 0.0       # written as an exact zero (the reference's value is rounding noise)
 
 
+@pytest.mark.parametrize("compute", ["fp32", "bf16"])
+@pytest.mark.parametrize("B", [1, 1024, 1029])
+def test_pool_backward_past_its_grid_cap_and_the_fold(B, compute):
+    """The backward runs at most `cap` workgroups of four samples and strides over the batch beyond them.  B = 1: one workgroup, three
+    idle waves; B = 1024: exactly the cap; B = 1029: the stride runs and its last round is ragged (sample 1028 alone).  Same float64
+    restatement and bounds as test_pool_operators_match_float64; and dw2 must be the workgroups' partials, read back from the
+    caller's scratch buffer, added in index order in fp32 -- bit for bit -- with db2 = +0.0."""
+    T, W = 2, R.H
+    cap = _lib.TEMPORAL_POOL_SCRATCH // W
+    nparts = min((B + 3) // 4, cap)
+    gen = torch.Generator().manual_seed(B + 100 * T)
+    dt = torch.float32 if compute == "fp32" else torch.bfloat16
+    h = torch.randn(T * B, 2 * R.H, generator=gen).to(dt).to(DEV)
+    z = torch.randn(T * B, R.H, generator=gen)
+    w2 = (torch.randn(1, R.H, generator=gen) * 0.4).to(DEV)
+    b2 = torch.randn(1, generator=gen).to(DEV)
+    if B > 1:   # sample 0: scores about -+80, as in the test above
+        z.reshape(T, B, -1)[:, 0, :] = 20.0 * torch.tensor([-1.0, 1.0])[:, None] * torch.sign(w2.cpu())
+    else:
+        # Alone in the batch a sample has to carry the relative bounds itself.  ds_t = a_t (dout . h_t - sum_u a_u dout . h_u) is
+        # a_0 a_1 times a difference for T = 2: with z ~ N(0, 1) the two scores are some 9 apart (w2 . tanh z has deviation 5), a_0
+        # is 1e-4 and fp32 leaves dz and dw2 three digits -- in a batch such a sample is a small term of the norm, here it would be
+        # all of it.  A tenth of the spread keeps both weights between 0.1 and 0.9.
+        z *= 0.1
+    z = z.to(dt).to(DEV)
+    gout = torch.randn(B, 2 * R.H, generator=gen).to(DEV)
+    with torch.no_grad():
+        _, wts = temporal._TemporalPoolFn.apply(h, z, w2, b2, T, B, compute)
+    dout = gout.to(dt).contiguous()
+    dh, dz = torch.full_like(h, float("nan")), torch.full_like(z, float("nan"))
+    dw2, db2 = torch.full((W,), float("nan"), device=DEV), torch.full((1,), -1.0, device=DEV)
+    scratch = torch.full((_lib.TEMPORAL_POOL_SCRATCH,), float("nan"), device=DEV)
+    w2f = w2.reshape(-1).contiguous()
+    a = _lib.TemporalPoolArgs()
+    a.h, a.ld_h, a.z, a.ld_z, a.w2, a.weights = h.data_ptr(), 2 * R.H, z.data_ptr(), R.H, w2f.data_ptr(), wts.data_ptr()
+    a.dout, a.ld_dout, a.dh, a.ld_dh, a.dz, a.ld_dz = dout.data_ptr(), 2 * R.H, dh.data_ptr(), 2 * R.H, dz.data_ptr(), R.H
+    a.dw2, a.db2, a.scratch = dw2.data_ptr(), db2.data_ptr(), scratch.data_ptr()
+    a.T, a.B, a.hidden, a.act_f32, a.stream = T, B, R.H, int(compute == "fp32"), _lib.current_stream()
+    _lib.check(_lib.load().mmdeer_temporal_pool_bwd(C.byref(a)))
+    # float64: h, z as the kernel read them
+    bt = lambda t: t.double().reshape(T, B, -1).transpose(0, 1)                      # noqa: E731
+    h64, z64 = bt(h).clone().requires_grad_(True), bt(z).clone().requires_grad_(True)
+    w64 = w2.double().clone().requires_grad_(True)
+    s = (torch.tanh(z64) @ w64.t() + b2.double())[..., 0]
+    ((torch.softmax(s, dim=1).unsqueeze(-1) * h64).sum(1) * gout.double()).sum().backward()
+    assert all(torch.isfinite(t.grad).all() for t in (h64, z64, w64))
+    tol, tol_z = (1e-5, 1e-4) if compute == "fp32" else (1e-2, 2e-2)
+    figs = {"dh": (_rel(bt(dh), h64.grad), tol), "dz": (_rel(bt(dz), z64.grad), tol_z), "dw2": (_rel(dw2, w64.grad[0]), tol_z)}
+    print(f"B={B} {compute} nparts={nparts}: " + ", ".join(f"{k} {d:.3e} (bound {b:.0e})" for k, (d, b) in figs.items()))
+    for k, (d, b) in figs.items():
+        assert d <= b, (k, d, b)
+    # the fold: the partials in index order from zero, one column per thread
+    parts = scratch.cpu().numpy().reshape(cap, W)
+    assert np.isfinite(parts[:nparts]).all() and np.isnan(parts[nparts:]).all()
+    acc = np.zeros(W, np.float32)
+    for p in range(nparts):
+        acc = acc + parts[p]
+    assert acc.dtype == np.float32 and np.array_equal(acc.view(np.uint32), dw2.cpu().numpy().view(np.uint32))
+    assert db2.cpu().numpy().view(np.uint32)[0] == 0                                 # +0.0
+
+
 def test_pool_operators_empty_batch():
     lib = _lib.load()
     a = _lib.TemporalPoolArgs()

@@ -183,6 +183,71 @@ def test_pool_operators_match_float64(B, L, compute):
         assert float(wts[2, L - 1]) == pytest.approx(float(a64[2, L - 1]), rel=1e-5) and float(wts[2, :L - 1].abs().sum()) == 0.0
 
 
+@pytest.mark.parametrize("compute", ["fp32", "bf16"])
+@pytest.mark.parametrize("B", [1024, 1027])
+def test_pool_backward_past_its_grid_cap_and_the_fold(B, compute):
+    """The backward runs at most `cap` workgroups of one sample each and strides over the batch beyond them: at B = 1027 three
+    workgroups take a second sample and cross the barrier between samples.  L = 2 with the masks of _pool_inputs (some samples
+    have one position masked, some both).  dx, dz and dw2 against text_ref.masked_pool in float64 with the bounds of
+    test_pool_operators_match_float64; and dw2 must be the workgroups' partials, read back from the caller's scratch buffer,
+    added in index order in fp32 -- bit for bit -- with db2 = +0.0."""
+    L = 2
+    cap = _lib.TOKEN_POOL_SCRATCH // A
+    nparts = min(B, cap)
+    dt = torch.float32 if compute == "fp32" else torch.bfloat16
+    x, z, mask, w2, b2, gout = _pool_inputs(B, L, dt)
+    assert bool(((mask.sum(1) == 1).sum() > 0) & ((mask.sum(1) == 2).sum() > 0))
+    xa, za, m = x.reshape(B * L, E).contiguous(), z.reshape(B * L, A).contiguous(), mask.reshape(-1).contiguous()
+    w2f = w2.reshape(-1).contiguous()
+    att = torch.empty(B, E, dtype=dt, device=DEV)
+    wts, probs = torch.empty(B, L, device=DEV), torch.empty(B, L, device=DEV)
+    dx, dz = torch.full_like(xa, float("nan")), torch.full_like(za, float("nan"))
+    dw2, db2 = torch.full((A,), float("nan"), device=DEV), torch.full((1,), -1.0, device=DEV)
+    scratch = torch.full((_lib.TOKEN_POOL_SCRATCH,), float("nan"), device=DEV)
+    a = text._pool_args(compute, B, L)
+    a.x, a.ld_x, a.z, a.ld_z, a.mask, a.w2, a.b2 = xa.data_ptr(), E, za.data_ptr(), A, m.data_ptr(), w2f.data_ptr(), b2.data_ptr()
+    a.attended, a.ld_att, a.weights, a.probs = att.data_ptr(), E, wts.data_ptr(), probs.data_ptr()
+    _lib.check(_lib.load().mmdeer_token_pool_fwd(C.byref(a)))
+    a.dout, a.ld_dout, a.dx, a.ld_dx, a.dz, a.ld_dz = gout.data_ptr(), E, dx.data_ptr(), E, dz.data_ptr(), A
+    a.dw2, a.db2, a.scratch = dw2.data_ptr(), db2.data_ptr(), scratch.data_ptr()
+    _lib.check(_lib.load().mmdeer_token_pool_bwd(C.byref(a)))
+    # float64 on the values the kernel read, and the scale of the terms summed into dz and dw2 (see the test above)
+    x64, z64, w64 = x.double(), z.double().requires_grad_(True), w2.double().requires_grad_(True)
+    att64, a64, p64 = R.masked_pool(x64, z64, mask, w64, b2.double())
+    (att64 * gout.double()).sum().backward()
+    with torch.no_grad():
+        da = (gout.double().unsqueeze(1) * x64).sum(-1)
+        S, c = (p64 * mask).sum(1, keepdim=True), (a64 * da).sum(1, keepdim=True)
+        gabs = p64 * (mask * (da.abs() + c.abs()) + c.abs() * R.EPS) / (S + R.EPS)
+        tz = torch.tanh(z64)
+        scale = {"dz": float((gabs.unsqueeze(-1) * w64.abs().reshape(1, 1, A) * (1 - tz * tz)).norm()),
+                 "dw2": float((gabs.unsqueeze(-1) * tz.abs()).sum((0, 1)).norm())}
+    hip = {"dx": dx.float().reshape(B, L, E), "dz": dz.float().reshape(B, L, A), "dw2": dw2.reshape(1, A)}
+    r64 = {"dx": a64.detach().unsqueeze(-1) * gout.double().unsqueeze(1), "dz": z64.grad, "dw2": w64.grad}
+    fp32_bound = {"dx": 1e-5, "dz": 1e-4, "dw2": 1e-4}
+    for k in hip:
+        ref = r64[k].detach()
+        assert torch.isfinite(ref).all() and torch.isfinite(hip[k]).all(), k
+        den = float(ref.norm())
+        if k in scale and den < 1e-2 * scale[k]:
+            den = scale[k]
+        d = float((hip[k].double() - ref).norm()) / den
+        if compute == "fp32" or k == "dw2":
+            bound = fp32_bound[k]
+        else:
+            bound = 2 * float((R.bf16(ref) - ref).norm()) / den + 1e-6
+        print(f"B={B} L={L} {compute} nparts={nparts} {k}: {d:.3e} (bound {bound:.3e})")
+        assert d <= bound, (k, d, bound)
+    # the fold: the partials in index order from zero, one column per thread
+    parts = scratch.cpu().numpy().reshape(cap, A)
+    assert np.isfinite(parts[:nparts]).all() and np.isnan(parts[nparts:]).all()
+    acc = np.zeros(A, np.float32)
+    for p in range(nparts):
+        acc = acc + parts[p]
+    assert acc.dtype == np.float32 and np.array_equal(acc.view(np.uint32), dw2.cpu().numpy().view(np.uint32))
+    assert db2.cpu().numpy().view(np.uint32)[0] == 0                                 # +0.0
+
+
 # ------------------------------------------------------------------------------------------------ gather and table gradients
 V, P = 1000, 20
 

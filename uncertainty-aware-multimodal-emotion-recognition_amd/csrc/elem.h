@@ -1,6 +1,6 @@
 // mmdeer -- activation elements as fp32, from bf16 or fp32 storage chosen by `template <bool F32>`: 1, 4 or 8 consecutive
 // elements from element index idx of `base`.  The 4- and 8-wide forms are vector accesses: idx must keep them aligned (8 bytes for
-// 4 bf16, 16 bytes otherwise).  Plain stores; a kernel that wants write-through stores (common.h: store_wt*) says so by name.
+// 4 bf16, 16 bytes otherwise).  Plain stores; the one write-through form is st4_wt, so a kernel that wants it says so by name.
 #pragma once
 #include "common.h"
 
@@ -34,6 +34,17 @@ template <bool F32>
 __device__ __forceinline__ void st4(void* base, long long idx, f32x4 v) {
   if constexpr (F32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx) = v;
   else *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(base) + idx) = u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
+}
+
+// st4 written through (common.h: store_wt*).  It pays where a wave writes whole rows contiguously -- full cache lines that the launch
+// does not read again; anywhere else use st4.  The 16-byte form carries its own s_nop 1 (finding 8): keep it in store_wt16.
+template <bool F32>
+__device__ __forceinline__ void st4_wt(void* base, long long idx, f32x4 v) {
+  if constexpr (F32) {
+    store_wt16(reinterpret_cast<float*>(base) + idx, v);
+  } else {
+    store_wt8(reinterpret_cast<bf16_t*>(base) + idx, u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)});
+  }
 }
 
 // one 16-byte access in bf16, two in fp32
@@ -72,12 +83,21 @@ __device__ __forceinline__ void st8(void* base, long long idx, const float (&x)[
   st8<F32>(base, idx, f32x4{x[0], x[1], x[2], x[3]}, f32x4{x[4], x[5], x[6], x[7]});
 }
 
-// four bf16 in two dwords -> fp32 (exact), and ReLU on four values
+// four bf16 in two dwords -> fp32 (exact), and ReLU / tanh on four values
 __device__ __forceinline__ f32x4 bf4_to_f32(u32x2 y) {
   return f32x4{__uint_as_float(y.x << 16), __uint_as_float(y.x & 0xFFFF0000u), __uint_as_float(y.y << 16), __uint_as_float(y.y & 0xFFFF0000u)};
 }
 __device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
+__device__ __forceinline__ f32x4 tanh4(f32x4 v) { return f32x4{tanhf(v.x), tanhf(v.y), tanhf(v.z), tanhf(v.w)}; }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus, threshold 20
+__device__ __forceinline__ float softplus_grad(float x) {
+#pragma clang fp contract(off)   // one rounding per operation in every kernel that uses it (nig_dev.h: nig_dx)
+  if (x > 20.f) return 1.f;
+  const float z = expf(x);
+  return z / (z + 1.f);
+}
 
 }  // namespace mmdeer

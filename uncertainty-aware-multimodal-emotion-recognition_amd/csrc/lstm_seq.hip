@@ -17,6 +17,7 @@
 // db2 = 0: b2 shifts every score of a sample equally, so the softmax does not depend on it.
 #include "../../include/mmdeer.h"
 #include "elem.h"
+#include "rowops.h"
 
 namespace mmdeer {
 namespace {
@@ -221,9 +222,8 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(mmdeer_lstm_seq_args 
 // ---- attention pool over time: one wave per sample; lane l owns z columns 4l .. 4l+3 and h columns 8l .. 8l+7
 template <bool F32>
 __device__ __forceinline__ float pool_score(const mmdeer_temporal_pool_args& a, long long row, const f32x4& w2, float b2, int lane) {
-  const f32x4 z = ld4<F32>(a.z, row * a.ld_z + lane * 4);
-  const float s = w2.x * tanhf(z.x) + w2.y * tanhf(z.y) + w2.z * tanhf(z.z) + w2.w * tanhf(z.w);
-  return wave_sum(s) + b2;
+  const f32x4 tz = tanh4(ld4<F32>(a.z, row * a.ld_z + lane * 4));
+  return wave_sum(w2.x * tz.x + w2.y * tz.y + w2.z * tz.z + w2.w * tz.w) + b2;
 }
 
 template <bool F32>
@@ -278,8 +278,7 @@ __global__ __launch_bounds__(256) void temporal_pool_bwd_kernel(mmdeer_temporal_
       const float ds = at * (wave_sum(p.x + p.y + p.z + p.w) - dot);
       st4<F32>(a.dh, row * a.ld_dh + lane * 8, at * d0);
       st4<F32>(a.dh, row * a.ld_dh + lane * 8 + 4, at * d1);
-      const f32x4 z = ld4<F32>(a.z, row * a.ld_z + lane * 4);
-      const f32x4 tz{tanhf(z.x), tanhf(z.y), tanhf(z.z), tanhf(z.w)};
+      const f32x4 tz = tanh4(ld4<F32>(a.z, row * a.ld_z + lane * 4));
       st4<F32>(a.dz, row * a.ld_dz + lane * 4, ds * w2 * (1.f - tz * tz));
       pw += ds * tz;
     }
@@ -288,15 +287,6 @@ __global__ __launch_bounds__(256) void temporal_pool_bwd_kernel(mmdeer_temporal_
   __syncthreads();
   if (w == 0)
     *reinterpret_cast<f32x4*>(a.scratch + blockIdx.x * 256 + lane * 4) = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-}
-
-// dw2[k] = sum over the backward's workgroups of their partials, in index order; db2 = 0 exactly
-__global__ __launch_bounds__(256) void temporal_pool_fold_kernel(const float* scratch, int nparts, float* dw2, float* db2) {
-  const int k = threadIdx.x;
-  float s = 0.f;
-  for (int p = 0; p < nparts; ++p) s += scratch[p * 256 + k];
-  dw2[k] = s;
-  if (k == 0) db2[0] = 0.f;
 }
 
 int check_seq(const mmdeer_lstm_seq_args* a, bool bwd) {
@@ -396,7 +386,7 @@ int mmdeer_temporal_pool_bwd(const mmdeer_temporal_pool_args* a) {
   int nwg = (a->B + 3) / 4;
   if (nwg > POOL_BWD_WG) nwg = POOL_BWD_WG;
   MMDEER_LAUNCH_ACT(temporal_pool_bwd_kernel, a->act_f32, dim3(nwg), dim3(256), (hipStream_t)a->stream, *a);
-  hipLaunchKernelGGL(temporal_pool_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
+  hipLaunchKernelGGL(fold_wg_partials_kernel<256>, dim3(1), dim3(256), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
   MMDEER_HIP(hipGetLastError());
   return 0;
 }

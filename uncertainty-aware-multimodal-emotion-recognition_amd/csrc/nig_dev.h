@@ -4,6 +4,7 @@
 // Reference: deer.py:86-98, losses.py:72-226, 268-348.
 #pragma once
 #include "nig.h"
+#include "elem.h"
 
 #ifndef GSTAMP
 #define GSTAMP(slot) do {} while (0)    // nig.hip's diagnostic build defines it before including this file
@@ -24,13 +25,6 @@ constexpr float kTwoPiEps = 6.28318530717958647692f;  // float32(2*pi + 1e-8) (l
 
 struct Nig { float mu, nu, alpha, beta; };
 
-__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus, threshold 20
-__device__ __forceinline__ float softplus_grad(float x) {
-#pragma clang fp contract(off)   // one rounding per operation in every kernel that includes this file (see nig_dx)
-  if (x > 20.f) return 1.f;
-  const float z = expf(x);
-  return z / (z + 1.f);
-}
 __device__ __forceinline__ Nig nig_act(const f32x4& ev) {   // deer.py:90-93
 #pragma clang fp contract(off)   // one rounding per operation in every kernel that includes this file (see nig_dx)
   Nig n;

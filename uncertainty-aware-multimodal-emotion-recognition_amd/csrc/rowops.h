@@ -95,6 +95,17 @@ __device__ __forceinline__ void fold_block(const float* src, float* dst, int n, 
   __syncthreads();
   if (pl == 0 && e < n) store_wt16(dst + e, fold_join(red[0][t], red[1][t], red[2][t], red[3][t]));
 }
+// The other fold (the attention pools' dw2: lstm_seq.hip, token_pool.hip), NOT fold_block's order: one workgroup of W threads, thread k
+// adds column k of the nparts workgroup partials (W floats each) in plain index order from zero, and zeroed[0] = +0.0 (the pools' db2:
+// the softmax does not see its bias).
+template <int W>
+__global__ __launch_bounds__(W) void fold_wg_partials_kernel(const float* scratch, int nparts, float* dst, float* zeroed) {
+  const int k = threadIdx.x;
+  float s = 0.f;
+  for (int p = 0; p < nparts; ++p) s += scratch[(long long)p * W + k];
+  dst[k] = s;
+  if (k == 0) zeroed[0] = 0.f;
+}
 
 // dst[r][0..ld_dst) (bf16) = src[r][0..cols) converted, zero-padded to ld_dst (a multiple of 8): gives the 84-wide
 // audio feature block / audio projection weight 16-byte aligned 128-element rows for the LDS-DMA GEMM kernels.

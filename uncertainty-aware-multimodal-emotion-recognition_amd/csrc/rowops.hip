@@ -15,16 +15,6 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T& karg() {
   return *(const __attribute__((address_space(4))) T*)__builtin_amdgcn_kernarg_segment_ptr();
 }
 
-template <bool F32>
-__device__ __forceinline__ void store4_wt(void* base, long long idx, f32x4 v) {
-  // a wave stores whole rows contiguously: full cache lines, written through (common.h: store_wt*)
-  if constexpr (F32) {
-    store_wt16(reinterpret_cast<float*>(base) + idx, v);
-  } else {
-    store_wt8(reinterpret_cast<bf16_t*>(base) + idx, u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)});
-  }
-}
-
 // ------------------------------------------------------------------ parameter pack
 template <bool DST_F32>
 __global__ __launch_bounds__(256) void pack_params_kernel(const PackTable t, void* wdst, float* vdst) {
@@ -51,8 +41,8 @@ __global__ __launch_bounds__(256) void pack_params_kernel(const PackTable t, voi
     while (sg + 1 < nseg && T.chunk_start[sg + 1] <= c) ++sg;
     const int e = (c - T.chunk_start[sg]) * 4;
     const f32x4 v = *reinterpret_cast<const f32x4*>((const float*)T.src[sg] + e);
-    if (T.is_vec[sg]) store4_wt<true>(vdst, T.dst_off[sg] + e, v);
-    else store4_wt<DST_F32>(wdst, T.dst_off[sg] + e, v);
+    if (T.is_vec[sg]) st4_wt<true>(vdst, T.dst_off[sg] + e, v);
+    else st4_wt<DST_F32>(wdst, T.dst_off[sg] + e, v);
   }
 }
 
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* y, void* out, f
     const int c = lane * 4 + i * 256;
     if (EXACT || c < N) {
       f32x4 o = (x[i] - mu) * rs * g[i] + b[i];
-      store4_wt<F32>(out, base + c, o);
+      st4_wt<F32>(out, base + c, o);
       if (out32) *reinterpret_cast<f32x4*>(out32 + base + c) = o;
     }
   }
@@ -282,7 +272,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* dout, const voi
             o.z = yv[r][i].z > 0.f ? dy.z * mask_scale : 0.f;
             o.w = yv[r][i].w > 0.f ? dy.w * mask_scale : 0.f;
           }
-          store4_wt<F32>(dz, base + c, o);
+          st4_wt<F32>(dz, base + c, o);
         }
       }
     }
@@ -349,14 +339,14 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(DropCtx d, int site, 
 template <bool SF32, bool DF32>
 __global__ __launch_bounds__(256) void convert_kernel(const void* src, void* dst, long long n4) {
   for (long long c = blockIdx.x * 256ll + threadIdx.x; c < n4; c += gridDim.x * 256ll)
-    store4_wt<DF32>(dst, c * 4, ld4<SF32>(src, c * 4));
+    st4_wt<DF32>(dst, c * 4, ld4<SF32>(src, c * 4));
 }
 
 // dst (activation dtype) += src (fp32)
 template <bool DF32>
 __global__ __launch_bounds__(256) void add_f32_kernel(void* dst, const float* src, long long n4) {
   for (long long c = blockIdx.x * 256ll + threadIdx.x; c < n4; c += gridDim.x * 256ll)
-    store4_wt<DF32>(dst, c * 4, ld4<DF32>(dst, c * 4) + *reinterpret_cast<const f32x4*>(src + c * 4));
+    st4_wt<DF32>(dst, c * 4, ld4<DF32>(dst, c * 4) + *reinterpret_cast<const f32x4*>(src + c * 4));
 }
 
 inline int grid_for(long long work, int per_block = 256, int cap = 2048) {

@@ -11,6 +11,7 @@
 // With a single key the reference's MultiHeadAttention softmax is identically 1, so self/cross attention are
 // output_proj(value_proj(.)) -- two GEMMs -- and never reach this file (tests/test_oracle_golden.py pins that identity).
 #include "common.h"
+#include "elem.h"
 #include "gemm.h"
 #include "rowops.h"
 
@@ -18,41 +19,6 @@
 
 namespace mmdeer {
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <bool F32>
-__device__ __forceinline__ f32x4 ld4(const void* base, long long idx) {
-  if constexpr (F32) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-  } else {
-    const u32x2 a = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    return f32x4{__uint_as_float(a.x << 16), __uint_as_float(a.x & 0xFFFF0000u), __uint_as_float(a.y << 16),
-                 __uint_as_float(a.y & 0xFFFF0000u)};
-  }
-}
-
-template <bool F32>
-__device__ __forceinline__ void st4(void* base, long long idx, f32x4 v) {
-  // every caller has a wave write whole rows contiguously: full cache lines, written through (common.h: store_wt*)
-  if constexpr (F32) {
-    store_wt16(reinterpret_cast<float*>(base) + idx, v);
-  } else {
-    u32x2 p;
-    p.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
-    p.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
-    store_wt8(reinterpret_cast<bf16_t*>(base) + idx, p);
-  }
-}
-
-template <bool F32>
-__device__ __forceinline__ float ld1(const void* base, long long idx) {
-  if constexpr (F32) return reinterpret_cast<const float*>(base)[idx];
-  else return bf2f(reinterpret_cast<const bf16_t*>(base)[idx]);
-}
-
-__device__ __forceinline__ float sigmoid_(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus_(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus, threshold 20
 
 // One wave per row, NV chunks of 4 columns per lane (N = 256 NV): the row stays in registers between the mean, the
 // variance and the output pass.  nn.LayerNorm: biased variance, eps 1e-5 inside the square root.
@@ -89,7 +55,7 @@ __global__ __launch_bounds__(256) void residual_ln_kernel(const void* y, int ld_
     const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + col), b = *reinterpret_cast<const f32x4*>(beta + col);
     f32x4 o = v[c] * rstd * g + b;
     if (x) o += ld4<F32>(x, (long long)row * ld_x + col);
-    st4<F32>(out, (long long)row * ld_out + col, o);
+    st4_wt<F32>(out, (long long)row * ld_out + col, o);
   }
 }
 
@@ -120,7 +86,7 @@ __global__ __launch_bounds__(256) void attn_mix_kernel(const AttnMix a) {
   const float w3 = a.w3[lane], b3 = a.b3[0];
   float u[3];
 #pragma unroll
-  for (int m = 0; m < 3; ++m) u[m] = sigmoid_(wave_sum(ld1<F32>(a.h2, (3ll * b + m) * 64 + lane) * w3) + b3);
+  for (int m = 0; m < 3; ++m) u[m] = sigmoidf_(wave_sum(ld1<F32>(a.h2, (3ll * b + m) * 64 + lane) * w3) + b3);
   // hidden layer of the weight network: the GEMM covered the 768 feature columns, the 3 uncertainty columns are added here
   const f32x4 pre = ld4<F32>(a.pre, (long long)b * 256 + col);
   float h[4] = {pre.x, pre.y, pre.z, pre.w};
@@ -148,8 +114,8 @@ __global__ __launch_bounds__(256) void attn_mix_kernel(const AttnMix a) {
     const f32x4 s = ld4<F32>(a.self_, (long long)b * 768 + m * 256 + col);
     const f32x4 c = ld4<F32>(a.cross, (long long)b * 768 + m * 256 + col);
     const f32x4 o = mad2(w[m], s, 1.f - u[m], c);                                  // complete_project.py:283-294
-    if (m < 2) st4<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
-    else st4<F32>(a.out_text, (long long)b * a.ld_text + col, o);
+    if (m < 2) st4_wt<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
+    else st4_wt<F32>(a.out_text, (long long)b * a.ld_text + col, o);
   }
 }
 
@@ -162,9 +128,9 @@ __global__ __launch_bounds__(256) void gate_mix_kernel(const void* g, int ld_g, 
     const int b = (int)(e / per_row), col = (int)(e - (long long)b * per_row) * 4;
     const f32x4 gl = ld4<F32>(g, (long long)b * ld_g + col), t = ld4<F32>(tri, (long long)b * ld_t + col),
                 v = ld4<F32>(av, (long long)b * ld_av + col);
-    const f32x4 s{sigmoid_(gl.x), sigmoid_(gl.y), sigmoid_(gl.z), sigmoid_(gl.w)};
+    const f32x4 s{sigmoidf_(gl.x), sigmoidf_(gl.y), sigmoidf_(gl.z), sigmoidf_(gl.w)};
     const f32x4 o = s * t + (1.f - s) * v;
-    st4<F32>(out, (long long)b * ld_out + col, o);
+    st4_wt<F32>(out, (long long)b * ld_out + col, o);
     if (out32) *reinterpret_cast<f32x4*>(out32 + (long long)b * N + col) = o;
   }
 }
@@ -185,7 +151,7 @@ __global__ __launch_bounds__(256) void stackb_head_kernel(const float* ev, int l
   if (e >= plane) return;
   const int b = (int)(e / 3), d = (int)(e - 3ll * b);
   const f32x4 r = *reinterpret_cast<const f32x4*>(ev + (long long)b * ld_ev + 4 * d);
-  const float mu = r.x, nu = softplus_(r.y) + 1e-6f, alpha = softplus_(r.z) + 1.0f, beta = softplus_(r.w) + 1e-6f;
+  const float mu = r.x, nu = softplus(r.y) + 1e-6f, alpha = softplus(r.z) + 1.0f, beta = softplus(r.w) + 1e-6f;
   const float alea = beta / (alpha - 1.f), epi = beta / (nu * (alpha - 1.f)), tot = alea + epi;
   const float s = tot / c.temperature[d];
   float h1[32];
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(256) void stackb_head_kernel(const float* ev, int l
     z += w3s[j] * fmaxf(acc, 0.f);
   }
   out[e] = mu; out[plane + e] = nu; out[2 * plane + e] = alpha; out[3 * plane + e] = beta;
-  out[4 * plane + e] = alea; out[5 * plane + e] = epi; out[6 * plane + e] = tot; out[7 * plane + e] = sigmoid_(z);
+  out[4 * plane + e] = alea; out[5 * plane + e] = epi; out[6 * plane + e] = tot; out[7 * plane + e] = sigmoidf_(z);
 }
 
 // ------------------------------------------------------------------ host side

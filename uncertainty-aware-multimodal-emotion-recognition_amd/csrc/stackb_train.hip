@@ -11,39 +11,12 @@
 //                                         (complete_project.py:395-402)
 //   * add_masked                        : out = (a + b) * (y > 0 ? scale : 0)   (gradient joins, residual connections)
 #include "common.h"
+#include "elem.h"
 
 #include "../../include/mmdeer.h"
 
 namespace mmdeer {
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <bool F32>
-__device__ __forceinline__ f32x4 tld4(const void* base, long long idx) {
-  if constexpr (F32) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-  } else {
-    const u32x2 a = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(base) + idx);
-    return f32x4{__uint_as_float(a.x << 16), __uint_as_float(a.x & 0xFFFF0000u), __uint_as_float(a.y << 16), __uint_as_float(a.y & 0xFFFF0000u)};
-  }
-}
-template <bool F32>
-__device__ __forceinline__ void tst4(void* base, long long idx, f32x4 v) {
-  if constexpr (F32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx) = v;
-  else *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(base) + idx) = u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
-}
-template <bool F32>
-__device__ __forceinline__ float tld1(const void* base, long long idx) {
-  if constexpr (F32) return reinterpret_cast<const float*>(base)[idx];
-  else return bf2f(reinterpret_cast<const bf16_t*>(base)[idx]);
-}
-template <bool F32>
-__device__ __forceinline__ void tst1(void* base, long long idx, float v) {
-  if constexpr (F32) reinterpret_cast<float*>(base)[idx] = v;
-  else reinterpret_cast<bf16_t*>(base)[idx] = f2bf(v);
-}
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 // One wave per sample; lane l owns columns 4 l .. 4 l + 3 of every 256-wide row (layouts: csrc/stackb.hip, AttnMix).
 template <bool F32>
@@ -54,8 +27,8 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
   const float w3 = a.est_w3[lane], b3 = a.est_b3[0];
   float u[3];
 #pragma unroll
-  for (int m = 0; m < 3; ++m) u[m] = sigm(wave_sum(tld1<F32>(a.h2, (3ll * b + m) * 64 + lane) * w3) + b3);
-  const f32x4 pre = tld4<F32>(a.pre, (long long)b * 256 + col);
+  for (int m = 0; m < 3; ++m) u[m] = sigmoidf_(wave_sum(ld1<F32>(a.h2, (3ll * b + m) * 64 + lane) * w3) + b3);
+  const f32x4 pre = ld4<F32>(a.pre, (long long)b * 256 + col);
   float h[4] = {pre.x, pre.y, pre.z, pre.w};
   const unsigned key = drop_on ? drop_key(dc, a.drop_site) : 0u;
 #pragma unroll
@@ -64,7 +37,7 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
     h[j] = fmaxf(fmaf(u[2], w[2], fmaf(u[1], w[1], fmaf(u[0], w[0], h[j]))), 0.f);   // mad2 (common.h): the eval and the training kernel round alike
     if (drop_on) h[j] = drop_rand1(key, (unsigned)b, (unsigned)(col + j)) < dc.thresh ? h[j] * dc.scale : 0.f;   // weight_network.2
   }
-  tst4<F32>(a.r, (long long)b * 256 + col, f32x4{h[0], h[1], h[2], h[3]});
+  st4<F32>(a.r, (long long)b * 256 + col, f32x4{h[0], h[1], h[2], h[3]});
   float lg[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -81,11 +54,11 @@ __global__ __launch_bounds__(256) void attn_mix_train_fwd_kernel(const mmdeer_st
   }
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
-    const f32x4 s = tld4<F32>(a.self_out, (long long)b * 768 + m * 256 + col);
-    const f32x4 c = tld4<F32>(a.cross_out, (long long)b * 768 + m * 256 + col);
+    const f32x4 s = ld4<F32>(a.self_out, (long long)b * 768 + m * 256 + col);
+    const f32x4 c = ld4<F32>(a.cross_out, (long long)b * 768 + m * 256 + col);
     const f32x4 o = mad2(w[m], s, 1.f - u[m], c);
-    if (m < 2) tst4<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
-    else tst4<F32>(a.out_text, (long long)b * a.ld_text + col, o);
+    if (m < 2) st4<F32>(a.out_av, (long long)b * a.ld_av + m * 256 + col, o);
+    else st4<F32>(a.out_text, (long long)b * a.ld_text + col, o);
   }
 }
 
@@ -104,26 +77,26 @@ __global__ __launch_bounds__(256) void attn_mix_bwd_kernel(const mmdeer_stackb_a
   float dw[3], du[3];
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
-    const f32x4 g = m < 2 ? tld4<F32>(a.d_av, (long long)b * a.ld_av + m * 256 + col) : tld4<F32>(a.d_text, (long long)b * a.ld_text + col);
-    const f32x4 s = tld4<F32>(a.self_out, (long long)b * 768 + m * 256 + col);
-    const f32x4 c = tld4<F32>(a.cross_out, (long long)b * 768 + m * 256 + col);
+    const f32x4 g = m < 2 ? ld4<F32>(a.d_av, (long long)b * a.ld_av + m * 256 + col) : ld4<F32>(a.d_text, (long long)b * a.ld_text + col);
+    const f32x4 s = ld4<F32>(a.self_out, (long long)b * 768 + m * 256 + col);
+    const f32x4 c = ld4<F32>(a.cross_out, (long long)b * 768 + m * 256 + col);
     dw[m] = wave_sum((g.x * s.x + g.y * s.y) + (g.z * s.z + g.w * s.w));
     du[m] = -wave_sum((g.x * c.x + g.y * c.y) + (g.z * c.z + g.w * c.w));
-    tst4<F32>(a.d_self, (long long)b * 768 + m * 256 + col, g * w[m]);
-    tst4<F32>(a.d_cross, (long long)(3 * b + m) * (a.ld_dcross ? a.ld_dcross : 256) + col, g * (1.f - u[m]));
+    st4<F32>(a.d_self, (long long)b * 768 + m * 256 + col, g * w[m]);
+    st4<F32>(a.d_cross, (long long)(3 * b + m) * (a.ld_dcross ? a.ld_dcross : 256) + col, g * (1.f - u[m]));
   }
-  if (a.unc8 && lane < 2) tst4<F32>(a.unc8, 8ll * b + 4 * lane, lane == 0 ? f32x4{u[0], u[1], u[2], 0.f} : f32x4{0.f, 0.f, 0.f, 0.f});
+  if (a.unc8 && lane < 2) st4<F32>(a.unc8, 8ll * b + 4 * lane, lane == 0 ? f32x4{u[0], u[1], u[2], 0.f} : f32x4{0.f, 0.f, 0.f, 0.f});
   // softmax over the three modalities
   const float dot = dw[0] * w[0] + dw[1] * w[1] + dw[2] * w[2];
   float dl[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) dl[k] = w[k] * (dw[k] - dot);
   if (lane == 0) {
-    tst4<F32>(a.d_logits8, 8ll * b, f32x4{dl[0], dl[1], dl[2], 0.f});
-    tst4<F32>(a.d_logits8, 8ll * b + 4, f32x4{0.f, 0.f, 0.f, 0.f});
+    st4<F32>(a.d_logits8, 8ll * b, f32x4{dl[0], dl[1], dl[2], 0.f});
+    st4<F32>(a.d_logits8, 8ll * b + 4, f32x4{0.f, 0.f, 0.f, 0.f});
   }
   // weight_network.3 -> hidden r (post-dropout): d r = W2^T d logits; mask (r > 0) * 1 / (1 - p)
-  const f32x4 r = tld4<F32>(a.r, (long long)b * 256 + col);
+  const f32x4 r = ld4<F32>(a.r, (long long)b * 256 + col);
   const float rr[4] = {r.x, r.y, r.z, r.w};
   float dp[4];
 #pragma unroll
@@ -131,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_mix_bwd_kernel(const mmdeer_stackb_a
     const float dr = dl[0] * a.wn_w2[col + j] + dl[1] * a.wn_w2[256 + col + j] + dl[2] * a.wn_w2[512 + col + j];
     dp[j] = rr[j] > 0.f ? dr * mask_scale : 0.f;
   }
-  tst4<F32>(a.d_pre, (long long)b * 256 + col, f32x4{dp[0], dp[1], dp[2], dp[3]});
+  st4<F32>(a.d_pre, (long long)b * 256 + col, f32x4{dp[0], dp[1], dp[2], dp[3]});
   // ... and through the three uncertainty columns of weight_network.0
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
@@ -146,11 +119,11 @@ __global__ __launch_bounds__(256) void attn_mix_bwd_kernel(const mmdeer_stackb_a
   for (int m = 0; m < 3; ++m) {
     const float dz = du[m] * u[m] * (1.f - u[m]);
     if (lane == 0) {
-      tst4<F32>(a.d_z8, 8 * (3ll * b + m), f32x4{dz, 0.f, 0.f, 0.f});
-      tst4<F32>(a.d_z8, 8 * (3ll * b + m) + 4, f32x4{0.f, 0.f, 0.f, 0.f});
+      st4<F32>(a.d_z8, 8 * (3ll * b + m), f32x4{dz, 0.f, 0.f, 0.f});
+      st4<F32>(a.d_z8, 8 * (3ll * b + m) + 4, f32x4{0.f, 0.f, 0.f, 0.f});
     }
-    const float h = tld1<F32>(a.h2, (3ll * b + m) * 64 + lane);
-    tst1<F32>(a.d_h2, (3ll * b + m) * 64 + lane, h > 0.f ? dz * w3 : 0.f);
+    const float h = ld1<F32>(a.h2, (3ll * b + m) * 64 + lane);
+    st1<F32>(a.d_h2, (3ll * b + m) * 64 + lane, h > 0.f ? dz * w3 : 0.f);
   }
 }
 
@@ -164,13 +137,13 @@ __global__ __launch_bounds__(256) void gate_mix_bwd_kernel(const void* dout, int
   const long long total = (long long)B * per_row;
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
     const int b = (int)(e / per_row), col = (int)(e - (long long)b * per_row) * 4;
-    const f32x4 d = tld4<F32>(dout, (long long)b * ld_do + col), gl = tld4<F32>(g, (long long)b * ld_g + col);
-    const f32x4 t = tld4<F32>(tri, (long long)b * ld_t + col), v = tld4<F32>(av, (long long)b * ld_av + col);
-    const f32x4 s{sigm(gl.x), sigm(gl.y), sigm(gl.z), sigm(gl.w)};
-    tst4<F32>(dg, (long long)b * ld_dg + col, d * (t - v) * s * (1.f - s));
+    const f32x4 d = ld4<F32>(dout, (long long)b * ld_do + col), gl = ld4<F32>(g, (long long)b * ld_g + col);
+    const f32x4 t = ld4<F32>(tri, (long long)b * ld_t + col), v = ld4<F32>(av, (long long)b * ld_av + col);
+    const f32x4 s{sigmoidf_(gl.x), sigmoidf_(gl.y), sigmoidf_(gl.z), sigmoidf_(gl.w)};
+    st4<F32>(dg, (long long)b * ld_dg + col, d * (t - v) * s * (1.f - s));
     const f32x4 dt = d * s;
-    tst4<F32>(dtri, (long long)b * ld_dt + col, f32x4{t.x > 0.f ? dt.x : 0.f, t.y > 0.f ? dt.y : 0.f, t.z > 0.f ? dt.z : 0.f, t.w > 0.f ? dt.w : 0.f});
-    tst4<F32>(dav, (long long)b * ld_dav + col, d * (1.f - s));
+    st4<F32>(dtri, (long long)b * ld_dt + col, f32x4{t.x > 0.f ? dt.x : 0.f, t.y > 0.f ? dt.y : 0.f, t.z > 0.f ? dt.z : 0.f, t.w > 0.f ? dt.w : 0.f});
+    st4<F32>(dav, (long long)b * ld_dav + col, d * (1.f - s));
   }
 }
 
@@ -182,9 +155,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* ev, int ld_e
   if (e >= plane) return;
   const int b = (int)(e / 3), d = (int)(e - 3ll * b);
   const f32x4 r = *reinterpret_cast<const f32x4*>(ev + (long long)b * ld_ev + 4 * d);
-  auto sp = [](float x) { return x > 20.f ? 1.f : sigm(x); };
-  tst4<F32>(dev, (long long)b * ld_dev + 8 * d, f32x4{g[e], g[plane + e] * sp(r.y), g[2 * plane + e] * sp(r.z), g[3 * plane + e] * sp(r.w)});
-  tst4<F32>(dev, (long long)b * ld_dev + 8 * d + 4, f32x4{0.f, 0.f, 0.f, 0.f});
+  auto sp = [](float x) { return x > 20.f ? 1.f : sigmoidf_(x); };
+  st4<F32>(dev, (long long)b * ld_dev + 8 * d, f32x4{g[e], g[plane + e] * sp(r.y), g[2 * plane + e] * sp(r.z), g[3 * plane + e] * sp(r.w)});
+  st4<F32>(dev, (long long)b * ld_dev + 8 * d + 4, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 
 template <bool F32>
@@ -194,13 +167,13 @@ __global__ __launch_bounds__(256) void add_masked_kernel(void* out, int ld_o, co
   const long long total = (long long)M * per_row;
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
     const int r = (int)(e / per_row), col = (int)(e - (long long)r * per_row) * 4;
-    f32x4 v = tld4<F32>(x, (long long)r * ld_x + col);
-    if (y2) v += tld4<F32>(y2, (long long)r * ld_y2 + col);
+    f32x4 v = ld4<F32>(x, (long long)r * ld_x + col);
+    if (y2) v += ld4<F32>(y2, (long long)r * ld_y2 + col);
     if (mask) {
-      const f32x4 k = tld4<F32>(mask, (long long)r * ld_m + col);
+      const f32x4 k = ld4<F32>(mask, (long long)r * ld_m + col);
       v = f32x4{k.x > 0.f ? v.x * scale : 0.f, k.y > 0.f ? v.y * scale : 0.f, k.z > 0.f ? v.z * scale : 0.f, k.w > 0.f ? v.w * scale : 0.f};
     }
-    tst4<F32>(out, (long long)r * ld_o + col, v);
+    st4<F32>(out, (long long)r * ld_o + col, v);
   }
 }
 

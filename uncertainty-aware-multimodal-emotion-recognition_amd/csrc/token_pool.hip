@@ -18,6 +18,7 @@
 // Statistics (mmdeer_token_stats): one workgroup per sample, ids in LDS, O(L^2) duplicate count, integer LDS atomics only.
 #include "../../include/mmdeer.h"
 #include "elem.h"
+#include "rowops.h"
 
 namespace mmdeer {
 namespace {
@@ -45,7 +46,6 @@ __device__ __forceinline__ float dot_row(const f32x4 (&a)[4], const f32x4 (&b)[4
   const f32x4 p = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
   return wave_sum((p.x + p.y) + (p.z + p.w));
 }
-__device__ __forceinline__ f32x4 tanh4(const f32x4& z) { return f32x4{tanhf(z.x), tanhf(z.y), tanhf(z.z), tanhf(z.w)}; }
 
 // ------------------------------------------------------------------------------------------------ gather
 // one wave per row (grid-stride).  Tables: x = (emb[clamp(id)] + pos[min(t, P - 1)]) * m and ids32 = the clamped id;
@@ -289,15 +289,6 @@ __global__ __launch_bounds__(256) void token_pool_bwd_kernel(mmdeer_token_pool_a
   }
 }
 
-// dw2[k] = sum over the backward's workgroups of their partials, in index order; db2 = 0 exactly
-__global__ __launch_bounds__(TOK_A) void token_pool_fold_kernel(const float* scratch, int nparts, float* dw2, float* db2) {
-  const int k = threadIdx.x;
-  float s = 0.f;
-  for (int p = 0; p < nparts; ++p) s += scratch[(long long)p * TOK_A + k];
-  dw2[k] = s;
-  if (k == 0) db2[0] = 0.f;
-}
-
 // ------------------------------------------------------------------------------------------------ statistics
 // out[b][0..5] = n / max_length, u / max(n, 1), n / (id_max + 1), c_max, #{999 <= id <= 1030} / max(n, 1),
 // #{100 <= id <= 999} / max(n, 1); out[b][6..15] = 0.  n = 0: all zeros.
@@ -486,7 +477,7 @@ int mmdeer_token_pool_bwd(const mmdeer_token_pool_args* a) {
   if (a->B == 0 || a->L == 0) return 0;
   const int nwg = a->B < TOK_POOL_BWD_WG ? a->B : TOK_POOL_BWD_WG;
   MMDEER_LAUNCH_ACT(token_pool_bwd_kernel, a->act_f32, dim3(nwg), dim3(256), (hipStream_t)a->stream, *a);
-  hipLaunchKernelGGL(token_pool_fold_kernel, dim3(1), dim3(TOK_A), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
+  hipLaunchKernelGGL(fold_wg_partials_kernel<TOK_A>, dim3(1), dim3(TOK_A), 0, (hipStream_t)a->stream, a->scratch, nwg, a->dw2, a->db2);
   MMDEER_HIP(hipGetLastError());
   return 0;
 }
