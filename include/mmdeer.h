@@ -343,7 +343,15 @@ int mmdeer_trimodal_attn_bwd(const void* qkv, const void* dobar, const float* pr
  *   mmdeer_trimodal_fused_fwd: xtok bf16 [2B][512] (row 2b + t) -> obar bf16 [B][512], probs fp32 [B][8][4]; q|k|v stay
  *                              on chip unless qkv_out (bf16 [2B][1536], optional) is given.  attn_w / av_w as above, optional.
  *   mmdeer_trimodal_fused_bwd: recomputes q|k|v per head tile and writes dqkv bf16 [2B][1536] from dobar bf16 [B][512]
- *                              and the saved probs. */
+ *                              and the saved probs.
+ * Rounding points: the scores are products of q and k ROUNDED to bf16 (the values qkv_out holds), v enters P V and q, k, v enter the
+ * backward unrounded.  The softmax over the two keys is stated with a clamp:
+ *   probs[t][t] = 1 / (1 + 2^min((s[t][1-t] - s[t][t]) * log2(e) / 8, 115)),   probs[t][1-t] = 2^min(..) * probs[t][t],
+ * so a key that loses by more than 115 ln 2 = 79.7 after the 1/8 keeps the probability 2^-115 (2.4e-35) where the true one is smaller,
+ * and the winner's is 1.
+ * Batch ceiling: both refuse (-1, before any launch) B > 2^21 - 1 = 2097151: obar and probs are addressed with 32-bit byte ranges and
+ * offsets (B * 1024 bytes of obar must stay below 2^31).  Both also refuse B < 0 and, when B > 0, a NULL xtok / whm / bias / obar /
+ * probs (backward: xtok / whm / bias / dobar / probs / dqkv).  B = 0 writes nothing. */
 int mmdeer_pack_qkv_headmajor(const float* in_proj_weight, void* whm_bf16, void* stream);
 int mmdeer_trimodal_fused_fwd(const void* xtok, const void* whm_bf16, const float* in_proj_bias, void* obar, float* probs,
                               void* qkv_out, float* attn_w, float* av_w, int B, int training, float dropout_p, uint64_t seed,

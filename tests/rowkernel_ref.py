@@ -1,6 +1,7 @@
 """float64 restatements of the row kernels: LayerNorm (csrc/rowops.hip, csrc/ln_rows.h), the trimodal 2-token attention
 (csrc/attention.hip), the side rows (csrc/side.hip: CrossModalAttention core, the T = 1 LSTM cell), mmdeer_convert and the dropout draw
-(csrc/common.h, make_drop of csrc/api.hip).  Written from the formulas in plain torch / numpy: nothing here calls the library or oracle/.
+(csrc/common.h, make_drop of csrc/api.hip), and the in_proj + attention of csrc/tri_fused.hip in stages (projection, clamped softmax of
+the stored q and k, context, backward).  Written from the formulas in plain torch / numpy: nothing here calls the library or oracle/.
 
 Every value comes with a *scale* (DESIGN.md section 13): the sum of the absolute values of the pieces that are added to form it,
 carried through the formula by the class SV below -- a sum's scale is the sum of its pieces' scales plus the sum of their absolute
@@ -273,31 +274,42 @@ def tri_keep(B, p, seed, offset):
 
 # =========================================================================== trimodal attention
 def _tri_split(qkv, dt):
-    X = leaf(qkv, dt)
+    """qkv [2B, 1536]: a tensor (an exact input) or an SV (values that carry a scale, e.g. the float64 projection of fused_proj)."""
+    X = SV(qkv.v.to(dt), qkv.s.to(dt)) if isinstance(qkv, SV) else leaf(qkv, dt)
     B = X.v.shape[0] // 2
     X = X.reshape(B, 2, 3, 8, 64)
     return B, X[:, :, 0], X[:, :, 1], X[:, :, 2]            # q, k, v: [B, t, h, d]
 
 
-def tri_attn(qkv, keep=None, p=0.0, av_kept=None, dt=F64, variant=None):
+def _tri_scores(q, k):
+    return stack([stack([(q[:, t] * k[:, u]).sum(-1) for u in range(2)], -1) for t in range(2)], -2)      # [B, 8, t, u]
+
+
+def tri_attn(qkv, keep=None, p=0.0, av_kept=None, dt=F64, variant=None, probs=None):
     """2-token, 8-head self-attention on rows (2b + t) of [2B, 1536] = [q | k | v]: scores q.k / 8, softmax over the 2 keys, dropout
     AFTER the softmax (keep [B, 8, 2, 2], scale float32(1 / (1 - p))), PV, mean over the two tokens.  -> dict of SV: obar [B, 512],
-    probs [B, 8, 2, 2] (before dropout), attn_w [B, 2, 2] (head mean after dropout), av_w [B, 2]."""
+    probs [B, 8, 2, 2] (before dropout), attn_w [B, 2, 2] (head mean after dropout), av_w [B, 2].  qkv: a tensor or an SV; with
+    `probs` (SV [B, 8, 2, 2]) given, the softmax stage is skipped and only v is taken from qkv (the staged reference of the fused kernel)."""
     B, q, k, v = _tri_split(qkv, dt)
     scale = drop_threshold(p)[1] if keep is not None else 1.0
     kf = None if keep is None else torch.as_tensor(keep).to(dt) * scale           # [B, 8, 2, 2], exact
-    s = stack([stack([(q[:, t] * k[:, u]).sum(-1) for u in range(2)], -1) for t in range(2)], -2)      # [B, 8, t, u]
-    if variant != "no_scale":
-        s = s.mulc(0.125)
-    if variant == "drop_before" and kf is not None:
-        s = s * SV(kf)
-    e = (s - s.max(-1)).exp()
-    prob = e / e.sum(-1, True)
+    if kf is not None and variant == "keep_swap":                                 # columns 4 h + 1 and 4 h + 2 exchanged
+        kf = kf.transpose(-1, -2)
+    if probs is None:
+        s = _tri_scores(q, k)
+        if variant != "no_scale":
+            s = s.mulc(0.125)
+        if variant == "drop_before" and kf is not None:
+            s = s * SV(kf)
+        e = (s - s.max(-1)).exp()
+        prob = e / e.sum(-1, True)
+    else:
+        prob = SV(probs.v.to(dt), probs.s.to(dt))
     d = prob if (kf is None or variant == "drop_before") else prob * SV(kf)
     # o_t = sum_u d[t, u] v_u ; obar = (o_0 + o_1) / 2
     w = d.sum(-2)                                                                   # [B, 8, u]
     o = SV(w.v[..., 0:1], w.s[..., 0:1]) * v[:, 0] + SV(w.v[..., 1:2], w.s[..., 1:2]) * v[:, 1]      # [B, 8, 64]
-    out = {"obar": o.mulc(0.5).reshape(B, 512), "probs": prob, "attn_w": d.sum(1).mulc(0.125)}
+    out = {"obar": (o if variant == "no_half" else o.mulc(0.5)).reshape(B, 512), "probs": prob, "attn_w": d.sum(1).mulc(0.125)}
     if keep is None:
         out["av_w"] = SV(torch.ones(B, 2, dtype=dt))
     else:
@@ -308,24 +320,100 @@ def tri_attn(qkv, keep=None, p=0.0, av_kept=None, dt=F64, variant=None):
     return out
 
 
-def tri_attn_bwd(qkv, dobar, probs, keep=None, p=0.0, dt=F64):
-    """backward of tri_attn from the SAVED probabilities, the keep mask fixed -> SV dqkv [2B, 1536]."""
+def tri_attn_bwd(qkv, dobar, probs, keep=None, p=0.0, dt=F64, variant=None):
+    """backward of tri_attn from the SAVED probabilities, the keep mask fixed -> SV dqkv [2B, 1536].  qkv: a tensor or an SV."""
     B, q, k, v = _tri_split(qkv, dt)
     scale = drop_threshold(p)[1] if keep is not None else 1.0
     kf = SV(torch.ones(B, 8, 2, 2, dtype=dt) if keep is None else torch.as_tensor(keep).to(dt) * scale)
     P = leaf(probs, dt).reshape(B, 8, 2, 2)
     go = leaf(dobar, dt).reshape(B, 8, 64).mulc(0.5)                                # d o_t = d obar / 2, both tokens
-    d = P * kf
+    d = P if variant == "dv_no_keep" else P * kf
     Dv = [(go * v[:, u]).sum(-1, True) for u in range(2)]                           # [B, 8, 1]
     dp = stack([cat([Dv[0], Dv[1]], -1)] * 2, -2) * kf                              # [B, 8, t, u]
     T = (P * dp).sum(-1, True)
-    ds = (P * (dp - SV(T.v.expand(-1, -1, -1, 2), T.s.expand(-1, -1, -1, 2)))).mulc(0.125)
+    ds = P * (dp - SV(T.v.expand(-1, -1, -1, 2), T.s.expand(-1, -1, -1, 2)))
+    if variant != "ds_no_scale":
+        ds = ds.mulc(0.125)
     el = lambda a, t, u: SV(a.v[:, :, t, u, None], a.s[:, :, t, u, None])           # [B, 8, 1]
     dq = [el(ds, t, 0) * k[:, 0] + el(ds, t, 1) * k[:, 1] for t in range(2)]
-    dk = [el(ds, 0, u) * q[:, 0] + el(ds, 1, u) * q[:, 1] for u in range(2)]
+    if variant == "dk_transposed":                                                  # ds[t][u] where ds[u][t] belongs
+        dk = [el(ds, u, 0) * q[:, 0] + el(ds, u, 1) * q[:, 1] for u in range(2)]
+    else:
+        dk = [el(ds, 0, u) * q[:, 0] + el(ds, 1, u) * q[:, 1] for u in range(2)]
     dv = [(el(d, 0, u) + el(d, 1, u)) * go for u in range(2)]
     rows = [cat([dq[t].reshape(B, 512), dk[t].reshape(B, 512), dv[t].reshape(B, 512)], -1) for t in range(2)]
     return stack(rows, 1).reshape(2 * B, 1536)
+
+
+# =========================================================================== in_proj + attention in one kernel (csrc/tri_fused.hip)
+# The kernel rounds q and k to bf16 in front of the scores and nothing else in front of P V or in the backward, so the reference is
+# staged, every stage taking the kernel's own earlier OUTPUT as an exact input:
+#   projection     qkv_out  against  sum_k x w + bias                                         (fused_proj)
+#   probabilities  probs    against  the clamped 2-key softmax of the STORED q, k             (fused_probs: 64 exact products a score)
+#   context        obar, attn_w, av_w  against  tri_attn(projection, probs = those reference probabilities)
+#   backward       dqkv     against  tri_attn_bwd(projection, dobar, the kernel's saved probs)
+LOG2E = 1.4426950408889634
+EXP2_CLAMP = 115.0
+
+
+def fused_weight_image(w_bits32):
+    """in_proj_weight as float32 bit patterns [1536][512] -> the head-major bf16 image (uint16 [1536][512]):
+    row 192 h + 96 wn + 32 part + dd  <-  row 512 part + 64 h + 32 wn + dd, every element through convert()."""
+    b = convert(np.asarray(w_bits32, dtype=np.uint32).reshape(1536, 512))
+    img = np.empty_like(b)
+    for h in range(8):
+        for wn in range(2):
+            for part in range(3):
+                src = 512 * part + 64 * h + 32 * wn
+                dst = 192 * h + 96 * wn + 32 * part
+                img[dst:dst + 32] = b[src:src + 32]
+    return img
+
+
+def fused_proj(x, w, bias, dt=F64, variant=None):
+    """x [2B, 512] (bf16 values), w [1536, 512] fp32 master weights (the kernel reads their bf16 image), bias [1536] fp32 -> SV [2B, 1536]
+    = sum_k x w + bias with the sum rule's scale sum_k |x w| + |bias| (+ |value|).  float32: the kernel's order as far as a CPU can
+    state it -- the accumulator starts at the bias and takes 16 steps of 32 exact products (a product of two bf16 numbers is exact
+    in float32; a step's sum is formed in float64 and rounded once)."""
+    X, W, b = torch.as_tensor(x).to(F64), bf16_round(torch.as_tensor(w).float()).to(F64), torch.as_tensor(bias).to(F64)
+    if variant == "no_bias":
+        b = torch.zeros_like(b)
+    elif variant == "bias_qk_swap":
+        b = torch.cat([b[512:1024], b[:512], b[1024:]])
+    elif variant == "wn_swap":                                                      # the two 32-dim halves of every head exchanged
+        W = W.reshape(3, 8, 2, 32, 512).flip(2).reshape(1536, 512)
+    if dt == F64:
+        v = X @ W.t() + b
+    else:
+        acc = b.to(dt).expand(X.shape[0], -1)
+        for c in range(0, 512, 32):
+            acc = (acc.to(F64) + X[:, c:c + 32] @ W[:, c:c + 32].t()).to(dt)
+        v = acc.to(F64)
+    s = X.abs() @ W.abs().t() + b.abs() + v.abs() + TINY
+    return SV(v.to(dt), s.to(dt))
+
+
+def fused_probs(tile, keep=None, p=0.0, dt=F64, variant=None):
+    """the kernel's softmax over two keys from the STORED q | k tile [2B, 1536] (bf16 values, exact):
+        p[t][t] = 1 / (1 + 2^min((s[t][1-t] - s[t][t]) log2(e) / 8, 115)),   p[t][1-t] = 1 - p[t][t], formed as 2^min(..) p[t][t]
+    (the difference from 1 would cancel in any precision once p[t][1-t] < 2^-53).  At the clamp the exponent is the constant 115.
+    -> SV [B, 8, 2, 2] and the largest |score gap| after the 1/8."""
+    B, q, k, _ = _tri_split(tile, dt)
+    s = _tri_scores(q, k)
+    if variant == "drop_before" and keep is not None:
+        s = s * SV(torch.as_tensor(keep).to(dt) * drop_threshold(p)[1])
+    own = stack([s[..., 0, 0], s[..., 1, 1]], -1)                                   # [B, 8, t]
+    oth = stack([s[..., 0, 1], s[..., 1, 0]], -1)
+    d = (oth - own).mulc(LOG2E if variant == "no_scale" else 0.125 * LOG2E)
+    gap = float(d.v.abs().max()) / LOG2E if d.v.numel() else 0.0
+    if variant != "no_clamp":
+        at = d.v >= EXP2_CLAMP
+        d = SV(torch.where(at, torch.full_like(d.v, EXP2_CLAMP), d.v), torch.where(at, torch.zeros_like(d.s), d.s))
+    ex = d.fn(torch.exp2, lambda x, y: y * 0.6931471805599453)
+    p_own = SV(torch.ones_like(ex.v)) / ex.addc(1.0)
+    p_oth = ex * p_own
+    row0, row1 = stack([p_own[..., 0], p_oth[..., 0]], -1), stack([p_oth[..., 1], p_own[..., 1]], -1)
+    return stack([row0, row1], -2), gap
 
 
 # =========================================================================== CrossModalAttention core
@@ -507,6 +595,80 @@ def tri_inputs(B, cls, bf16):
     if bf16:
         qkv, dobar = bf16_round(qkv), bf16_round(dobar)
     return qkv.contiguous(), dobar
+
+
+# ---- the fused kernel (tests/test_gpu_fused_attention.py).  One workgroup = 128 samples x one head: 127 / 128 / 129 sit either side of
+# one row tile, 641 = 6 tiles (48 workgroups), 1025 = 9 tiles, the last holding ONE sample (72 workgroups: 9 per XCD).
+FUSED_B = (1, 2, 127, 128, 129, 300, 641, 1025)
+FUSED_B_ALL_CLASSES = (1, 2, 129)
+FUSED_CLASSES = ("normal", "identical_tokens", "x_zero", "bias_zero", "bias_ramp", "saturated", "clamp_x4", "clamp_qbias40")
+FUSED_CLASSES_EVERY_B = ("normal", "clamp_x4")
+FUSED_DROPS = ((91, 5), (0, 0), (2 ** 40 + 7, 2 ** 33 + 1))                         # (seed, offset)
+FUSED_P = (0.0, 0.3, 0.9)
+# K per family.  tile, ctx (obar / attn_w / av_w) and bwd contain the projection, whose summation inside the MFMA a CPU cannot restate:
+# at least 8, the constant accepted for bf16 MFMA accumulation over sum |a w| (C_BOUND of tests/test_gpu_gemm_routes.py); else twice the
+# float32 CPU evaluation's worst ratio, rounded up to the next half (tests/test_cpu_rowkernel_ref.py measures and asserts: tile 0.95, probs 0.87, ctx 0.57, bwd 0.39).
+K.update({"fused_tile": 8.0, "fused_probs": 2.0, "fused_ctx": 8.0, "fused_bwd": 8.0})
+
+
+def fused_cases(B):
+    """(class, p, seed, offset) of batch B: every class at the small batches, two at every batch; eval and p = 0.3 / 0.9 each, the
+    (seed, offset) pairs in rotation so that every pair meets every p."""
+    classes = FUSED_CLASSES if B in FUSED_B_ALL_CLASSES else FUSED_CLASSES_EVERY_B
+    out = []
+    for ci, cls in enumerate(classes):
+        for pi, p in enumerate(FUSED_P):
+            seed, offset = FUSED_DROPS[(ci + pi + FUSED_B.index(B)) % 3]
+            out.append((cls, p, seed, offset))
+    return out
+
+
+_FUSED_MEMO = {}
+
+
+def fused_weights():
+    """fp32 master in_proj_weight [1536, 512] (std 0.06) and bias [1536] (std 0.2): one set for every case."""
+    if "w" not in _FUSED_MEMO:
+        g = _gen("fused weights", 15)
+        _FUSED_MEMO["w"] = (torch.randn(1536, 512, generator=g) * 0.06, torch.randn(1536, generator=g) * 0.2)
+    return _FUSED_MEMO["w"]
+
+
+def fused_inputs(B, cls):
+    """x [2B, 512] (bf16 values), bias [1536] fp32, dobar [B, 512] (bf16 values); the weights are fused_weights()[0].
+    With x of unit normals a score gap (after the 1/8) has a spread of about 2.6; x scaled by 2.5 puts the gaps at 20 .. 79 (saturated,
+    p down to 1e-34, below the clamp at 79.7), x scaled by 4 or +40 on head 0's q bias beyond 80 (the clamp)."""
+    if (B, cls) in _FUSED_MEMO:
+        return _FUSED_MEMO[(B, cls)]
+    g = _gen(B, cls, 16)
+    x = torch.randn(2 * B, 512, generator=g)
+    bias = fused_weights()[1].clone()
+    if cls == "identical_tokens":
+        x.view(B, 2, 512)[:, 1] = x.view(B, 2, 512)[:, 0]
+    elif cls == "x_zero":
+        x.zero_()
+    elif cls == "bias_zero":
+        bias.zero_()
+    elif cls == "bias_ramp":
+        bias = torch.arange(1536, dtype=torch.float32) / 64.0
+    elif cls == "saturated":
+        x *= 2.5
+    elif cls == "clamp_x4":
+        x *= 4.0
+    elif cls == "clamp_qbias40":
+        bias[:64] += 40.0
+    dobar = torch.randn(B, 512, generator=g)
+    _FUSED_MEMO[(B, cls)] = (bf16_round(x).contiguous(), bias.contiguous(), bf16_round(dobar))
+    return _FUSED_MEMO[(B, cls)]
+
+
+def fused_proj_of(B, cls, dt=F64):
+    """fused_proj of a case's inputs, computed once per (B, class, dtype) and left unchanged."""
+    key = (B, cls, dt, "proj")
+    if key not in _FUSED_MEMO:
+        x, bias, _ = fused_inputs(B, cls)
+        _FUSED_MEMO[key] = fused_proj(x, fused_weights()[0], bias, dt)
+    return _FUSED_MEMO[key]
 
 
 CROSS_B = (1, 3, 4, 5, 1027)

@@ -819,6 +819,15 @@ def _ln_bwd_args(**kw):
     ("mmdeer_dropout_mask", (1, -8, -8, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),     # a positive product
     ("mmdeer_dropout_mask", (1, -65536, -65536, 0.3, 0, 0, _FAKE, None), "dropout_mask: rows and cols must be >= 0"),   # ... of 2^32
     ("mmdeer_dropout_mask", (1, 8, 8, 0.3, 0, 0, None, None), "dropout_mask: out is NULL"),
+    # the fused kernel stores obar through a 32-bit range of B * 1024 bytes, and offset 2^31 is its "do not store" marker: B <= 2^21 - 1
+    ("mmdeer_trimodal_fused_fwd", (_FAKE, _FAKE, _FAKE, _FAKE, _FAKE, None, None, None, 2 ** 21, 0, 0.0, 0, 0, None),
+     "tri_fused_fwd: batch 2097152 exceeds 2097151"),
+    ("mmdeer_trimodal_fused_fwd", (_FAKE, _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, 2 ** 31 - 1, 1, 0.3, 0, 0, None),
+     "tri_fused_fwd: batch 2147483647 exceeds 2097151"),
+    ("mmdeer_trimodal_fused_bwd", (_FAKE, _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, 2 ** 21, 0, 0.0, 0, 0, None),
+     "tri_fused_bwd: batch 2097152 exceeds 2097151"),
+    ("mmdeer_trimodal_fused_fwd", (_FAKE, _FAKE, _FAKE, _FAKE, _FAKE, None, None, None, -1, 0, 0.0, 0, 0, None), "trimodal_fused_fwd: batch must be >= 0"),
+    ("mmdeer_trimodal_fused_bwd", (_FAKE, _FAKE, _FAKE, _FAKE, None, _FAKE, 4, 0, 0.0, 0, 0, None), "trimodal_fused_bwd: NULL"),
 ])
 def test_row_operators_refuse_before_any_launch(fn, args, words):
     """LayerNorm, the trimodal attention and the dropout mask check their shapes and pointers on the host: N = 0 would divide by zero in
@@ -837,6 +846,8 @@ def test_row_operators_accept_empty_problems_without_a_launch():
     assert lib.mmdeer_layernorm_fwd(None, None, None, None, None, None, None, 0, 256, 1, None) == 0
     assert lib.mmdeer_trimodal_attn_fwd(None, None, None, None, None, 0, 1, 1, 0.3, 0, 0, None) == 0
     assert lib.mmdeer_trimodal_attn_bwd(None, None, None, None, 0, 0, 1, 0.3, 0, 0, None) == 0
+    assert lib.mmdeer_trimodal_fused_fwd(None, None, None, None, None, None, None, None, 0, 1, 0.3, 0, 0, None) == 0
+    assert lib.mmdeer_trimodal_fused_bwd(None, None, None, None, None, None, 0, 1, 0.3, 0, 0, None) == 0
     assert lib.mmdeer_dropout_mask(1, 0, 8, 0.3, 0, 0, _FAKE, None) == 0 and lib.mmdeer_dropout_mask(1, 8, 0, 0.3, 0, 0, _FAKE, None) == 0
 
 

@@ -4,6 +4,8 @@
    same operation, and every hand-written backward agrees with autograd of its forward;
  * the same formulas in float32 on the CPU pass the comparison at half the constants K of rowkernel_ref.K over all cases of
    tests/test_gpu_rowkernels.py (the worst ratios are printed: pytest -s), and eleven seeded errors are rejected;
+ * the staged statement of the fused in_proj + attention kernel (csrc/tri_fused.hip) agrees with k_tri_fwd / k_tri_bwd behind a float64
+   in_proj, its float32 evaluation passes at K / 2 over all cases of tests/test_gpu_fused_attention.py, and twelve seeded errors are rejected;
  * the dropout draw, restated in uint32 arithmetic, is statistically a Bernoulli(thresh / 2^32) field without row, column, site, seed
    or offset structure (|z| < 6), and its threshold has the stated edges;
  * convert() is round-to-nearest-even.
@@ -82,6 +84,123 @@ def test_float32_side_rows_are_within_half_of_K(bf):
                           ("dgates", R.lstm_cell_t1_bwd(gates, dout, H, nd, F32).v, R.lstm_cell_t1_bwd(gates, dout, H, nd), bf)])
     print(f"\nfloat32 CPU worst ratios ({'bf16' if bf else 'fp32'} storage): cross_fwd {WORST['cross_fwd']:.2f}  "
           f"cross_bwd {WORST['cross_bwd']:.2f}  lstm {WORST['lstm']:.2f}")
+
+
+# =========================================================================== the fused in_proj + attention kernel (csrc/tri_fused.hip)
+def _fused_stages(B, cls, p, seed, offset, dt=F64, tile=None, variant=None):
+    """the staged statement of rowkernel_ref for one case -> dict of SV (tile, probs, obar, attn_w, av_w, dqkv) and the largest score
+    gap.  `tile`: the stored q|k|v the probabilities are formed from (the GPU test passes the kernel's; here the float32 evaluation's);
+    the backward takes the float32 probabilities formed from that tile as its saved ones."""
+    x, bias, dobar = R.fused_inputs(B, cls)
+    keep, av = R.tri_keep(B, p, seed, offset) if p > 0 else (None, None)
+    proj = R.fused_proj_of(B, cls, dt) if variant is None else R.fused_proj(x, R.fused_weights()[0], bias, dt, variant)
+    if tile is None:
+        tile = bf16(R.fused_proj_of(B, cls, F32).v)
+    saved = R.fused_probs(tile, keep, p, F32)[0].v
+    if variant == "unrounded_qk":
+        probs, gap = R.fused_probs(proj.v, keep, p, dt)
+    else:
+        probs, gap = R.fused_probs(tile, keep, p, dt, variant)
+    f = R.tri_attn(proj, keep, p, av, dt, variant, probs=probs)
+    out = {"tile": proj, "probs": probs, "obar": f["obar"], "attn_w": f["attn_w"], "av_w": f["av_w"],
+           "dqkv": R.tri_attn_bwd(proj, dobar, saved, keep, p, dt, variant)}
+    return out, gap
+
+
+_FUSED_FAMILY = {"tile": ("fused_tile", True), "probs": ("fused_probs", False), "obar": ("fused_ctx", True), "attn_w": ("fused_ctx", False),
+                 "av_w": ("fused_ctx", False), "dqkv": ("fused_bwd", True)}
+
+
+def test_float32_fused_attention_is_within_half_of_K():
+    """every case of tests/test_gpu_fused_attention.py: the float32 evaluation of the kernel's formula (the accumulator starts at the
+    bias and takes 16 steps of 32 exact products; q and k rounded to bf16 in front of the scores) passes at K / 2; the classes reach the
+    score gaps they are there for."""
+    gaps, floor = {}, {}
+    for B in R.FUSED_B:
+        for cls, p, seed, offset in R.fused_cases(B):
+            ref, gap = _fused_stages(B, cls, p, seed, offset)
+            f32, _ = _fused_stages(B, cls, p, seed, offset, F32)
+            gaps[cls] = max(gaps.get(cls, 0.0), gap)
+            for key, (family, bf) in _FUSED_FAMILY.items():
+                floor[family] = max(floor.get(family, 0.0), _measure(family, [(f"B={B} {cls} p={p} {key}", f32[key].v, ref[key], bf)]))
+            if cls in ("identical_tokens", "x_zero"):
+                assert bool((f32["probs"].v == 0.5).all())
+    print("\nfloat32 CPU worst ratios: " + "  ".join(f"{k} {v:.2f}" for k, v in floor.items()))
+    print("largest score gap after the 1/8: " + "  ".join(f"{k} {v:.1f}" for k, v in gaps.items()))
+    clamp_at = R.EXP2_CLAMP / R.LOG2E                                                            # 79.7
+    assert 60 < gaps["saturated"] < clamp_at - 1 and gaps["normal"] < 20 and gaps["bias_zero"] < 20
+    assert gaps["clamp_x4"] > 160 and gaps["clamp_qbias40"] > 160
+    # K: twice the float32 figure rounded up to the next half, at least 8 for the families that contain the projection
+    for family, at_least in (("fused_tile", 8.0), ("fused_probs", 0.0), ("fused_ctx", 8.0), ("fused_bwd", 8.0)):
+        assert R.K[family] == max(at_least, math.ceil(4 * floor[family]) / 2), (family, floor[family])
+
+
+FUSED_VARIANTS = [  # variant, the output that shows it, a case of the GPU file: (B, class, p)
+    ("no_bias", "tile", (2, "normal", 0.0)), ("bias_qk_swap", "tile", (2, "normal", 0.0)), ("wn_swap", "tile", (2, "normal", 0.0)),
+    ("unrounded_qk", "probs", (129, "normal", 0.0)), ("no_scale", "probs", (2, "normal", 0.0)), ("drop_before", "probs", (2, "normal", 0.3)),
+    ("keep_swap", "obar", (129, "normal", 0.3)), ("no_half", "obar", (2, "normal", 0.0)), ("no_clamp", "probs", (2, "clamp_x4", 0.0)),
+    ("dk_transposed", "dqkv", (2, "normal", 0.3)), ("dv_no_keep", "dqkv", (2, "normal", 0.3)), ("ds_no_scale", "dqkv", (2, "normal", 0.0))]
+
+
+@pytest.mark.parametrize("variant,key,case", FUSED_VARIANTS, ids=[v[0] for v in FUSED_VARIANTS])
+def test_seeded_fused_attention_errors_are_rejected(variant, key, case):
+    """twelve errors the kernel could hold, each shown by one output on a case of the GPU file, at the K the GPU test uses; the float32
+    evaluation of the right formula passes there.  `unrounded_qk` proves that the comparison pins the rounding point in front of the
+    scores.  (v rounded to bf16 in front of P V is NOT on the list: it moves obar by less than obar's own bf16 cell.)"""
+    B, cls, p = case
+    seed, offset = next((s, o) for c, pp, s, o in R.fused_cases(B) if c == cls and pp == p)
+    family, bf = _FUSED_FAMILY[key]
+    ref, _ = _fused_stages(B, cls, p, seed, offset)
+    f32, _ = _fused_stages(B, cls, p, seed, offset, F32)
+    bad, _ = _fused_stages(B, cls, p, seed, offset, variant=variant)
+    store = (lambda t: bf16(t)) if bf else (lambda t: t.float())
+    assert not R.rejects(key, store(f32[key].v), ref[key], R.K[family], bf)
+    assert R.rejects(key, store(bad[key].v), ref[key], R.K[family], bf)
+
+
+@pytest.mark.parametrize("p", [0.0, 0.3])
+def test_fused_attention_stages_agree_with_the_oracle_and_with_autograd(p):
+    """the staged statement against oracle.deer_oracle: k_tri_fwd / k_tri_bwd behind their float64 in_proj (the oracle rounds q and k
+    to bf16 itself: the tile handed to fused_probs is that rounding); the restated backward on an SV is autograd of the forward."""
+    B, cls = 5, "normal"
+    g = R._gen("oracle tie", 17)
+    x, dobar = R.bf16_round(torch.randn(2 * B, 512, generator=g)).double(), R.bf16_round(torch.randn(B, 512, generator=g)).double()
+    w, bias = R.fused_weights()
+    keep, av = R.tri_keep(B, p, 1234, 5) if p > 0 else (None, None)
+    proj = R.fused_proj(x, w, bias)
+    assert _rel(proj.v, x @ R.bf16_round(w).double().t() + bias.double()) < 1e-14
+    assert bool((proj.s >= (x.abs() @ R.bf16_round(w).double().abs().t() + bias.double().abs())).all())
+    probs, gap = R.fused_probs(bf16(proj.v))
+    prob_o, obar_o = O.k_tri_fwd(x.view(B, 2, 512), w.double(), bias.double(), mask=keep, p=p)
+    assert gap < 20 and _rel(probs.v, prob_o) < 1e-12
+    f = R.tri_attn(proj, keep, p, av, probs=probs)
+    assert float(((f["obar"].v - obar_o).abs() - 2.0 ** -8 * f["obar"].v.abs()).max()) <= 0          # the oracle's obar is bf16-rounded
+    dq_o = O.k_tri_bwd(x.view(B, 2, 512), w.double(), bias.double(), dobar, prob_o, mask=keep, p=p).reshape(2 * B, 1536)
+    mine = R.tri_attn_bwd(proj, dobar, prob_o, keep, p)
+    assert float(((mine.v - dq_o).abs() - 2.0 ** -8 * mine.v.abs()).max()) <= 0
+    # autograd through the SV path (the unstaged forward: its own softmax of the unrounded q, k, whose probabilities are the saved ones)
+    leaf = proj.v.clone().requires_grad_(True)
+    ff = R.tri_attn(R.SV(leaf, proj.s), keep, p, av)
+    (ff["obar"].v * dobar).sum().backward()
+    assert _rel(R.tri_attn_bwd(proj, dobar, ff["probs"].v.detach(), keep, p).v, leaf.grad) < 1e-12
+    # the clamp: a losing key keeps 2^-115, the winner 1; without it the true probability is far below
+    t = torch.zeros(2, 1536)
+    t[0, 0], t[1, 0], t[0, 512], t[1, 512] = 32.0, -32.0, -32.0, 32.0                             # head 0: q_t . k_t = -1024, gap 256
+    pc = R.fused_probs(t)[0].v[0, 0]
+    assert pc[0, 1] == 1.0 and pc[1, 0] == 1.0 and pc[0, 0] == 2.0 ** -115 and pc[1, 1] == 2.0 ** -115
+    assert R.fused_probs(t, variant="no_clamp")[0].v[0, 0, 0, 0] < 1e-100
+    t[0, 512], t[1, 512] = 32.0, -32.0                                                            # q_t . k_t = +1024
+    pw = R.fused_probs(t)[0].v[0, 0]                                                              # the winner's side is not clamped
+    assert pw[0, 0] == 1.0 and 0 < pw[0, 1] < 1e-100
+
+
+def test_fused_weight_image_restatement_is_the_documented_permutation():
+    """row 192 h + 96 wn + 32 part + dd <- row 512 part + 64 h + 32 wn + dd, a bijection on the 1536 rows, values through convert()."""
+    w = torch.arange(1536 * 512, dtype=torch.float32).reshape(1536, 512) * 0.5 + 1.0
+    bits = w.view(torch.int32).numpy().view(np.uint32)
+    img = torch.from_numpy(R.fused_weight_image(bits).view(np.int16)).view(torch.bfloat16)
+    want = w.bfloat16().view(3, 8, 2, 32, 512).permute(1, 2, 0, 3, 4).reshape(1536, 512)
+    assert torch.equal(img.view(torch.int16), want.view(torch.int16))
 
 
 # =========================================================================== seeded errors

@@ -40,6 +40,7 @@ constexpr int TF_SCR = TF_BM * TF_CROW;                        // scratch for th
 constexpr int TF_FLAGS = cmax(TF_RING, TF_SCR + 2 * TF_BM * 8);   // 8 words behind everything the DMA or the epilogue writes
 constexpr int TF_LDS = TF_FLAGS + 64;
 static_assert(TF_LDS <= 160 * 1024, "LDS budget");
+constexpr int TF_MAX_BATCH = (1 << 21) - 1;                    // B * TF_E * 2 bytes of obar < 2^31 (mmdeer.h states it)
 
 // the other token's value: lanes li and li ^ 1 (quad_perm [1, 0, 3, 2])
 __device__ __forceinline__ float tok_swap(float v) { return dpp_read<0xB1>(v); }
@@ -507,6 +508,9 @@ int launch_pack_qkv_headmajor(const float* in_proj_weight, void* dst_bf16, hipSt
 int launch_tri_fused_fwd(const void* xtok, const void* whm, const float* bias, void* obar, float* probs, void* qkv_out, int B,
                          int train, const DropCtx& dc, hipStream_t s) {
   if (B == 0) return 0;
+  // obar and probs are stored through 32-bit buffer ranges (B * 1024 and B * 128 bytes, formed as int) at 32-bit byte offsets, and
+  // offset 2^31 is the "do not store" marker: the range must end below it
+  MMDEER_CHECK(B <= TF_MAX_BATCH, "tri_fused_fwd: batch %d exceeds %d (32-bit buffer ranges of obar / probs)", B, TF_MAX_BATCH);
   MMDEER_CHECK(((uintptr_t)xtok % 16) == 0 && ((uintptr_t)whm % 16) == 0 && ((uintptr_t)obar % 8) == 0 && ((uintptr_t)bias % 16) == 0,
                "tri_fused_fwd: misaligned operand");
   TriFusedArgs a{};
@@ -525,6 +529,9 @@ int launch_tri_fused_fwd(const void* xtok, const void* whm, const float* bias, v
 int launch_tri_fused_bwd(const void* xtok, const void* whm, const float* bias, const void* dobar, const float* probs, void* dqkv,
                          int B, int train, const DropCtx& dc, hipStream_t s) {
   if (B == 0) return 0;
+  // the backward addresses with 64-bit pointers (its row index 2 B + 255 fits an int up to B = 2^30 - 128), but its probs come from a
+  // forward of the same batch: one ceiling for the pair
+  MMDEER_CHECK(B <= TF_MAX_BATCH, "tri_fused_bwd: batch %d exceeds %d (the forward's ceiling)", B, TF_MAX_BATCH);
   MMDEER_CHECK(((uintptr_t)xtok % 16) == 0 && ((uintptr_t)whm % 16) == 0 && ((uintptr_t)dobar % 8) == 0 && ((uintptr_t)dqkv % 16) == 0,
                "tri_fused_bwd: misaligned operand");
   TriFusedArgs a{};
