@@ -2,10 +2,12 @@
 (librosa / cv2 / BERT) are out of scope; the pre-extracted-feature branch of EnhancedAudioEncoder (row a14) is real,
 and EnhancedTextEncoder is the reference's no-BERT configuration on token ids and a mask (mmdeer.text; its
 ``forward_embeddings`` takes the caller's own contextual embeddings in place of BERT's last_hidden_state).  EnhancedVideoEncoder is
-the reference's encoder downstream of its spatial CNN, on (B, T, 512) per-frame features (mmdeer.video; frame tensors raise)."""
+the reference's encoder downstream of its spatial CNN, on (B, T, 512) per-frame features (mmdeer.video; frame tensors raise);
+FrameVideoEncoder is the same encoder from frames, its Conv2d backbone run on HIP, forward only (mmdeer.frames)."""
 from mmdeer.side import EnhancedAudioEncoder  # noqa: F401
 from mmdeer.text import TemporalTextEncoder as EnhancedTextEncoder  # noqa: F401
 from mmdeer.video import TemporalVideoEncoder as EnhancedVideoEncoder  # noqa: F401
+from mmdeer.frames import FrameVideoEncoder  # noqa: F401
 
 
 def _out_of_scope(name):

@@ -60,6 +60,12 @@ VIDEO_CONSTANTS, _VIDEO_CLASSES, VIDEO_SYMBOLS = _header.parse(_header.read(_hea
 globals().update({cls.__name__: cls for cls in _VIDEO_CLASSES.values()})    # Conv3TimeArgs, BnTimeArgs
 VIDEO_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _VIDEO_CLASSES.items()}
 BN_TIME_SCRATCH = VIDEO_CONSTANTS["BN_TIME_SCRATCH"]
+# include/mmdeer_frames.h, the companion header of the Conv2d backbone on frames: the same derivation again
+_FRAME_NAMES = {"mmdeer_conv2d_args": "Conv2dArgs", "mmdeer_bn2d_args": "Bn2dArgs"}
+FRAME_CONSTANTS, _FRAME_CLASSES, FRAME_SYMBOLS = _header.parse(_header.read(_header.FRAMES_HEADER_PATH), _FRAME_NAMES, {})
+globals().update({cls.__name__: cls for cls in _FRAME_CLASSES.values()})    # Conv2dArgs, Bn2dArgs
+FRAME_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _FRAME_CLASSES.items()}
+BN2D_SCRATCH = FRAME_CONSTANTS["BN2D_SCRATCH"]
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -74,7 +80,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -108,7 +114,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         lib = bind(C.CDLL(path), require_all=True)
         if lib.mmdeer_abi_version() != ABI_VERSION:
             raise RuntimeError("libmmdeer_hip.so ABI version mismatch")
-        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
+        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
             if lib.mmdeer_sizeof(cname.encode()) != C.sizeof(cls):
                 raise RuntimeError(f"mmdeer: ctypes layout of mmdeer_{cname} ({C.sizeof(cls)} bytes) differs from the library's "
                                    f"({lib.mmdeer_sizeof(cname.encode())})")

@@ -8,6 +8,7 @@
 
 #include "../../include/mmdeer.h"
 #include "../../include/mmdeer_video.h"
+#include "../../include/mmdeer_frames.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -539,6 +540,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(stackb_attn_train_args) SZ(stackb_attn_args) SZ(stackb_forward_args) SZ(stackb_weights) SZ(softmax_mix_args)
   SZ(lstm_seq_args) SZ(temporal_pool_args) SZ(evidence_tail_args) SZ(token_embed_args) SZ(token_pool_args) SZ(token_stats_args)
   SZ(conv3_time_args) SZ(bn_time_args)   // mmdeer_video.h
+  SZ(conv2d_args) SZ(bn2d_args)          // mmdeer_frames.h
 #undef SZ
   return -1;
 }

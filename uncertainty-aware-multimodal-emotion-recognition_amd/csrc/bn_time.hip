@@ -20,33 +20,13 @@
 // every digit of the variance of a channel whose mean is large against its spread; this form does not.
 // Backward: the same block structure for the partial sums of g and g * xhat, a fold launch, then dx.
 #include "../../include/mmdeer_video.h"
-#include "elem.h"
+#include "bn_fold.h"
 
 namespace mmdeer {
 namespace {
 
 constexpr int BN_C = 512;          // channels
-constexpr int BN_MAXBLK = 1024;    // row blocks at most; scratch = BN_MAXBLK * 2 * BN_C floats
-constexpr int BN_FOLD_CH = 8, BN_FOLD_SEG = 32;   // fold kernels: channels per workgroup, block segments per channel
 static_assert(BN_MAXBLK * 2 * BN_C == MMDEER_BN_TIME_SCRATCH, "scratch holds two per-channel partials per row block");
-
-// rows per block: at least 32, even, and at most BN_MAXBLK blocks
-inline int bn_rows_per_block(int R) {
-  int rpb = (R + BN_MAXBLK - 1) / BN_MAXBLK;
-  if (rpb < 32) rpb = 32;
-  return (rpb + 1) & ~1;
-}
-inline int bn_blocks(int R) { const int rpb = bn_rows_per_block(R); return (R + rpb - 1) / rpb; }
-
-// Chan's merge of (na, ma, M2a) with (nb, mb, M2b); nb may be 0
-__device__ __forceinline__ void chan_merge(float na, f32x4& ma, f32x4& M2a, float nb, const f32x4& mb, const f32x4& M2b) {
-  const float n = na + nb;
-  if (nb == 0.f) return;
-  const float fb = nb / n, fab = na * fb;
-  const f32x4 d = mb - ma;
-  ma += d * fb;
-  M2a += M2b + d * d * fab;
-}
 
 template <bool F32>
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(mmdeer_bn_time_args a, int rpb) {
@@ -80,35 +60,9 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(mmdeer_bn_time_ar
   }
 }
 
-// fold of the blocks' (count, mean, M2): see the head of this file
+// fold of the blocks' (count, mean, M2): see the head of this file and bn_fold.h
 __global__ __launch_bounds__(256) void bn_stats_final_kernel(mmdeer_bn_time_args a, int rpb, int nblk) {
-  __shared__ float sn[BN_FOLD_SEG][BN_FOLD_CH], sm[BN_FOLD_SEG][BN_FOLD_CH], sM2[BN_FOLD_SEG][BN_FOLD_CH];
-  const int cl = threadIdx.x % BN_FOLD_CH, seg = threadIdx.x / BN_FOLD_CH, c = blockIdx.x * BN_FOLD_CH + cl;
-  const int per = (nblk + BN_FOLD_SEG - 1) / BN_FOLD_SEG, b0 = seg * per, b1 = min(b0 + per, nblk);
-  float n = 0.f, mean = 0.f, M2 = 0.f;
-  auto merge = [&](float nb, float mb, float M2b) __attribute__((always_inline)) {
-    if (nb == 0.f) return;
-    const float nn = n + nb, fb = nb / nn, d = mb - mean;
-    mean += d * fb;
-    M2 += M2b + d * d * (n * fb);
-    n = nn;
-  };
-#pragma unroll 4
-  for (int b = b0; b < b1; ++b)
-    merge((float)min(rpb, a.R - b * rpb), a.scratch[(long long)b * 2 * BN_C + c], a.scratch[(long long)b * 2 * BN_C + BN_C + c]);
-  sn[seg][cl] = n; sm[seg][cl] = mean; sM2[seg][cl] = M2;
-  __syncthreads();
-  if (seg != 0) return;
-  for (int s = 1; s < BN_FOLD_SEG; ++s) merge(sn[s][cl], sm[s][cl], sM2[s][cl]);
-  const float var = M2 / (float)a.R;
-  a.mean[c] = mean;
-  a.rstd[c] = 1.f / sqrtf(var + a.eps);
-  if (a.running_mean) {
-    const float unbiased = a.R > 1 ? M2 / (float)(a.R - 1) : var;
-    a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * mean;
-    a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * unbiased;
-    if (c == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
-  }
+  bn_fold_stats(a, a.R, BN_C, rpb, nblk);
 }
 
 // mean and rstd of this thread's four channels (running != 0: `rstd` holds the running variance)
@@ -118,10 +72,6 @@ __device__ __forceinline__ void bn_load_stats(const mmdeer_bn_time_args& a, int 
   if (a.running) {
     rstd = f32x4{1.f / sqrtf(rstd.x + a.eps), 1.f / sqrtf(rstd.y + a.eps), 1.f / sqrtf(rstd.z + a.eps), 1.f / sqrtf(rstd.w + a.eps)};
   }
-}
-
-__device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) {
-  return f32x4{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w)};
 }
 
 template <bool F32>

@@ -87,6 +87,29 @@ __device__ __forceinline__ RTile tile_gload(const ST* base, const ST* safe, long
   return t;
 }
 
+// Row origins of a gathered A operand (conv2d.hip): row (tid >> 3) + 32 j of this thread's tile starts o<j> elements behind the
+// tile's origin instead of (row) * ld.  The origins of rows beyond rows_valid are never used: those rows read `safe`.
+struct RowGather { long long o0, o1, o2, o3; };
+
+// tile_gload of a row-major operand whose rows are gathered
+template <typename CT, typename ST, int ROWS, bool VEC16>
+__device__ __forceinline__ RTile tile_gload_rows(const ST* base, const ST* safe, const RowGather& rg, int rows_valid, int k0, int K, int tid) {
+  constexpr int EPC = Elem<CT>::EPC;
+  RTile t;
+  t.r0 = t.r1 = t.r2 = t.r3 = zero4();
+  const int kc = tid & 7, ke = k0 + kc * EPC, rem = K - ke;
+  const int kvalid = rem >= EPC ? EPC : (rem > 0 ? rem : 0);
+  const int row = tid >> 3;
+  const ST* p = base + ke;
+  t.r0 = load_chunk<CT, ST, VEC16>(p + rg.o0, safe, row < rows_valid ? kvalid : 0);
+  if constexpr (ROWS >= 64) t.r1 = load_chunk<CT, ST, VEC16>(p + rg.o1, safe, row + 32 < rows_valid ? kvalid : 0);
+  if constexpr (ROWS >= 128) {
+    t.r2 = load_chunk<CT, ST, VEC16>(p + rg.o2, safe, row + 64 < rows_valid ? kvalid : 0);
+    t.r3 = load_chunk<CT, ST, VEC16>(p + rg.o3, safe, row + 96 < rows_valid ? kvalid : 0);
+  }
+  return t;
+}
+
 // Zero the part of a register tile that lies beyond K (only called for a partial last K-tile).
 template <typename CT, bool TRANS>
 __device__ __forceinline__ RTile tile_ktail_mask(RTile t, int k0, int K, int tid) {
@@ -219,6 +242,19 @@ struct FastLoader {
       step = (long long)KT * ld;
     }
   }
+  // init for a row-major operand whose rows are gathered (RowGather)
+  __device__ __forceinline__ void init_rows(const void* opnd, long long off, const RowGather& rg, int rows_valid, int k0, int tid) {
+    static_assert(!TRANS, "gathered rows: row-major operands only");
+    const ST* base = reinterpret_cast<const ST*>(opnd) + off;
+    const ST* safe = reinterpret_cast<const ST*>(opnd);
+    const int row = tid >> 3;
+    const long long ko = k0 + (tid & 7) * EPC;
+    p0 = (row < rows_valid ? base + rg.o0 : safe) + ko;
+    p1 = (row + 32 < rows_valid ? base + rg.o1 : safe) + ko;
+    p2 = (row + 64 < rows_valid ? base + rg.o2 : safe) + ko;
+    p3 = (row + 96 < rows_valid ? base + rg.o3 : safe) + ko;
+    step = KT;
+  }
   __device__ __forceinline__ u32x4 ld1(const ST* p) const {
     if constexpr (sizeof(CT) == 4) {
       return *reinterpret_cast<const u32x4*>(p);
@@ -262,8 +298,10 @@ struct KArgs {
 // then -- and only then -- wait for the loads and store them to the other LDS buffer; one barrier per K-tile.
 // Whole K-tiles of regular tiles go through the FastLoader; a ragged last K-tile (K = 84, odd batch sizes as the
 // reduction dimension) and irregular edge tiles take the generic clamped loader.
-template <typename CT, int BM, int BN, bool TA, bool TB, int AM, int BMODE, int TM, int TN>
-__device__ __forceinline__ void k_loop(const KArgs& ka, unsigned char* lds, f32x4 (&acc)[TM][TN], float (&bsum)[TM]) {
+// AG: the rows of A are gathered -- row j of the tile starts ag.o<j> elements behind A + a_off (ka.lda is unused).
+template <typename CT, int BM, int BN, bool TA, bool TB, int AM, int BMODE, int TM, int TN, bool AG = false>
+__device__ __forceinline__ void k_loop(const KArgs& ka, unsigned char* lds, f32x4 (&acc)[TM][TN], float (&bsum)[TM],
+                                       const RowGather& ag = RowGather{}) {
   constexpr int KT = Elem<CT>::KT;
   constexpr int WTM = BM / 2, WTN = BN / 2;
   constexpr int A_BYTES = BM * LDS_ROW, B_BYTES = BN * LDS_ROW, STAGE = A_BYTES + B_BYTES;
@@ -279,7 +317,8 @@ __device__ __forceinline__ void k_loop(const KArgs& ka, unsigned char* lds, f32x
   auto gload_generic = [&](int k0) __attribute__((always_inline)) {
     const AST* ab = reinterpret_cast<const AST*>(ka.A);
     const BST* bb = reinterpret_cast<const BST*>(ka.B);
-    ra = tile_gload<CT, AST, BM, TA, SrcOf<CT, AM>::V16>(ab + ka.a_off, ab, ka.lda, ka.a_rows, k0, K, tid);
+    if constexpr (AG) ra = tile_gload_rows<CT, AST, BM, SrcOf<CT, AM>::V16>(ab + ka.a_off, ab, ag, ka.a_rows, k0, K, tid);
+    else ra = tile_gload<CT, AST, BM, TA, SrcOf<CT, AM>::V16>(ab + ka.a_off, ab, ka.lda, ka.a_rows, k0, K, tid);
     rb = tile_gload<CT, BST, BN, TB, SrcOf<CT, BMODE>::V16>(bb + ka.b_off, bb, ka.ldb, ka.b_rows, k0, K, tid);
   };
   auto lstore = [&](int buf) __attribute__((always_inline)) {
@@ -322,7 +361,8 @@ __device__ __forceinline__ void k_loop(const KArgs& ka, unsigned char* lds, f32x
   FastLoader<CT, BM, TA, AM> fa_;
   FastLoader<CT, BN, TB, BMODE> fb_;
   if (kt0 < kfull) {
-    fa_.init(ka.A, ka.a_off, ka.lda, ka.a_rows, kt0 * KT, tid);
+    if constexpr (AG) fa_.init_rows(ka.A, ka.a_off, ag, ka.a_rows, kt0 * KT, tid);
+    else fa_.init(ka.A, ka.a_off, ka.lda, ka.a_rows, kt0 * KT, tid);
     fb_.init(ka.B, ka.b_off, ka.ldb, ka.b_rows, kt0 * KT, tid);
     ra = fa_.load();
     rb = fb_.load();
