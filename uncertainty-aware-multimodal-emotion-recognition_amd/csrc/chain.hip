@@ -31,17 +31,19 @@
 // What bounds it (cycle stamps of workgroup 0, tools/chain_stamps.py, tools/sb_chain_stamps.py; B = 4096, 256 workgroups): for wide
 // layers the weight stream into the CU -- every workgroup streams ALL weights of the chain (2.2 MB for F9..F17) for its 16 rows at
 // ~320 cycles per 16-KiB stage = 51 B/clk per CU (tools/probes/wstream.hip: 54 with plain register loads from a fragment-major image,
-// 39-44 through an LDS-DMA ring) --; for 256-wide layers the layer ends: decode of the next table record ~1.0k cycles, barrier skew
-// between the two waves of a SIMD ~1.5k, LayerNorm ~1.9k, and the restart of the 4-deep ring behind every layer end (eight stages in
-// 4.5k cycles instead of 2.6k).  One workgroup per 16 rows also means the launch only pays while the chip holds all workgroups at
-// once: stackc.hip uses 16-sample workgroups for B <= 4096, 32-sample workgroups up to 8192 and the separate launches above.
+// 39-44 through an LDS-DMA ring) --; for 256-wide layers the layer ends: the next table record ~0.45k cycles (scalar loads; ~1.0k
+// while it was a vector read from LDS made scalar), barrier skew between the two waves of a SIMD ~1.5k, LayerNorm ~1.9k, and the
+// restart of the 4-deep ring behind every layer end (eight stages in 4.5k cycles instead of 2.6k).  One workgroup per 16 rows also
+// means the launch only pays while the chip holds all workgroups at once: stackc.hip uses 16-sample workgroups for B <= 4096,
+// 32-sample workgroups up to 8192 and the separate launches above.
 // Measured dead ends (rounds 3-4): the LDS-DMA weight ring (36-45 B/clk) and a seventh slot of it; re-reading the activation fragments
 // from LDS at every stage while the weights also went through LDS; two stages per barrier; the segment tables from the kernel
 // arguments by dependent scalar loads record after record (~1000 cycles each); weights into registers from the ROW-MAJOR copy
 // (16 lanes x 64 bytes per request: 22 B/clk); a tile's epilogue inside the first stage of the next tile; deferring the stash /
 // LayerNorm stores into the next layer's first tile; an 8-deep ring (chain_depth = 8: parity-green, slower -- 137 spilled VGPRs at
-// 192 compiler-visible registers); both LayerNorm-backward fold passes behind one barrier pair (no change); the dropout step counter
-// as an untracked load and the first record from scalar loads (+3 us per step).
+// 192 compiler-visible registers); both LayerNorm-backward fold passes behind one barrier pair (no change -- and none again as one
+// pass through 64 KiB of scratch); the dropout step counter as an untracked load and the first record from scalar loads (+3 us per
+// step).
 //
 // Backward chains (dX = dY W through fragment-major images of W^T) use the same kernel: a segment's epilogue can multiply by the
 // (Y > 0) * scale mask of the forward layer below (four mask values per lane, requested by an untracked asm load before the tile's
@@ -128,9 +130,11 @@ __device__ __forceinline__ unsigned chain_drop_key(unsigned long long seed, unsi
   return k;
 }
 
-// ---- kernel-side tables (derived by launch_chain).  They are copied into LDS by one parallel vector load at kernel start
-// and read from there: the kernel walks them record after record, and as dependent scalar loads from the kernarg segment
-// each record was a ~1000-cycle round trip.  All fields are dwords (a sub-dword field would be a vector load).
+// ---- kernel-side tables (derived by launch_chain).  They are copied into LDS by one parallel vector load at kernel start;
+// the weight stream's cursor and segment 0 read them from there (as DEPENDENT scalar loads from the kernarg segment, at the
+// point of use, each record was a ~1000-cycle round trip).  The segment loop takes its records from the kernarg segment all
+// the same, by scalar loads issued a layer end ahead of their use (chain_body).  All fields are dwords (a sub-dword field would
+// be a vector load).
 struct ChainSegK {           // one GEMM segment = ntiles column tiles of `nkt` weight stages each; 96 bytes
   const bf16_t* W;           // fragment-major image of the segment's [N][K] matrix
   int in_aux, nkt;           // in_aux: the segment multiplies the second input panel; stages per tile: K / 64
@@ -810,41 +814,41 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
     }
   };
 
-  // The table record of a segment (its end part included) is requested while the segment BEFORE it winds down -- in front of the
-  // layer end's barrier, where half the waves wait for the other half anyway -- and only converted to scalars here: read at the top
-  // of the loop and again behind the barrier, the three dependent LDS round trips and their waits were ~1500 cycles per layer.
+  // A table record reaches the loop as wave-uniform scalars, in two parts.  The segment part (ChainSegK, plus the fields of the end
+  // part that a LayerNorm-backward prefetch needs at the top of the segment) is read one segment AHEAD, the end part (ChainEndK) of
+  // the current segment where its layer ends: both by scalar loads from the kernel-argument segment (constant address space, the
+  // index is wave-uniform), issued in front of the layer end's barrier, where half the waves wait for the other half anyway, and
+  // covered by that barrier's wait.  Segment 0's first part alone comes from the LDS copy of the tables (a vector read, lane 0 made
+  // scalar: as scalar loads it would be live across the NIG prologue).  Read from LDS for every segment, a record was eleven vector
+  // reads and ~45 v_readfirstlane in every workgroup: 940-1016 cycles between "layer end done" and "segment decoded".
   int half = 0;        // D = 8: the granule of the ring the next tile starts in
-  u32x4 R[11];
-  auto fetch_rec = [&](int si_) __attribute__((always_inline)) {
-    const u32x4* rec = reinterpret_cast<const u32x4*>(tab + si_ * SEG_BYTES);
+  constexpr int SEG_DW = (int)sizeof(ChainSegK) / 4;      // dwords 0..23 of a record: ChainSegK; 24..43: ChainEndK
+  static_assert(SEG_DW == 24 && __builtin_offsetof(ChainEndK, mean) == 24 && __builtin_offsetof(ChainEndK, nout) == 44 &&
+                __builtin_offsetof(ChainEndK, has_ln) == 52 && __builtin_offsetof(ChainEndK, lnb_y) == 56, "record dwords named below");
+  unsigned rs[SEG_DW];      // the current segment's ChainSegK
+  unsigned rl[8];           // of its ChainEndK: mean, rstd (record dwords 30..33), nout (35), has_ln (37), lnb_y (38, 39)
+  {
+    const u32x4* rec = reinterpret_cast<const u32x4*>(tab);
 #pragma unroll
-    for (int k = 0; k < 11; ++k) R[k] = rec[k];
-  };
-  fetch_rec(0);
+    for (int k = 0; k < SEG_DW / 4; ++k) {
+      const u32x4 v = rec[k];
+      rs[4 * k] = (unsigned)sc(v.x); rs[4 * k + 1] = (unsigned)sc(v.y); rs[4 * k + 2] = (unsigned)sc(v.z); rs[4 * k + 3] = (unsigned)sc(v.w);
+    }
+    const u32x4 v7 = rec[7], v8 = rec[8], v9 = rec[9];
+    rl[0] = (unsigned)sc(v7.z); rl[1] = (unsigned)sc(v7.w); rl[2] = (unsigned)sc(v8.x); rl[3] = (unsigned)sc(v8.y);
+    rl[4] = (unsigned)sc(v8.w); rl[5] = (unsigned)sc(v9.y); rl[6] = (unsigned)sc(v9.z); rl[7] = (unsigned)sc(v9.w);
+  }
+  auto p64 = [](unsigned lo, unsigned hi) -> unsigned long long { return ((unsigned long long)hi << 32) | lo; };
   for (int si = 0; si < nseg; ++si) {
-    const u32x4 q0 = R[0], q1 = R[1], q2 = R[2], q3 = R[3], q4 = R[4], q5 = R[5];
-    const u32x4 e0 = R[6], e1 = R[7], e2 = R[8], e3 = R[9], e4 = R[10];
-    const int nkt = sc(q0.w), kb = sc(q1.y), endi = sc(q1.z);
+    const int nkt = (int)rs[3], kb = (int)rs[5], endi = (int)rs[6];
     SegCtl sg;
-    sg.ntiles = sc(q1.x); sg.N = sc(q1.w); sg.in_aux = sc(q0.z);
-    sg.vec_off = sc(q2.x); sg.dcol_off = sc(q2.y); sg.nout_off = sc(q2.z); sg.site = sc(q2.w);
-    sg.shift = sc(q3.x); sg.relu = sc(q3.y); sg.fold = sc(q3.z);
-    const int mb = sc(q3.w);
-    sg.rows_out = sc(q4.x); sg.kin_off = sc(q4.y);
-    sg.mask_scale = __uint_as_float((unsigned)sc(q4.z)); sg.has_bias = sc(q4.w);
-    sg.mask_y = reinterpret_cast<const bf16_t*>(sp(q5.x, q5.y)); sg.ld_mask = sc(q5.z); sg.mask_col0 = sc(q5.w);
-    // the end part, as scalars, now: stash / LayerNorm pointers, widths, kind
-    bf16_t* const stash = reinterpret_cast<bf16_t*>(sp(e0.x, e0.y));
-    bf16_t* const end_xln = reinterpret_cast<bf16_t*>(sp(e0.z, e0.w));
-    float* const end_out32 = reinterpret_cast<float*>(sp(e1.x, e1.y));
-    float* const end_mean = reinterpret_cast<float*>(sp(e1.z, e1.w));
-    float* const end_rstd = reinterpret_cast<float*>(sp(e2.x, e2.y));
-    const int ld_stash = sc(e2.z), nout = sc(e2.w);
-    const int gb_off = sc(e3.x), has_ln = endi >= 0 ? sc(e3.y) : 0;
-    const bf16_t* const end_lnb_y = reinterpret_cast<const bf16_t*>(sp(e3.z, e3.w));
-    const float lms = __uint_as_float((unsigned)sc(e4.x));
-    const int res_split = endi >= 0 ? sc(e4.y) : 0;
-    bf16_t* const stash2 = reinterpret_cast<bf16_t*>(sp(e4.z, e4.w));
+    sg.ntiles = (int)rs[4]; sg.N = (int)rs[7]; sg.in_aux = (int)rs[2];
+    sg.vec_off = (int)rs[8]; sg.dcol_off = (int)rs[9]; sg.nout_off = (int)rs[10]; sg.site = (int)rs[11];
+    sg.shift = (int)rs[12]; sg.relu = (int)rs[13]; sg.fold = (int)rs[14];
+    const int mb = (int)rs[15];
+    sg.rows_out = (int)rs[16]; sg.kin_off = (int)rs[17];
+    sg.mask_scale = __uint_as_float(rs[18]); sg.has_bias = (int)rs[19];
+    sg.mask_y = reinterpret_cast<const bf16_t*>(p64(rs[20], rs[21])); sg.ld_mask = (int)rs[22]; sg.mask_col0 = (int)rs[23];
     // a layer that ends in a LayerNorm backward: this lane's chunks of the forward's rows and the row statistics.
     // 16-sample workgroups request them NOW, before the segment's weight stages (>= D of them: FLY younger loads), and wait with
     // vmcnt(FLY) at the layer end; 32-sample workgroups have no registers to hold them across the segment (the compiler would spill
@@ -852,10 +856,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
     ChainLnbIn lnb[TS];
 #pragma unroll
     for (int ps = 0; ps < TS; ++ps) { lnb[ps].y[0] = lnb[ps].y[1] = u32x4{0u, 0u, 0u, 0u}; lnb[ps].mu = 0.f; lnb[ps].rs = 0.f; }
-    auto lnb_fetch = [&]() __attribute__((always_inline)) {
-      const bf16_t* ly = end_lnb_y;
-      const float* lmean = end_mean;
-      const float* lrstd = end_rstd;
+    auto lnb_fetch = [&](const bf16_t* ly, const float* lmean, const float* lrstd, int nout) __attribute__((always_inline)) {
 #pragma unroll
       for (int ps = 0; ps < TS; ++ps) {       // 16 rows per pass: this lane's row is 16 ps + 2 wave + (lane >> 5)
         const int r = 16 * ps + 2 * wave + (lane >> 5);
@@ -867,7 +868,9 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
         asm volatile("global_load_dword %0, %1, off" : "=v"(lnb[ps].rs) : "v"(lrstd + gr) : "memory");
       }
     };
-    if (TS == 1 && has_ln == 2) lnb_fetch();
+    if (TS == 1 && endi >= 0 && rl[5] == 2u)
+      lnb_fetch(reinterpret_cast<const bf16_t*>(p64(rl[6], rl[7])), reinterpret_cast<const float*>(p64(rl[0], rl[1])),
+                reinterpret_cast<const float*>(p64(rl[2], rl[3])), (int)rl[4]);
     stamp(3 + 3 * si);
 #define CH_SEG1(MBv, KBv, NKTv, Hv) seg_body(std::integral_constant<int, MBv>{}, std::integral_constant<bool, KBv>{}, std::integral_constant<int, NKTv>{}, std::integral_constant<int, Hv>{}, sg)
 #define CH_SEG(MBv, KBv, NKTv) do { if constexpr (D == 8) { if (half) half = CH_SEG1(MBv, KBv, NKTv, 1); else half = CH_SEG1(MBv, KBv, NKTv, 0); } else CH_SEG1(MBv, KBv, NKTv, 0); } while (0)
@@ -886,13 +889,43 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
 #undef CH_SEG
 #undef CH_SEG1
     stamp(4 + 3 * si);
-    fetch_rec(si + 1 < nseg ? si + 1 : 0);       // the next segment's record: lands while this layer ends
+    // scalar loads from the kernel arguments, in flight while this layer ends: the next segment's first part, this segment's end part
+    unsigned rn[SEG_DW], rln[8], re[20];
+    {
+      const auto* nrec = reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(&KA.rec[si + 1 < nseg ? si + 1 : 0]);
+      const auto* crec = reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(&KA.rec[si].end);
+#pragma unroll
+      for (int k = 0; k < SEG_DW; ++k) rn[k] = nrec[k];
+      rln[0] = nrec[30]; rln[1] = nrec[31]; rln[2] = nrec[32]; rln[3] = nrec[33];
+      rln[4] = nrec[35]; rln[5] = nrec[37]; rln[6] = nrec[38]; rln[7] = nrec[39];
+#pragma unroll
+      for (int k = 0; k < 20; ++k) re[k] = crec[k];
+      // every loaded register is named HERE: the loads cannot sink behind the barrier to their first use (a round trip of its own
+      // there), and their one wait is the one the barrier needs for the epilogue's LDS writes anyway
+      asm volatile("" :: "s"(rn[0]), "s"(rn[1]), "s"(rn[2]), "s"(rn[3]), "s"(rn[4]), "s"(rn[5]), "s"(rn[6]), "s"(rn[7]), "s"(rn[8]), "s"(rn[9]),
+                   "s"(rn[10]), "s"(rn[11]), "s"(rn[12]), "s"(rn[13]), "s"(rn[14]), "s"(rn[15]));
+      asm volatile("" :: "s"(rn[16]), "s"(rn[17]), "s"(rn[18]), "s"(rn[19]), "s"(rn[20]), "s"(rn[21]), "s"(rn[22]), "s"(rn[23]), "s"(rln[0]),
+                   "s"(rln[1]), "s"(rln[2]), "s"(rln[3]), "s"(rln[4]), "s"(rln[5]), "s"(rln[6]), "s"(rln[7]));
+      asm volatile("" :: "s"(re[0]), "s"(re[1]), "s"(re[2]), "s"(re[3]), "s"(re[4]), "s"(re[5]), "s"(re[6]), "s"(re[7]), "s"(re[8]), "s"(re[9]));
+      asm volatile("" :: "s"(re[10]), "s"(re[11]), "s"(re[12]), "s"(re[13]), "s"(re[14]), "s"(re[15]), "s"(re[16]), "s"(re[17]), "s"(re[18]), "s"(re[19]));
+    }
     if (endi >= 0) {
       const int rows_out = sg.rows_out, img_out = rows_out * 128;
       wstamp(200 + 8 * si + wave);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();              // the output panel is complete
       stamp(130 + 4 * si);
+      // the end part (ChainEndK, dword by dword): stash / LayerNorm pointers, widths, kind
+      bf16_t* const stash = reinterpret_cast<bf16_t*>(p64(re[0], re[1]));
+      bf16_t* const end_xln = reinterpret_cast<bf16_t*>(p64(re[2], re[3]));
+      float* const end_out32 = reinterpret_cast<float*>(p64(re[4], re[5]));
+      float* const end_mean = reinterpret_cast<float*>(p64(re[6], re[7]));
+      float* const end_rstd = reinterpret_cast<float*>(p64(re[8], re[9]));
+      const int ld_stash = (int)re[10], nout = (int)re[11], gb_off = (int)re[12], has_ln = (int)re[13];
+      const bf16_t* const end_lnb_y = reinterpret_cast<const bf16_t*>(p64(re[14], re[15]));
+      const float lms = __uint_as_float(re[16]);
+      const int res_split = (int)re[17];
+      bf16_t* const stash2 = reinterpret_cast<bf16_t*>(p64(re[18], re[19]));
       if (has_ln == 2) {
         stamp(100);
         if constexpr (TS == 1) {
@@ -902,7 +935,7 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
           else
             asm volatile("s_waitcnt vmcnt(%4)" : "+v"(lnb[0].y[0]), "+v"(lnb[0].y[1]), "+v"(lnb[0].mu), "+v"(lnb[0].rs) : "n"(2 * G) : "memory");
         } else {
-          lnb_fetch();
+          lnb_fetch(end_lnb_y, end_mean, end_rstd, nout);
 #pragma unroll
           for (int ps = 0; ps < TS; ++ps)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(lnb[ps].y[0]), "+v"(lnb[ps].y[1]), "+v"(lnb[ps].mu), "+v"(lnb[ps].rs) : : "memory");
@@ -993,6 +1026,10 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
       unsigned char* t = pin; pin = pout; pout = t;
       rows_in = rows_out;
     }
+#pragma unroll
+    for (int k = 0; k < SEG_DW; ++k) rs[k] = rn[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) rl[k] = rln[k];
     stamp(5 + 3 * si);
   }
   // forward head chain: the NIG head on the finished e2 panel (the last layer end's barrier made it complete; its stash copy only
