@@ -372,22 +372,30 @@ int mmdeer_nig_loss(const float* gamma, const float* nu, const float* alpha, con
  *
  * deer.DEERLoss.forward (reference src/models/deer.py:125-195, loss variant 1) on n elements (mu, nu, alpha, beta and
  * targets of one shape): loss_out[5] = total, nll_loss, evidence_reg, kl_reg, mse with
- * total = mean(nll) + evidence_weight * mean(reg) + kl_weight * mean(clamp(kl, 0)).
- * scratch: mmdeer_deer_loss_v1_scratch(n) floats. */
+ * total = mean(nll) + evidence_weight * mean(reg) + kl_weight * mean(clamp(kl, 0)); the clamp passes the gradient where
+ * kl >= 0.  scratch: mmdeer_deer_loss_v1_scratch(n) floats (4 per block of 256 elements), written in full and no further.
+ * Refused (-1, nothing written): a NULL tensor, n <= 0, one to three of the four gradient pointers. */
 long long mmdeer_deer_loss_v1_scratch(long long n);
 int mmdeer_deer_loss_v1(const float* mu, const float* nu, const float* alpha, const float* beta, const float* targets,
                         long long n, float evidence_weight, float kl_weight, float* loss_out, float* dmu, float* dnu,
                         float* dalpha, float* dbeta, float* scratch, void* stream);
 /* losses.UncertaintyRegularizationLoss.forward with flat keys (src/utils/losses.py:363-416): alpha, beta [B][D], D <= 8;
- * loss_out[3] = reg_loss (= dw * diversity + sw * sparsity), diversity_loss, sparsity_loss. */
+ * loss_out[3] = reg_loss (= dw * diversity + sw * sparsity), diversity_loss, sparsity_loss.  The variance is the unbiased
+ * one: B = 1 gives NaN in reg_loss, diversity_loss and every gradient element, as the reference does (sparsity_loss stays
+ * finite).  Refused (-1, nothing written): B <= 0, D outside 1..8, one gradient pointer of the two. */
 int mmdeer_uncertainty_reg_loss(const float* alpha, const float* beta, int B, int D, float diversity_weight,
                                 float sparsity_weight, float* loss_out, float* dalpha, float* dbeta, void* stream);
 /* losses.CalibrationLoss.forward, n_bins = 15, 'uniform' (src/utils/losses.py:431-497) on n flattened elements:
- * loss_out[1]; bin_counts[15] (optional) are the exact bin populations. */
+ * loss_out[1]; bin_counts[15] (optional) are the exact bin populations.  The bin edges are the embedded fp32 values of
+ * torch.linspace(0, 1, 16): the same bits as mmdeer_calibration_loss_bins with that table.  Bin k is [edge k, edge k + 1),
+ * the last bin is closed on the right; a confidence outside [0, 1] (alpha < 1) is in no bin and carries a zero gradient.
+ * u = beta / (alpha - 1 + 1e-8) = inf in fp32 gives confidence 0 (bin 0) and, as in the fp32 reference program, NaN in
+ * that sample's dalpha (0 * inf) and 0 in its dbeta.  The error clamp passes dgamma for 0 <= |y - gamma| / 2 <= 1. */
 int mmdeer_calibration_loss(const float* gamma, const float* alpha, const float* beta, const float* targets, long long n,
                             float* loss_out, int32_t* bin_counts, float* dgamma, float* dalpha, float* dbeta, void* stream);
 /* The same with any number of uniform bins (1 <= n_bins <= 32): `edges` is a HOST array of n_bins + 1 fp32 bin boundaries,
- * torch.linspace(0, 1, n_bins + 1) as fp32 evaluates it (the reference's rule, losses.py:459); bin_counts[n_bins]. */
+ * torch.linspace(0, 1, n_bins + 1) as fp32 evaluates it (the reference's rule, losses.py:459); bin_counts[n_bins].
+ * Refused (-1, nothing written): n <= 0, n_bins outside 1..32, one or two of the three gradient pointers. */
 int mmdeer_calibration_loss_bins(const float* gamma, const float* alpha, const float* beta, const float* targets, long long n,
                                  const float* edges, int n_bins, float* loss_out, int32_t* bin_counts, float* dgamma, float* dalpha,
                                  float* dbeta, void* stream);
@@ -669,7 +677,9 @@ int mmdeer_evidence_tail_bwd(const mmdeer_evidence_tail_args* a);
  * batch; every call adds {n, sum p, sum t, sum p^2, sum t^2, sum pt, sum |p-t|, sum (p-t)^2} per emotion dimension over
  * the rows without NaN -- CCC, Pearson, MAE and RMSE follow from these 24 numbers, so validation copies 192 bytes to the
  * host instead of (N, 3) arrays.  sample_err / sample_unc (optional, [B]): per-sample mean |error| / mean uncertainty for
- * the quantile-binned calibration error (metrics.py:214-279). */
+ * the quantile-binned calibration error (metrics.py:214-279), as fp32 programs (three additions from 0, one division by 3;
+ * a NaN in the row gives NaN).  sample_err may be asked for without unc, sample_unc may not (-1).  B = 0 returns 0 and
+ * touches nothing; two launches on the same inputs add the same bits. */
 int mmdeer_eval_accumulate(const float* pred, const float* target, const float* unc, double* acc, float* sample_err,
                            float* sample_unc, int B, void* stream);
 
@@ -680,7 +690,9 @@ int mmdeer_eval_accumulate(const float* pred, const float* target, const float* 
  *     order statistics np.quantile interpolates between -- vals[r][0..1] = sorted[floor(q_r (nv - 1))], the one after it --
  *     their weight frac[r] and *nvalid = nv.  (The host forms the edges: 2 nq floats, as numpy's 'linear' method does.)
  *   mmdeer_eval_ece_bins: bins[i] = {count, sum (1 - unc), sum (1 - err)} over edges[i] <= unc < edges[i + 1]; edges is a
- *     DEVICE array of n_bins + 1 doubles, n_bins <= 16.  ECE = sum_i count_i / nv * |sum1_i - sum2_i| / count_i. */
+ *     DEVICE array of n_bins + 1 doubles, n_bins <= 16.  ECE = sum_i count_i / nv * |sum1_i - sum2_i| / count_i.
+ *     The comparison is in double: an uncertainty equal to an interior edge belongs to the upper bin, one equal to
+ *     edges[n_bins] or below edges[0] to none.  Refused (-1, nothing written): n <= 0, n_bins outside 1..16. */
 int mmdeer_eval_quantile_select(const float* err, const float* unc, long long n, int nq, float* vals, double* frac,
                                 long long* nvalid, void* stream);
 int mmdeer_eval_ece_bins(const float* err, const float* unc, long long n, const double* edges, int n_bins, double* bins,
