@@ -66,6 +66,9 @@ FRAME_CONSTANTS, _FRAME_CLASSES, FRAME_SYMBOLS = _header.parse(_header.read(_hea
 globals().update({cls.__name__: cls for cls in _FRAME_CLASSES.values()})    # Conv2dArgs, Bn2dArgs
 FRAME_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _FRAME_CLASSES.items()}
 BN2D_SCRATCH = FRAME_CONSTANTS["BN2D_SCRATCH"]
+# include/mmdeer_routes.h, the companion header of the layer chains' route queries (no struct of its own: mmdeer_chain_args is
+# mmdeer.h's, passed by reference)
+_, _, ROUTE_SYMBOLS = _header.parse(_header.read(_header.ROUTES_HEADER_PATH), {}, {})
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -80,7 +83,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args

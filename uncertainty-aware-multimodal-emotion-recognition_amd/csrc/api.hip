@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mmdeer.h"
+#include "../../include/mmdeer_routes.h"
 #include "../../include/mmdeer_video.h"
 #include "../../include/mmdeer_frames.h"
 #include "attention.h"
@@ -466,13 +467,15 @@ int mmdeer_dropout_mask(int site, int rows, int cols, float dropout_p, uint64_t 
   return launch_dropout_mask(dc, site, rows, cols, out, (hipStream_t)stream);
 }
 
-// The layer-chain kernel as an operator (include/mmdeer.h: mmdeer_chain): every row of the input is a sample.
-int mmdeer_chain(const mmdeer_chain_args* a) {
+}  // extern "C"
+namespace {
+// The argument mapping of mmdeer_chain, shared with the dry run mmdeer_chain_route; returns 1 for an empty batch (nothing to do).
+int chain_front(const mmdeer_chain_args* a, ChainArgs& c) {
   MMDEER_CHECK(a && a->nseg >= 1 && a->nseg <= MMDEER_CHAIN_MAX_SEGS, "mmdeer_chain: 1..%d segments", MMDEER_CHAIN_MAX_SEGS);
   MMDEER_CHECK(a->rows >= 0, "mmdeer_chain: rows");
-  if (a->rows == 0) return 0;
+  if (a->rows == 0) return 1;
   MMDEER_CHECK(a->samples_per_workgroup == 0 || a->samples_per_workgroup == 16 || a->samples_per_workgroup == 32, "mmdeer_chain: samples_per_workgroup must be 0, 16 or 32");
-  ChainArgs c{};
+  c = ChainArgs{};
   c.X = reinterpret_cast<const bf16_t*>(a->X); c.ldx = a->ldx; c.K0 = a->K0; c.B = a->rows; c.groups = 1; c.group_stride = 0;
   c.ts = a->samples_per_workgroup;
   c.drop = make_drop(a->dropout_p, a->seed, a->offset, a->offset_dev);
@@ -496,7 +499,28 @@ int mmdeer_chain(const mmdeer_chain_args* a) {
       q.lnb_dz = reinterpret_cast<bf16_t*>(s.lnb_dz); q.lnb_partial = s.lnb_partial; q.lnb_mask_scale = s.lnb_mask_scale;
     }
   }
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+// The layer-chain kernel as an operator (include/mmdeer.h: mmdeer_chain): every row of the input is a sample.
+int mmdeer_chain(const mmdeer_chain_args* a) {
+  ChainArgs c;
+  const int rc = chain_front(a, c);
+  if (rc != 0) return rc < 0 ? -1 : 0;
   return launch_chain(c, (hipStream_t)a->stream);
+}
+
+int mmdeer_chain_route(const mmdeer_chain_args* a, char* out, int cap) {
+  if (out && cap > 0) out[0] = 0;
+  ChainArgs c;
+  const int rc = chain_front(a, c);
+  if (rc != 0) return rc < 0 ? -1 : 0;
+  ChainKernel k;
+  TRY(launch_chain(c, nullptr, &k));
+  if (out && cap > 0) snprintf(out, cap, "%s workgroups=%d", chain_kernel_name(k), chain_workgroups(c));
+  return 1;
 }
 
 int mmdeer_chain_workgroups(int rows, int samples_per_workgroup) {

@@ -152,9 +152,17 @@ struct RepackTable { int njobs; int pad_; RepackJob job[REPACK_MAX]; };
 int check_repack(RepackTable& t);      // validates the jobs and places them on the grid: granules of the launch, or -1
 int launch_repack(RepackTable& t, hipStream_t s);
 
+// The kernel a chain launch runs: a pure host function of the samples per workgroup (chain_samples_per_workgroup) and option
+// chain_depth, which selects among the 16-sample instantiations (2 / 8: A/B measurements; anything else: the 4-deep default).
+enum ChainKernel { CHAIN_S16, CHAIN_S16_D2, CHAIN_S16_D8, CHAIN_S32 };
+ChainKernel chain_route(int samples_per_workgroup);
+const char* chain_kernel_name(ChainKernel k);      // "s16", "s16_d2", "s16_d8", "s32"
+
 void chain_seg_defaults(ChainSeg& s);
-// Validates shapes / alignment, derives the kernel's tables and enqueues the chain on `stream`.
-int launch_chain(const ChainArgs& a, hipStream_t stream);
+// Validates shapes / alignment, derives the kernel's tables and enqueues the chain on `stream`.  With `dry` it stops in front of the
+// launch and answers the kernel it would have run: every check, no GPU touched.
+int launch_chain(const ChainArgs& a, hipStream_t stream, ChainKernel* dry = nullptr);
 inline int chain_samples_per_workgroup(const ChainArgs& a) { return a.ts == 16 || a.ts == 32 ? a.ts : chain_samples_per_workgroup(a.B); }
+inline int chain_workgroups(const ChainArgs& a) { const int m = chain_samples_per_workgroup(a); return (a.B + m - 1) / m; }
 
 }  // namespace mmdeer

@@ -32,8 +32,8 @@
 // layers the weight stream into the CU -- every workgroup streams ALL weights of the chain (2.2 MB for F9..F17) for its 16 rows at
 // ~320 cycles per 16-KiB stage = 51 B/clk per CU (tools/probes/wstream.hip: 54 with plain register loads from a fragment-major image,
 // 39-44 through an LDS-DMA ring) --; for 256-wide layers the layer ends: the next table record ~0.45k cycles (scalar loads; ~1.0k
-// while it was a vector read from LDS made scalar), barrier skew between the two waves of a SIMD ~1.5k, LayerNorm ~1.9k, and the
-// restart of the 4-deep ring behind every layer end (eight stages in 4.5k cycles instead of 2.6k).  One workgroup per 16 rows also
+// while it was a vector read from LDS made scalar), barrier skew between the two waves of a SIMD ~1.5k, LayerNorm ~1.9k, and eight
+// stages that take 4.5k cycles instead of 2.6k (NOT the restart of the 4-deep ring: see the 8-deep ring below).  One workgroup per 16 rows also
 // means the launch only pays while the chip holds all workgroups at once: stackc.hip uses 16-sample workgroups for B <= 4096,
 // 32-sample workgroups up to 8192 and the separate launches above.
 // Measured dead ends (rounds 3-4): the LDS-DMA weight ring (36-45 B/clk) and a seventh slot of it; re-reading the activation fragments
@@ -41,8 +41,11 @@
 // arguments by dependent scalar loads record after record (~1000 cycles each); weights into registers from the ROW-MAJOR copy
 // (16 lanes x 64 bytes per request: 22 B/clk); a tile's epilogue inside the first stage of the next tile; deferring the stash /
 // LayerNorm stores into the next layer's first tile; an 8-deep ring (chain_depth = 8: parity-green, slower -- 137 spilled VGPRs at
-// 192 compiler-visible registers); both LayerNorm-backward fold passes behind one barrier pair (no change -- and none again as one
-// pass through 64 KiB of scratch); the dropout step counter as an untracked load and the first record from scalar loads (+3 us per
+// 192 compiler-visible registers; and slower by as much WITHOUT a spill, as an instantiation with no NIG head compiled in and the
+// fragments read from the panel: every part of the chain, wide layers, small segments and record decodes alike, took 25-75 % more
+// cycles, so the spills were not why, and neither is the restart of the 4-deep ring what the small segments lose --
+// profiles/chain_ring8_ab.json); both LayerNorm-backward fold passes behind one barrier pair (no change -- and
+// none again as one pass through 64 KiB of scratch); the dropout step counter as an untracked load and the first record from scalar loads (+3 us per
 // step).
 //
 // Backward chains (dX = dY W through fragment-major images of W^T) use the same kernel: a segment's epilogue can multiply by the
@@ -584,15 +587,21 @@ __device__ __forceinline__ void chain_body(const ChainKArgs& a) {
     p_tile();
   };
   auto issue = [&](auto slotc) __attribute__((always_inline)) {
-    wr_issue<decltype(slotc)::value>(p_cur);
+    constexpr int SL = decltype(slotc)::value;
+    wr_issue<SL>(p_cur);
     if (++p_kt < p_nkt) p_cur += 2048;          // padding stages load the last real one again
-    if (p_kt == p_nv) {
-      p_kt = 0;
-      if (++p_nt == p_ntiles) {
-        if (++p_si == nseg) p_si = 0;   // past the end the stream wraps around: D stages nobody reads, but every
-        p_load();                       // stage of the chain sees the same number of younger loads (constant waits)
-      } else {
-        p_tile();
+    // A tile takes whole granules and the stream starts in slot 0, so a tile begins in the first slot of a granule and can only end
+    // in the last one: the other G - 1 issue sites of every granule carry no end-of-tile code at all (the cursor's advance -- the next
+    // tile's address, or the next segment's record -- was most of the instruction text of a stage)
+    if constexpr ((SL + 1) % G == 0) {
+      if (p_kt == p_nv) {
+        p_kt = 0;
+        if (++p_nt == p_ntiles) {
+          if (++p_si == nseg) p_si = 0;   // past the end the stream wraps around: D stages nobody reads, but every
+          p_load();                       // stage of the chain sees the same number of younger loads (constant waits)
+        } else {
+          p_tile();
+        }
       }
     }
   };
@@ -1134,7 +1143,24 @@ void chain_seg_defaults(ChainSeg& s) {
   s.drop_site = -1;
 }
 
-int launch_chain(const ChainArgs& a, hipStream_t stream) {
+ChainKernel chain_route(int msamp) {
+  if (msamp != 16) return CHAIN_S32;
+  const int depth = opt(OPT_CHAIN_DEPTH);
+  if (depth == 2) return CHAIN_S16_D2;
+  if (depth == 8) return CHAIN_S16_D8;
+  return CHAIN_S16;
+}
+const char* chain_kernel_name(ChainKernel k) {
+  switch (k) {
+    case CHAIN_S16: return "s16";
+    case CHAIN_S16_D2: return "s16_d2";
+    case CHAIN_S16_D8: return "s16_d8";
+    case CHAIN_S32: return "s32";
+  }
+  return "?";
+}
+
+int launch_chain(const ChainArgs& a, hipStream_t stream, ChainKernel* dry) {
   MMDEER_CHECK(a.nseg >= 1 && a.nseg <= CHAIN_MAX_SEGS, "chain: 1..%d segments (got %d)", CHAIN_MAX_SEGS, a.nseg);
   if (a.nig.enabled) {
     const ChainNig& g = a.nig;
@@ -1273,10 +1299,14 @@ int launch_chain(const ChainArgs& a, hipStream_t stream) {
   MMDEER_CHECK(a.seg[a.nseg - 1].end_layer, "chain: the last segment must end its layer");
   MMDEER_CHECK(vec <= CHAIN_VEC_FLOATS, "chain: %d bias / gamma / beta floats exceed the LDS area (%d)", vec, CHAIN_VEC_FLOATS);
   k.nseg = a.nseg; k.nvec = nvec;
-  if (ts == 1 && opt(OPT_CHAIN_DEPTH) == 2) hipLaunchKernelGGL(chain_kernel_s16_d2, dim3(nwg), dim3(512), 0, stream, k);
-  else if (ts == 1 && opt(OPT_CHAIN_DEPTH) == 8) hipLaunchKernelGGL(chain_kernel_s16_d8, dim3(nwg), dim3(512), 0, stream, k);
-  else if (ts == 1) hipLaunchKernelGGL(chain_kernel_s16, dim3(nwg), dim3(512), 0, stream, k);
-  else hipLaunchKernelGGL(chain_kernel_s32, dim3(nwg), dim3(512), 0, stream, k);
+  const ChainKernel route = chain_route(msamp);
+  if (dry) { *dry = route; return 0; }
+  switch (route) {
+    case CHAIN_S16_D2: hipLaunchKernelGGL(chain_kernel_s16_d2, dim3(nwg), dim3(512), 0, stream, k); break;
+    case CHAIN_S16_D8: hipLaunchKernelGGL(chain_kernel_s16_d8, dim3(nwg), dim3(512), 0, stream, k); break;
+    case CHAIN_S16: hipLaunchKernelGGL(chain_kernel_s16, dim3(nwg), dim3(512), 0, stream, k); break;
+    case CHAIN_S32: hipLaunchKernelGGL(chain_kernel_s32, dim3(nwg), dim3(512), 0, stream, k); break;
+  }
   MMDEER_HIP(hipGetLastError());
   return 0;
 }

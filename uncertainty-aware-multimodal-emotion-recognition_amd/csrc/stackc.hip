@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../../include/mmdeer.h"
+#include "../../include/mmdeer_routes.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -614,6 +615,31 @@ size_t mmdeer_workspace_bytes(int batch, int compute_f32) { return make_layout(n
 size_t mmdeer_weights_bytes(int compute_f32) { return make_layout(nullptr, nullptr, 0, compute_f32).wbytes; }
 long long mmdeer_workspace_offset(int batch, int compute_f32, const char* name) { return layout_offset('S', batch, compute_f32 ? 1 : 0, name); }
 long long mmdeer_weights_offset(int compute_f32, const char* name) { return layout_offset('W', 0, compute_f32 ? 1 : 0, name); }
+
+// The chain launches of one single-call training step (mmdeer_forward + mmdeer_backward(phase = 0), no outside gradient) and the
+// kernel each would run: make_plan says which chains run, chain_route (chain.h) the kernel.
+int mmdeer_step_chain_routes(int batch, int compute_f32, int inputs_bf16, int targets, char* out, int cap) {
+  MMDEER_CHECK(batch >= 0, "step_chain_routes: batch");
+  const int c = out && cap > 0 ? cap : 0;
+  if (c) out[0] = 0;
+  if (batch == 0) return 0;
+  const Plan p = make_plan(batch, compute_f32 ? 1 : 0, 0, false, inputs_bf16 != 0, targets != 0);
+  const int ms = chain_samples_per_workgroup(batch);
+  int n = 0, len = 0;
+  auto line = [&](const char* label) {
+    ++n;
+    if (len >= c) return;
+    const int w = snprintf(out + len, c - len, "%s%s %s", len ? "\n" : "", label, chain_kernel_name(chain_route(ms)));
+    len = len + w < c ? len + w : c;
+  };
+  if (p.chains) {
+    line(p.in_chain ? "F1-F6" : "F2-F6");
+    line(p.nig_tail ? "F9-F18" : "F9-F17");
+  }
+  if (p.bchain) line(p.nigfold ? "B1-B10" : "B2-B10");
+  if (p.dchain) line("B13-B17");
+  return n;
+}
 
 int mmdeer_trace_begin(void** events, int n_events) {
   MMDEER_CHECK(events != nullptr && n_events > 0, "trace_begin: no events");
