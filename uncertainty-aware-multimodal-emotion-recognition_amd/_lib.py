@@ -69,6 +69,12 @@ BN2D_SCRATCH = FRAME_CONSTANTS["BN2D_SCRATCH"]
 # include/mmdeer_routes.h, the companion header of the layer chains' route queries (no struct of its own: mmdeer_chain_args is
 # mmdeer.h's, passed by reference)
 _, _, ROUTE_SYMBOLS = _header.parse(_header.read(_header.ROUTES_HEADER_PATH), {}, {})
+# include/mmdeer_frames_bwd.h, the companion header of the Conv2d backbone's backward: tables of its own again
+_FRAME_BWD_NAMES = {"mmdeer_bn2d_bwd_args": "Bn2dBwdArgs", "mmdeer_conv2d_wgrad_args": "Conv2dWgradArgs", "mmdeer_conv2d_dgrad_args": "Conv2dDgradArgs"}
+FRAME_BWD_CONSTANTS, _FRAME_BWD_CLASSES, FRAME_BWD_SYMBOLS = _header.parse(_header.read(_header.FRAMES_BWD_HEADER_PATH), _FRAME_BWD_NAMES, {})
+globals().update({cls.__name__: cls for cls in _FRAME_BWD_CLASSES.values()})    # Bn2dBwdArgs, Conv2dWgradArgs, Conv2dDgradArgs
+FRAME_BWD_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _FRAME_BWD_CLASSES.items()}
+BN2D_BWD_SCRATCH = FRAME_BWD_CONSTANTS["BN2D_BWD_SCRATCH"]
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -83,7 +89,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -117,7 +123,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         lib = bind(C.CDLL(path), require_all=True)
         if lib.mmdeer_abi_version() != ABI_VERSION:
             raise RuntimeError("libmmdeer_hip.so ABI version mismatch")
-        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
+        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
             if lib.mmdeer_sizeof(cname.encode()) != C.sizeof(cls):
                 raise RuntimeError(f"mmdeer: ctypes layout of mmdeer_{cname} ({C.sizeof(cls)} bytes) differs from the library's "
                                    f"({lib.mmdeer_sizeof(cname.encode())})")

@@ -10,6 +10,7 @@
 #include "../../include/mmdeer_routes.h"
 #include "../../include/mmdeer_video.h"
 #include "../../include/mmdeer_frames.h"
+#include "../../include/mmdeer_frames_bwd.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -565,6 +566,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(lstm_seq_args) SZ(temporal_pool_args) SZ(evidence_tail_args) SZ(token_embed_args) SZ(token_pool_args) SZ(token_stats_args)
   SZ(conv3_time_args) SZ(bn_time_args)   // mmdeer_video.h
   SZ(conv2d_args) SZ(bn2d_args)          // mmdeer_frames.h
+  SZ(bn2d_bwd_args) SZ(conv2d_wgrad_args) SZ(conv2d_dgrad_args)   // mmdeer_frames_bwd.h
 #undef SZ
   return -1;
 }

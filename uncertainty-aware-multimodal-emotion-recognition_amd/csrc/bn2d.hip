@@ -14,20 +14,12 @@
 // of its own.  The max pool starts its running maximum at 0 instead of padding with -inf: after the ReLU every value is >= 0, and
 // every 3 x 3 window holds at least one real element (its centre (2 ph, 2 pw) is inside the image), so the two agree.
 #include "../../include/mmdeer_frames.h"
-#include "bn_fold.h"
+#include "bn2d_norm.h"   // Lane, Norm (shared with bn2d_bwd.hip); bn_fold.h
 
 namespace mmdeer {
 namespace {
 
 static_assert(BN_MAXBLK * 2 * 512 == MMDEER_BN2D_SCRATCH, "scratch holds two per-channel partials per row block");
-
-struct Lane {
-  int cq, par, PAR;
-};
-__device__ __forceinline__ Lane lane_of(int C) {
-  const int CQ = C >> 2;   // a power of two
-  return Lane{(int)threadIdx.x & (CQ - 1), (int)threadIdx.x / CQ, 256 / CQ};
-}
 
 template <bool F32>
 __global__ __launch_bounds__(256) void bn2d_stats_partial_kernel(mmdeer_bn2d_args a, int M, int rpb) {
@@ -67,22 +59,6 @@ __global__ __launch_bounds__(256) void bn2d_stats_partial_kernel(mmdeer_bn2d_arg
 __global__ __launch_bounds__(256) void bn2d_stats_final_kernel(mmdeer_bn2d_args a, int M, int rpb, int nblk) {
   bn_fold_stats(a, M, a.C, rpb, nblk);
 }
-
-// the normalisation of this thread's four channels: v = relu((x - mean) * rstd * gamma + beta)
-struct Norm {
-  f32x4 mean, rstd, gamma, beta;
-  __device__ __forceinline__ void load(const mmdeer_bn2d_args& a, int cq) {
-    mean = *reinterpret_cast<const f32x4*>(a.mean + 4 * cq);
-    rstd = *reinterpret_cast<const f32x4*>(a.rstd + 4 * cq);
-    if (a.running) {   // `rstd` holds the running variance
-      rstd = f32x4{1.f / sqrtf(rstd.x + a.eps), 1.f / sqrtf(rstd.y + a.eps), 1.f / sqrtf(rstd.z + a.eps), 1.f / sqrtf(rstd.w + a.eps)};
-    }
-    gamma = *reinterpret_cast<const f32x4*>(a.gamma + 4 * cq);
-    beta = *reinterpret_cast<const f32x4*>(a.beta + 4 * cq);
-  }
-  // a constant channel gives relu(beta) exactly: (x - mean) is an exact zero
-  __device__ __forceinline__ f32x4 operator()(const f32x4& x) const { return relu4(fma4((x - mean) * rstd, gamma, beta)); }
-};
 
 // PAD and POOL: OH x OW is the interior of the output buffer (H x W, or the pooled size); Q = N (OH + 2) (OW + 2) output pixels
 template <bool F32, bool POOL>

@@ -18,28 +18,13 @@
 // The descriptor is a one-problem GemmGroup (M = N OH OW, N = Cout, K = KWe Cp, batch 1, no split); its batch stride sB, unused by a
 // batch of one, carries the tap stride of the image.
 #include "../../include/mmdeer_frames.h"
+#include "conv2d_geom.h"   // ConvGeom, conv_geom (shared with conv2d_bwd.hip)
 #include "elem.h"
 #include "gemm_kernel.inc"
 #include "options.h"
 
 namespace mmdeer {
 namespace {
-
-struct ConvGeom {
-  int Hp, Wp, Cp, OH, OW, k;
-};
-
-// geometry of one layer, from the header's rules; false: unsupported (k, Cin)
-inline bool conv_geom(int H, int W, int Cin, int k, int act_f32, ConvGeom& g, int& KWe) {
-  const int epc = act_f32 ? 4 : 8;
-  if (k == 7 && Cin == 3) { g.Cp = epc; KWe = 8; }
-  else if (k == 3 && Cin > 0 && Cin % epc == 0) { g.Cp = Cin; KWe = 3; }
-  else return false;
-  const int p = k / 2;
-  g.k = k; g.Hp = H + 2 * p; g.Wp = W + 2 * p;
-  g.OH = (H + 2 * p - k) / 2 + 1; g.OW = (W + 2 * p - k) / 2 + 1;
-  return true;
-}
 
 template <typename CT, int BM, int BN>
 __global__ __launch_bounds__(256, (BM * BN <= 64 * 64) ? 3 : 2) void conv2d_s2_kernel(const GemmGroup g, const ConvGeom cg) {
