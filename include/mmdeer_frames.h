@@ -1,5 +1,5 @@
-/* mmdeer -- C ABI of the frame video encoder's operators (csrc/conv2d.hip, csrc/bn2d.hip): the forward of the Conv2d backbone that
- * turns frames into per-frame features.  A companion of mmdeer.h in the same grammar (mmdeer/_header.py derives the ctypes binding),
+/* mmdeer -- C ABI of the frame video encoder's operators (csrc/conv2d.hip, csrc/bn2d.hip on csrc/bn_rows.h): the forward of the Conv2d
+ * backbone that turns frames into per-frame features.  A companion of mmdeer.h in the same grammar (mmdeer/_header.py derives the ctypes binding),
  * exported by the same library and covered by the same MMDEER_ABI_VERSION.  The conventions are mmdeer.h's: every call enqueues on
  * `stream`, never synchronises and allocates nothing; a refused call writes nothing, returns -1 and leaves its reason in
  * mmdeer_last_error(), and every refusal is decided on the host before any HIP runtime call; "act" = fp32 when act_f32 != 0,

@@ -1,5 +1,5 @@
-/* mmdeer -- C ABI of the frame video encoder's BACKWARD operators (csrc/bn2d_bwd.hip, csrc/conv2d_bwd.hip): the gradients of the
- * Conv2d backbone whose forward is include/mmdeer_frames.h.  A companion of mmdeer.h in the same grammar (mmdeer/_header.py derives
+/* mmdeer -- C ABI of the frame video encoder's BACKWARD operators (csrc/bn2d_bwd.hip on csrc/bn_rows.h, csrc/conv2d_bwd.hip): the
+ * gradients of the Conv2d backbone whose forward is include/mmdeer_frames.h.  A companion of mmdeer.h in the same grammar (mmdeer/_header.py derives
  * the ctypes binding), exported by the same library and covered by the same MMDEER_ABI_VERSION.  The conventions are mmdeer.h's:
  * every call enqueues on `stream`, never synchronises and allocates nothing; a refused call writes nothing, returns -1 and leaves its
  * reason in mmdeer_last_error(), and every refusal is decided on the host before any HIP runtime call; "act" = fp32 when

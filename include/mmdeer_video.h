@@ -1,5 +1,5 @@
-/* mmdeer -- C ABI of the temporal video encoder's operators (csrc/conv_time.hip, csrc/bn_time.hip): a companion of mmdeer.h, in the
- * same grammar (mmdeer/_header.py derives the ctypes binding of both), exported by the same library and covered by the same
+/* mmdeer -- C ABI of the temporal video encoder's operators (csrc/conv_time.hip, csrc/bn_time.hip on csrc/bn_rows.h): a companion of mmdeer.h,
+ * in the same grammar (mmdeer/_header.py derives the ctypes binding of both), exported by the same library and covered by the same
  * MMDEER_ABI_VERSION.  The conventions are mmdeer.h's: every call enqueues on `stream` and never synchronises; a refused call
  * writes nothing, returns -1 and leaves its reason in mmdeer_last_error(), and every refusal is decided on the host before any
  * HIP runtime call; "act" = fp32 when act_f32 != 0, else bf16.

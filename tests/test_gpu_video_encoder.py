@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from mmdeer import _lib, fusions, video
+from mmdeer import _lib, frames, fusions, video
 
 from . import video_ref as R
 from .test_oracle_golden import check_side_grads
@@ -179,6 +179,26 @@ def test_batchnorm_operators_match_float64(Rn, compute):
     (o64 * (out.double() > 0) * dout.double() * 1.25).sum().backward()
     assert _rel(dx, x64.grad) <= store and _rel(dg, g64.grad) <= 1e-4 and _rel(db, b64.grad) <= 1e-4
     assert dx.dtype == dt
+
+
+@pytest.mark.parametrize("compute", ["fp32", "bf16"])
+@pytest.mark.parametrize("Rn", [2, 390, 33001])       # one row per parity; a ragged last block; the row blocks grow
+def test_batchnorm_statistics_are_the_frame_encoders_bit_for_bit(Rn, compute):
+    """mmdeer_bn_time_stats and mmdeer_bn2d_stats are one pair of kernels (csrc/bn_rows.h): on the same [R][512] matrix, taken by
+    the second as one frame of R x 1 positions, they store the same bits in mean, rstd and the running buffers."""
+    x = _bn_inputs(Rn, compute)[0]
+    bns = []
+    for _ in range(2):
+        bn = torch.nn.BatchNorm1d(W)
+        with torch.no_grad():
+            bn.running_mean.copy_(torch.linspace(-1, 1, W)); bn.running_var.copy_(torch.linspace(0.5, 2, W)); bn.num_batches_tracked.fill_(41)
+        bns.append(bn.to(DEV))
+    got = (video.bn_stats(x, compute, bns[0]), frames.bn2d_stats(x, 1, Rn, 1, bns[1]))
+    for (m, r), bn in zip(got, bns):
+        assert torch.isfinite(m).all() and torch.isfinite(r).all() and int(bn.num_batches_tracked) == 42
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
+    assert torch.equal(bns[0].running_mean, bns[1].running_mean) and torch.equal(bns[0].running_var, bns[1].running_var)
+    assert torch.equal(bns[0].num_batches_tracked, bns[1].num_batches_tracked)
 
 
 @pytest.mark.parametrize("Rn", [390, 1221])

@@ -182,6 +182,12 @@ def ptr(t) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def set_bn_buffers(a, bn) -> None:
+    """The running buffers of an nn BatchNorm module into the argument struct of a statistics call, which updates them on the device."""
+    a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+    a.num_batches_tracked, a.momentum = bn.num_batches_tracked.data_ptr(), bn.momentum
+
+
 def current_stream() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream

@@ -1,26 +1,21 @@
 // The backward of nn.BatchNorm2d(C) + ReLU (+ MaxPool2d(3, 2, 1) / AdaptiveAvgPool2d(1)) of the frame video encoder's backbone on the
 // dense channels-last output y [M = N * H * W][C] of a convolution (include/mmdeer_frames_bwd.h), C in {64, 128, 256, 512}.
 //
-// Lane mapping: bn2d.hip's (bn2d_norm.h) -- thread t owns four consecutive channels of every PAR-th row of its workgroup's share.
-// The ReLU mask and the pool's arg-max come from Norm, the expression the forward stored its output from.
-//
 // Launches.  POOL source only: one index byte per pooled element (the first maximum of its window in (kh, kw) row-major order among
-// the in-image positions).  Then, for every source: per-block partial sums of g and g * xhat over the block's rows (each thread its
-// rows in index order, the PAR partials of a workgroup in index order out of LDS) into scratch; the fold of the blocks per channel
-// in a fixed order (bn_fold.h's split: segments of consecutive blocks, then the segments) into dbeta and dgamma; and dy.  g is
-// formed twice, by one function: the upstream gradient is gathered, never scattered, so there is no atomic and no ordering to fix.
-#include "../../include/mmdeer_frames_bwd.h"
-#include "bn2d_norm.h"
+// the in-image positions).  Then, for every source, bn_rows.h's backward -- partial sums, fold, dy -- with this file's gradient
+// functor.  g is formed twice, by one function: the upstream gradient is gathered, never scattered, so there is no atomic and no
+// ordering to fix.  The ReLU mask and the pool's arg-max come from Norm, the expression the forward stored its output from.
+#include "bn_rows.h"
 
 namespace mmdeer {
 namespace {
 
-static_assert(BN_MAXBLK * 2 * 512 == MMDEER_BN2D_BWD_SCRATCH, "scratch holds two per-channel partials per row block");
-
-// g = u * (v > 0) and xhat of this thread's four channels of row r
+// the backward's gradient functor (bn_rows.h): g = u * (v > 0) and xhat of this thread's four channels of row r
 template <bool F32, int SRC>
 struct Grad {
+  using Args = mmdeer_bn2d_bwd_args;
   Norm norm;
+  void* dy;
   int C, cq, H, W, PH, PW;
   float inv_hw;
   const void* y;
@@ -32,8 +27,10 @@ struct Grad {
     C = a.C; cq = cq_; H = a.H; W = a.W;
     PH = (H - 1) / 2 + 1; PW = (W - 1) / 2 + 1;
     inv_hw = 1.f / (float)(H * W);
-    y = a.y; dout = a.dout; idx = reinterpret_cast<const unsigned char*>(a.pool_idx);
+    y = a.y; dout = a.dout; dy = a.dy; idx = reinterpret_cast<const unsigned char*>(a.pool_idx);
   }
+  __device__ __forceinline__ f32x4 scale() const { return norm.gamma * norm.rstd; }
+  __device__ __forceinline__ void store(int r, const f32x4& d) const { st4<F32>(dy, (long long)r * C + 4 * cq, d); }
   // the pooled element (n, ph, pw) gives its gradient to window position `at` (= 3 i + j) only
   __device__ __forceinline__ void take(f32x4& u, long long q, unsigned at) const {
     const unsigned w = *reinterpret_cast<const unsigned*>(idx + q * C + 4 * cq);
@@ -86,12 +83,12 @@ __global__ __launch_bounds__(256) void bn2d_pool_index_kernel(mmdeer_bn2d_bwd_ar
     unsigned at0 = 0, at1 = 0, at2 = 0, at3 = 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      const int h = 2 * ph - 1 + i;
-      if (h < 0 || h >= H) continue;
+      int h;
+      if (!pool_tap(i, ph, H, h)) continue;
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const int w = 2 * pw - 1 + j;
-        if (w < 0 || w >= W) continue;
+        int w;
+        if (!pool_tap(j, pw, W, w)) continue;
         const f32x4 t = norm(ld4<F32>(a.y, ((n * H + h) * W + w) * C + 4 * l.cq));
         const unsigned at = 3 * i + j;
         if (t.x > best.x) { best.x = t.x; at0 = at; }
@@ -104,93 +101,15 @@ __global__ __launch_bounds__(256) void bn2d_pool_index_kernel(mmdeer_bn2d_bwd_ar
   }
 }
 
-// per-block partial sums: scratch[block][0][C] = sum g, scratch[block][1][C] = sum g * xhat
-template <bool F32, int SRC>
-__global__ __launch_bounds__(256) void bn2d_bwd_partial_kernel(mmdeer_bn2d_bwd_args a, int M, int rpb) {
-  __shared__ f32x4 sg[256], sx[256];
-  const Lane l = lane_of(a.C);
-  Grad<F32, SRC> grad;
-  grad.init(a, l.cq);
-  const int CQ = a.C >> 2, r0 = blockIdx.x * rpb, r1 = min(r0 + rpb, M);
-  f32x4 s{0.f, 0.f, 0.f, 0.f}, sxh{0.f, 0.f, 0.f, 0.f};
-  for (int r = r0 + l.par; r < r1; r += l.PAR) {
-    f32x4 xh;
-    const f32x4 g = grad(r, xh);
-    s += g;
-    sxh = fma4(g, xh, sxh);
-  }
-  sg[threadIdx.x] = s; sx[threadIdx.x] = sxh;
-  __syncthreads();
-  if (l.par != 0) return;
-  for (int q = 1; q < l.PAR; ++q) {
-    s += sg[q * CQ + l.cq];
-    sxh += sx[q * CQ + l.cq];
-  }
-  float* part = a.scratch + (long long)blockIdx.x * 2 * a.C;
-  *reinterpret_cast<f32x4*>(part + 4 * l.cq) = s;
-  *reinterpret_cast<f32x4*>(part + a.C + 4 * l.cq) = sxh;
-}
-
-// the fold of the blocks' partials: a workgroup owns BN_FOLD_CH channels, its threads are BN_FOLD_SEG segments of consecutive blocks
-__global__ __launch_bounds__(256) void bn2d_bwd_fold_kernel(mmdeer_bn2d_bwd_args a, int nblk) {
-  __shared__ float sb[BN_FOLD_SEG][BN_FOLD_CH], sg[BN_FOLD_SEG][BN_FOLD_CH];
-  const int C = a.C, cl = threadIdx.x % BN_FOLD_CH, seg = threadIdx.x / BN_FOLD_CH, c = blockIdx.x * BN_FOLD_CH + cl;
-  const int per = (nblk + BN_FOLD_SEG - 1) / BN_FOLD_SEG, b0 = seg * per, b1 = min(b0 + per, nblk);
-  float db = 0.f, dg = 0.f;
-  for (int b = b0; b < b1; ++b) {
-    db += a.scratch[(long long)b * 2 * C + c];
-    dg += a.scratch[(long long)b * 2 * C + C + c];
-  }
-  sb[seg][cl] = db; sg[seg][cl] = dg;
-  __syncthreads();
-  if (seg != 0) return;
-  for (int s = 1; s < BN_FOLD_SEG; ++s) { db += sb[s][cl]; dg += sg[s][cl]; }
-  a.dbeta[c] = db;
-  a.dgamma[c] = dg;
-}
-
-template <bool F32, int SRC>
-__global__ __launch_bounds__(256) void bn2d_bwd_dy_kernel(mmdeer_bn2d_bwd_args a, int M, int rpb) {
-  const Lane l = lane_of(a.C);
-  Grad<F32, SRC> grad;
-  grad.init(a, l.cq);
-  const int r0 = blockIdx.x * rpb, r1 = min(r0 + rpb, M);
-  const float inv_m = 1.f / (float)M;
-  const f32x4 scale = grad.norm.gamma * grad.norm.rstd;
-  f32x4 mb{0.f, 0.f, 0.f, 0.f}, mg{0.f, 0.f, 0.f, 0.f};
-  if (!a.running) {
-    mb = *reinterpret_cast<const f32x4*>(a.dbeta + 4 * l.cq) * inv_m;
-    mg = *reinterpret_cast<const f32x4*>(a.dgamma + 4 * l.cq) * inv_m;
-  }
-  for (int r = r0 + l.par; r < r1; r += l.PAR) {
-    f32x4 xh;
-    const f32x4 g = grad(r, xh);
-    st4<F32>(a.dy, (long long)r * a.C + 4 * l.cq, scale * (g - mb - xh * mg));
-  }
-}
-
-constexpr long long LIMIT = 1ll << 31;   // elements of one buffer
-
-template <bool F32, int SRC>
-int launch_bn2d_bwd(const mmdeer_bn2d_bwd_args& a, int M, hipStream_t s) {
-  const int rpb = bn_rows_per_block(M), nblk = bn_blocks(M);
-  hipLaunchKernelGGL((bn2d_bwd_partial_kernel<F32, SRC>), dim3(nblk), dim3(256), 0, s, a, M, rpb);
-  hipLaunchKernelGGL(bn2d_bwd_fold_kernel, dim3(a.C / BN_FOLD_CH), dim3(256), 0, s, a, nblk);
-  hipLaunchKernelGGL((bn2d_bwd_dy_kernel<F32, SRC>), dim3(nblk), dim3(256), 0, s, a, M, rpb);
-  MMDEER_HIP(hipGetLastError());
-  return 0;
-}
-
 template <bool F32>
-int launch_bn2d_bwd_src(const mmdeer_bn2d_bwd_args& a, int M, hipStream_t s) {
-  if (a.src == MMDEER_BN2D_SRC_DENSE) return launch_bn2d_bwd<F32, MMDEER_BN2D_SRC_DENSE>(a, M, s);
-  if (a.src == MMDEER_BN2D_SRC_AVG) return launch_bn2d_bwd<F32, MMDEER_BN2D_SRC_AVG>(a, M, s);
+int launch_bn2d_bwd_src(const mmdeer_bn2d_bwd_args& a, int M) {
+  if (a.src == MMDEER_BN2D_SRC_DENSE) return bn_launch_bwd<Grad<F32, MMDEER_BN2D_SRC_DENSE>, 1>(a, M);
+  if (a.src == MMDEER_BN2D_SRC_AVG) return bn_launch_bwd<Grad<F32, MMDEER_BN2D_SRC_AVG>, 1>(a, M);
   const int PH = (a.H - 1) / 2 + 1, PW = (a.W - 1) / 2 + 1;
   const long long Q = (long long)a.N * PH * PW;
-  long long ppb = (Q + BN_MAXBLK - 1) / BN_MAXBLK;   // pooled elements per workgroup: at least 32, and at most BN_MAXBLK workgroups
-  if (ppb < 32) ppb = 32;
-  hipLaunchKernelGGL((bn2d_pool_index_kernel<F32>), dim3((unsigned)((Q + ppb - 1) / ppb)), dim3(256), 0, s, a, PH, PW, Q, (int)ppb);
-  return launch_bn2d_bwd<F32, MMDEER_BN2D_SRC_POOL>(a, M, s);
+  const PixelPlan p = bn_pixel_plan(Q);
+  hipLaunchKernelGGL((bn2d_pool_index_kernel<F32>), dim3(p.nblk), dim3(256), 0, (hipStream_t)a.stream, a, PH, PW, Q, p.ppb);
+  return bn_launch_bwd<Grad<F32, MMDEER_BN2D_SRC_POOL>, 1>(a, M);
 }
 
 }  // namespace
@@ -201,10 +120,7 @@ using namespace mmdeer;
 extern "C" {
 
 int mmdeer_bn2d_bwd(const mmdeer_bn2d_bwd_args* a) {
-  MMDEER_CHECK(a, "bn2d_bwd: NULL argument struct");
-  MMDEER_CHECK(a->C == 64 || a->C == 128 || a->C == 256 || a->C == 512, "bn2d_bwd: unsupported C=%d (64, 128, 256 or 512)", a->C);
-  MMDEER_CHECK(a->N >= 0 && a->H >= 1 && a->W >= 1, "bn2d_bwd: bad shape N=%d H=%d W=%d", a->N, a->H, a->W);
-  MMDEER_CHECK((long long)a->N * a->H * a->W * a->C < LIMIT, "bn2d_bwd: y has 2^31 elements or more");
+  TRY(bn_check_nhwc(a, "bn2d_bwd", "y"));
   MMDEER_CHECK(a->src == MMDEER_BN2D_SRC_DENSE || a->src == MMDEER_BN2D_SRC_POOL || a->src == MMDEER_BN2D_SRC_AVG,
                "bn2d_bwd: src must be 0, 1 or 2 (got %d)", a->src);
   if (a->N == 0) return 0;
@@ -216,8 +132,7 @@ int mmdeer_bn2d_bwd(const mmdeer_bn2d_bwd_args* a) {
                    al16(a->dgamma) && al16(a->dbeta) && al16(a->scratch) && al16(a->pool_idx),
                "bn2d_bwd: misaligned pointer (every pointer needs 16 bytes)");
   const int M = a->N * a->H * a->W;
-  hipStream_t s = (hipStream_t)a->stream;
-  return a->act_f32 ? launch_bn2d_bwd_src<true>(*a, M, s) : launch_bn2d_bwd_src<false>(*a, M, s);
+  return a->act_f32 ? launch_bn2d_bwd_src<true>(*a, M) : launch_bn2d_bwd_src<false>(*a, M);
 }
 
 }  // extern "C"

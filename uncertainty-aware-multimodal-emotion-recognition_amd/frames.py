@@ -108,8 +108,7 @@ def bn2d_stats(y: torch.Tensor, N: int, H: int, W: int, bn=None, eps: float = 1e
     a = _bn_args(y, N, H, W)
     a.mean, a.rstd, a.scratch, a.eps = mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(), eps
     if bn is not None:
-        a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        a.num_batches_tracked, a.momentum = bn.num_batches_tracked.data_ptr(), bn.momentum
+        _lib.set_bn_buffers(a, bn)
     _lib.check(_lib.load().mmdeer_bn2d_stats(C.byref(a)))
     return mean, rstd
 

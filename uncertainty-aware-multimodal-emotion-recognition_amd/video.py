@@ -94,8 +94,7 @@ def bn_stats(x: torch.Tensor, compute_dtype: str, bn: Optional[nn.BatchNorm1d] =
     a = _bn_args(x, compute_dtype)
     a.mean, a.rstd, a.scratch, a.eps = mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(), eps
     if bn is not None:
-        a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-        a.num_batches_tracked, a.momentum = bn.num_batches_tracked.data_ptr(), bn.momentum
+        _lib.set_bn_buffers(a, bn)
     _lib.check(_lib.load().mmdeer_bn_time_stats(C.byref(a)))
     return mean, rstd
 
