@@ -1,8 +1,10 @@
 """Temporal text encoder: ``encoders.EnhancedTextEncoder`` (reference src/models/encoders.py:553-761) on token-level text --
 ids and a mask (the reference's no-BERT configuration: ``nn.Embedding(30000, 768, padding_idx=0)`` + ``nn.Embedding(128, 768)``),
-or a (B, L, 768) matrix of contextual embeddings from the caller's own BERT (the reference's BERT branch downstream of
-``last_hidden_state``) -> the (B, 512) block that ``ComposedDEER`` / ``generic_fusion`` take.  BERT itself and tokenisation
-are outside this package.
+a (B, L, 768) matrix of contextual embeddings from the caller's own BERT (the reference's BERT branch downstream of
+``last_hidden_state``), or -- constructed with ``bert=BertEncoder(...)`` (mmdeer.bert: the trunk's forward on HIP, frozen) -- the
+reference's BERT configuration itself: ids and a mask through the trunk, then the same path on its ``last_hidden_state``
+-> the (B, 512) block that ``ComposedDEER`` / ``generic_fusion`` take.  Tokenisation and pretrained weights are outside this
+package; so is the trunk's backward.
 
 Per forward: ``mmdeer_token_embed_fwd`` (gather + position + mask, or mask alone), one ``mmdeer_gemm`` over all B * L rows for
 the pool's ``W1 x + b1``, ``mmdeer_token_pool_fwd`` (masked softmax over tokens, renormalisation, weighted sum),
@@ -20,6 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib, fusions, ops, side
+from .bert import BertEncoder
 
 _SITE_BERT, _SITE_LING, _SITE_OUT = 136, 137, 138    # the reference's three nn.Dropout sites; the pool has none
 
@@ -169,9 +172,15 @@ class TemporalTextEncoder(nn.Module):
     the reference takes from ``bert(...).last_hidden_state``) -> (B, 512) fp32; differentiable w.r.t. the embeddings.  The
     ids feed the token statistics only and are NOT clamped, as in the reference; negative valid ids are undefined input (the
     reference's ``bincount`` raises on them; checking here would cost a device sync per call).
-    In ``.train()`` the three dropout sites of the reference are live (the library's counter-hash masks)."""
+    In ``.train()`` the three dropout sites of the reference are live (the library's counter-hash masks).
 
-    def __init__(self, config: Optional[Dict] = None, compute_dtype: str = "fp32"):
+    ``bert=BertEncoder(...)`` (``hidden_size`` 768) makes it the reference's BERT configuration: the module holds the trunk as
+    ``self.bert`` and creates no ``embedding`` / ``positional_encoding`` tables, so its ``state_dict`` keys are the reference's
+    (``bert.*``, ``token_attention.*``, ...).  ``forward(input_ids, attention_mask)`` then runs the trunk under ``no_grad`` (it is
+    forward only and has no dropout) and ``forward_embeddings`` on its ``last_hidden_state`` as it comes, fp32 or bf16; everything
+    behind the trunk trains as without it."""
+
+    def __init__(self, config: Optional[Dict] = None, compute_dtype: str = "fp32", bert: Optional[BertEncoder] = None):
         super().__init__()
         config = config or {}
         self.hidden_dim = config.get("hidden_dim", 512)
@@ -182,11 +191,16 @@ class TemporalTextEncoder(nn.Module):
         self.dropout_seed, self._train_step = config.get("dropout_seed", 0), 0     # counter-hash dropout: seed + one tick per training forward
         if self.hidden_dim % 32:
             raise NotImplementedError("hidden_dim must be a multiple of 32")
-        self.bert = None
+        if bert is not None and not isinstance(bert, BertEncoder):
+            raise TypeError(f"bert must be a mmdeer.bert.BertEncoder (got {type(bert).__name__})")
+        if bert is not None and bert.hidden_size != E:
+            raise ValueError(f"the text encoder takes a BERT trunk of hidden_size {E} (got {bert.hidden_size})")
+        self.bert = bert
         self.bert_hidden_size = E
-        self.vocab_size = 30000
-        self.embedding = nn.Embedding(self.vocab_size, E, padding_idx=0)
-        self.positional_encoding = nn.Embedding(self.max_length, E)
+        if bert is None:
+            self.vocab_size = 30000
+            self.embedding = nn.Embedding(self.vocab_size, E, padding_idx=0)
+            self.positional_encoding = nn.Embedding(self.max_length, E)
         self.token_attention = nn.Sequential(nn.Linear(E, A), nn.Tanh(), nn.Linear(A, 1), nn.Softmax(dim=1))
         self.bert_projection = nn.Sequential(nn.Linear(E, self.hidden_dim), nn.ReLU(), nn.Dropout(self.dropout))
         self.linguistic_features_dim = 10
@@ -238,6 +252,10 @@ class TemporalTextEncoder(nn.Module):
         ops._check_dev(input_ids, attention_mask)
         if B == 0:
             return torch.zeros(0, self.hidden_dim, device=input_ids.device)
+        if self.bert is not None:
+            with torch.no_grad():
+                hidden = self.bert(input_ids, attention_mask).last_hidden_state
+            return self.forward_embeddings(hidden, input_ids, attention_mask)
         if B * L > MAX_ROWS and torch.is_grad_enabled() and (self.embedding.weight.requires_grad or self.positional_encoding.weight.requires_grad):
             raise ValueError(f"B * L = {B * L} is above the {MAX_ROWS} rows the table gradients take")
         m = (attention_mask != 0).float().reshape(-1).contiguous()
