@@ -353,20 +353,51 @@ def audio_encoder_features(P, x, prefix="", hidden=256):
 
 
 # --------------------------------------------------------------------------- Stack B
-# complete_project.CompleteDEERModel, eval-mode forward.  Parameter dict keyed by the reference's state_dict names
+# complete_project.CompleteDEERModel, eval-mode forward (masks=None) or training-mode forward on given dropout masks.  Parameter dict keyed by the reference's state_dict names
 # (audio_encoder.*, attention_module.*, fusion_module.*, prediction_heads.<dim>.*, calibration_layer.*).
-def _stackb_encoder(P, x, prefix, layers=3):
-    """EnhancedModalityEncoder -- complete_project.py:76-117: Linear-ReLU-LN, `layers` x (x + LN(ReLU(Lin x))), Linear."""
-    h = _layer_norm(torch.relu(_lin(x, P, prefix + ".input_projection.0")),
+STACKB_EST_P = 0.2     # UncertaintyEstimator's nn.Dropout(0.2) -- complete_project.py:186, not a config field
+
+
+def _site(masks, p, name):
+    """(keep matrix or None, p) of the dropout site `name`.  `masks`: None (eval mode: every site open) or {site: 0/1 keep matrix}, a
+    site that is absent being open; `p`: one probability for every site, or {site: p} (absent: 0.3, the config's default).  The
+    estimator's p is 0.2 unless a dict names it."""
+    if masks is None or masks.get(name) is None:
+        return None, 0.0
+    if isinstance(p, dict):
+        return masks[name], float(p.get(name, STACKB_EST_P if name == "est" else 0.3))
+    return masks[name], STACKB_EST_P if name == "est" else float(p)
+
+
+def _relu_at(x, masks, name):
+    """ReLU.  ``masks["relu"]`` ({name: int tensor of x's shape -- 1: on, 0: off, -1: by x's own sign}) forces the decision of single
+    units: where an input lies closer to zero than fp32 arithmetic resolves, the derivative on either side is a correct answer, and a
+    test that compares gradients takes the side the step under test took (tests/test_gpu_stackb_step.py).  ``masks["relu_seen"]``
+    (a dict) receives every ReLU's input by name."""
+    if masks is not None and masks.get("relu_seen") is not None:
+        masks["relu_seen"][name] = x.detach()
+    d = None if masks is None or masks.get("relu") is None else masks["relu"].get(name)
+    if d is None:
+        return torch.relu(x)
+    return x * torch.where(d < 0, x > 0, d > 0).to(x.dtype)
+
+
+def _stackb_encoder(P, x, prefix, layers=3, masks=None, p=0.3, m=0):
+    """EnhancedModalityEncoder -- complete_project.py:76-117: Linear-ReLU-LN, `layers` x (x + LN(Dropout(ReLU(Lin x)))), Linear.
+    Dropout sites ``res.<m>.<l>`` (:68): encoder m's block l, keep (B, D)."""
+    h = _layer_norm(_relu_at(_lin(x, P, prefix + ".input_projection.0"), masks, f"stem.{m}"),
                     P[prefix + ".input_projection.2.weight"], P[prefix + ".input_projection.2.bias"])
     for i in range(layers):
         q = f"{prefix}.encoder_layers.{i}.layers"          # ResidualBlock, complete_project.py:60-73
-        h = h + _layer_norm(torch.relu(_lin(h, P, q + ".0")), P[q + ".3.weight"], P[q + ".3.bias"])
+        h = h + _layer_norm(_drop(_relu_at(_lin(h, P, q + ".0"), masks, f"res.{m}.{i}"), *_site(masks, p, f"res.{m}.{i}")), P[q + ".3.weight"], P[q + ".3.bias"])
     return _lin(h, P, prefix + ".output_projection")
 
 
-def _stackb_mha(P, prefix, query, key, value, heads=8):
-    """MultiHeadAttention on (B, S, D) tensors -- complete_project.py:120-184 (eval: no dropout, no mask)."""
+def _stackb_mha(P, prefix, query, key, value, heads=8, mask=None, p=0.0):
+    """MultiHeadAttention on (B, S, D) tensors -- complete_project.py:120-184 (no attention mask).  `mask`: the dropout on the
+    attention weights (:141, 172) for ONE query and ONE key.  The softmax over the single key is 1, so the dropped weight of a head
+    is keep / (1 - p) and multiplies that head's slice of the value path: keep (B, heads), one decision per (row, head), or already
+    spread over the columns, (B, D)."""
     Bq, _, D = query.shape
     hd = D // heads
     split = lambda t: t.view(Bq, -1, heads, hd).transpose(1, 2)
@@ -374,50 +405,59 @@ def _stackb_mha(P, prefix, query, key, value, heads=8):
         split(_lin(value, P, prefix + ".value_proj"))
     w = torch.softmax(Q @ K.transpose(-2, -1) / math.sqrt(hd), dim=-1)
     o = (w @ V).transpose(1, 2).contiguous().view(Bq, -1, D)
+    if mask is not None:
+        assert query.shape[1] == 1 and key.shape[1] == 1, "the mask form is stated for one query and one key"
+        cols = mask if mask.shape[1] == D else mask.repeat_interleave(hd, dim=1)
+        o = _drop(o, cols.reshape(Bq, 1, D), p)
     return _lin(o, P, prefix + ".output_proj")
 
 
-def _stackb_uncertainty(P, x, prefix):
-    """UncertaintyEstimator -- complete_project.py:187-213: D -> D/2 -> D/4 -> 1, sigmoid."""
-    h = torch.relu(_lin(x, P, prefix + ".0"))
-    h = torch.relu(_lin(h, P, prefix + ".3"))
+def _stackb_uncertainty(P, x, prefix, mask=None, p=STACKB_EST_P, masks=None, i=0):
+    """UncertaintyEstimator -- complete_project.py:187-213: D -> D/2 (ReLU, Dropout(0.2)) -> D/4 -> 1, sigmoid."""
+    h = _drop(_relu_at(_lin(x, P, prefix + ".0"), masks, f"est.0.{i}"), mask, p)
+    h = _relu_at(_lin(h, P, prefix + ".3"), masks, f"est.3.{i}")
     return torch.sigmoid(_lin(h, P, prefix + ".5"))
 
 
-def stackb_attention(P, audio, video, text, heads=8, prefix="attention_module"):
-    """UncertaintyAwareAttention -- complete_project.py:216-304."""
+def stackb_attention(P, audio, video, text, heads=8, prefix="attention_module", masks=None, p=0.3):
+    """UncertaintyAwareAttention -- complete_project.py:216-304.  Dropout sites: ``attn_self`` / ``attn_cross`` keep (B, 3, heads)
+    or (B, 3, D) (modality on axis 1; see _stackb_mha), ``est`` keep (B, 3, D/2), ``wn`` keep (B, D) (weight_network, :237)."""
     a3, v3, t3 = audio.unsqueeze(1), video.unsqueeze(1), text.unsqueeze(1)
     ue = prefix + ".uncertainty_estimator.estimator"
-    ua, uv, ut = (_stackb_uncertainty(P, x, ue) for x in (audio, video, text))
+    sl = lambda name, i: (lambda k, q: (None if k is None else k[:, i], q))(*_site(masks, p, name))
+    ua, uv, ut = (_stackb_uncertainty(P, x, ue, *sl("est", i), masks, i) for i, x in enumerate((audio, video, text)))
     sa = prefix + ".self_attention"
-    a_self, v_self, t_self = (_stackb_mha(P, sa, x, x, x, heads).squeeze(1) for x in (a3, v3, t3))
+    a_self, v_self, t_self = (_stackb_mha(P, sa, x, x, x, heads, *sl("attn_self", i)).squeeze(1) for i, x in enumerate((a3, v3, t3)))
     ca = prefix + ".cross_attention"      # text is the query, the modality itself key and value (:270-273)
-    a_cross, v_cross, t_cross = (_stackb_mha(P, ca, t3, x, x, heads).squeeze(1) for x in (a3, v3, t3))
+    a_cross, v_cross, t_cross = (_stackb_mha(P, ca, t3, x, x, heads, *sl("attn_cross", i)).squeeze(1) for i, x in enumerate((a3, v3, t3)))
     wi = torch.cat([a_self, v_self, t_self, ua, uv, ut], dim=1)
     wn = prefix + ".weight_network"
-    w = torch.softmax(_lin(torch.relu(_lin(wi, P, wn + ".0")), P, wn + ".3"), dim=1)
+    w = torch.softmax(_lin(_drop(_relu_at(_lin(wi, P, wn + ".0"), masks, "wn"), *_site(masks, p, "wn")), P, wn + ".3"), dim=1)
     return {"audio": w[:, 0:1] * a_self + (1 - ua) * a_cross,
             "video": w[:, 1:2] * v_self + (1 - uv) * v_cross,
             "text": w[:, 2:3] * t_self + (1 - ut) * t_cross,
             "attention_weights": w, "modality_uncertainties": torch.cat([ua, uv, ut], dim=1)}
 
 
-def stackb_fusion(P, audio, video, text, prefix="fusion_module"):
-    """HierarchicalFusionModule -- complete_project.py:307-366."""
-    def stage(x, q):   # Linear, ReLU, Dropout, LayerNorm, Linear, ReLU
-        h = _layer_norm(torch.relu(_lin(x, P, q + ".0")), P[q + ".3.weight"], P[q + ".3.bias"])
-        return torch.relu(_lin(h, P, q + ".4"))
-    av = stage(torch.cat([audio, video], dim=1), prefix + ".av_fusion")
+def stackb_fusion(P, audio, video, text, prefix="fusion_module", masks=None, p=0.3):
+    """HierarchicalFusionModule -- complete_project.py:307-366.  Dropout sites ``av`` / ``tri`` (:318, 328), keep (B, fusion_dim)."""
+    def stage(x, q, site):   # Linear, ReLU, Dropout, LayerNorm, Linear, ReLU
+        h = _layer_norm(_drop(_relu_at(_lin(x, P, q + ".0"), masks, site + ".0"), *_site(masks, p, site)), P[q + ".3.weight"], P[q + ".3.bias"])
+        return _relu_at(_lin(h, P, q + ".4"), masks, site + ".4")
+    av = stage(torch.cat([audio, video], dim=1), prefix + ".av_fusion", "av")
     tri_in = torch.cat([av, text], dim=1)
     gate = torch.sigmoid(_lin(tri_in, P, prefix + ".fusion_gate.0"))
-    tri = stage(tri_in, prefix + ".trimodal_fusion")
+    tri = stage(tri_in, prefix + ".trimodal_fusion", "tri")
     return gate * tri + (1 - gate) * av
 
 
-def stackb_head(P, x, prefix):
-    """DEERPredictionHead -- complete_project.py:369-418."""
+def stackb_head(P, x, prefix, masks=None, p=0.3, d=0):
+    """DEERPredictionHead -- complete_project.py:369-418.  Dropout sites behind the first two layers (:379, 382): ``h0.<d>`` keep
+    (B, hidden) and ``h3.<d>`` keep (B, hidden / 2), d the head's index."""
     q = prefix + ".evidence_network"
-    e = _lin(torch.relu(_lin(torch.relu(_lin(x, P, q + ".0")), P, q + ".3")), P, q + ".6")
+    h = _drop(_relu_at(_lin(x, P, q + ".0"), masks, f"h0.{d}"), *_site(masks, p, f"h0.{d}"))
+    h = _drop(_relu_at(_lin(h, P, q + ".3"), masks, f"h3.{d}"), *_site(masks, p, f"h3.{d}"))
+    e = _lin(h, P, q + ".6")
     mu = e[:, 0]
     nu = F.softplus(e[:, 1]) + 1e-6
     alpha = F.softplus(e[:, 2]) + 1.0
@@ -440,15 +480,17 @@ def stackb_calibration(P, unc, prefix="calibration_layer"):
     return torch.cat(cols, dim=1)
 
 
-def stackb_forward(P, audio, video, text, heads=8, layers=3):
-    """CompleteDEERModel.forward -- complete_project.py:517-589."""
-    enc = [_stackb_encoder(P, x, n, layers) for x, n in
-           ((audio, "audio_encoder"), (video, "video_encoder"), (text, "text_encoder"))]
-    att = stackb_attention(P, *enc, heads=heads)
-    fused = stackb_fusion(P, att["audio"], att["video"], att["text"])
+def stackb_forward(P, audio, video, text, heads=8, layers=3, masks=None, p=0.3):
+    """CompleteDEERModel.forward -- complete_project.py:517-589.  ``masks=None``: eval mode.  Otherwise the training-mode forward
+    with the given keep matrices ({site: 0/1 matrix}; the sites and their shapes are named in the functions above, an absent site is
+    open) and `p` (one probability, or {site: p}); the estimator's p is 0.2 whatever `p` says, unless a dict names ``est``."""
+    enc = [_stackb_encoder(P, x, n, layers, masks, p, m) for m, (x, n) in
+           enumerate(((audio, "audio_encoder"), (video, "video_encoder"), (text, "text_encoder")))]
+    att = stackb_attention(P, *enc, heads=heads, masks=masks, p=p)
+    fused = stackb_fusion(P, att["audio"], att["video"], att["text"], masks=masks, p=p)
     out = {}
-    for d in DIM_NAMES:
-        for k, v in stackb_head(P, fused, f"prediction_heads.{d}").items():
+    for i, d in enumerate(DIM_NAMES):
+        for k, v in stackb_head(P, fused, f"prediction_heads.{d}", masks, p, i).items():
             out[f"{d}_{k}"] = v
     out["mu_all"] = torch.stack([out[f"{d}_mu"] for d in DIM_NAMES], dim=1)
     out["uncertainty_all"] = torch.stack([out[f"{d}_uncertainty"] for d in DIM_NAMES], dim=1)

@@ -233,7 +233,8 @@ def test_stackb_gradients_other_parameters_and_ragged_batches(B):
 
 
 def test_stackb_bf16_gradients_track_fp32():
-    """bf16 storage / fp32 accumulation: every gradient within a few bf16 roundings of the fp32 one (cosine + norm)."""
+    """bf16 storage / fp32 accumulation: every gradient within a few bf16 roundings of the fp32 one (cosine + norm).
+    The tight statement, launch by launch against float64, is tests/test_gpu_stackb_step.py."""
     b = synth.make_batch(256, seed=3)
     res = {}
     for compute in ("fp32", "bf16"):
@@ -292,7 +293,8 @@ def test_stackb_training_mode_dropout_and_optimizer_steps():
 
 def test_stackb_dropout_backward_matches_finite_differences():
     """With dropout live the backward must use the SAME masks as the forward: directional derivative of the loss along a
-    random parameter direction (masks frozen by resetting the step counter) vs the analytic gradient, fp32."""
+    random parameter direction (masks frozen by resetting the step counter) vs the analytic gradient, fp32.
+    The tight statement, every gradient against float64 on the same masks, is tests/test_gpu_stackb_step.py."""
     m, _ = _train_model("fp32", tag="stackb2")
     b = synth.make_batch(33, seed=12)
     xs, y = _batch_dev(b)

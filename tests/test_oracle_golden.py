@@ -248,14 +248,19 @@ def test_stackb_single_key_attention_is_two_linears(golden_dir):
     assert torch.equal(full, short)
 
 
-def stackb_oracle_gradients(O, P, batch):
-    """MultiTaskDEERLoss gradients of the oracle's Stack B (dropout sites open), by autograd.  Shared with the GPU tests."""
-    Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-    o = O.stackb_forward(Pg, *(torch.from_numpy(batch[k]) for k in ("audio", "video", "text")))
+def stackb_oracle_gradients(O, P, batch, masks=None, p=0.3, dtype=None, outputs=False):
+    """MultiTaskDEERLoss gradients of the oracle's Stack B, by autograd.  Shared with the GPU tests.  Default: dropout sites open, in
+    the parameters' dtype.  ``masks`` / ``p``: the training-mode forward on these keep matrices (``O.stackb_forward``); ``dtype``: the
+    whole computation in that dtype (float64: the reference of tests/test_gpu_stackb_step.py); ``outputs``: the forward's dict too."""
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    Pg = {k: cast(v).clone().requires_grad_(True) for k, v in P.items()}
+    kw = {} if masks is None else dict(masks=masks, p=p)
+    o = O.stackb_forward(Pg, *(cast(torch.from_numpy(batch[k])) for k in ("audio", "video", "text")), **kw)
     pred = {k: v.unsqueeze(1) for k, v in o.items() if k.split("_")[-1] in ("mu", "nu", "alpha", "beta") and v.dim() == 1}
-    loss = O.multitask_loss(pred, torch.from_numpy(batch["targets"]))
+    loss = O.multitask_loss(pred, cast(torch.from_numpy(batch["targets"])))
     loss["total_loss"].backward()
-    return loss["total_loss"].detach(), {k: v.grad for k, v in Pg.items()}
+    res = loss["total_loss"].detach(), {k: v.grad for k, v in Pg.items()}
+    return (*res, {k: v.detach() for k, v in o.items() if torch.is_tensor(v)}) if outputs else res
 
 
 def check_gradient_digests(g, grads, rtol, atol_frac):

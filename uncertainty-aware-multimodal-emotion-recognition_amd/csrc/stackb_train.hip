@@ -86,11 +86,11 @@ __global__ __launch_bounds__(256) void attn_mix_bwd_kernel(const mmdeer_stackb_a
     st4<F32>(a.d_cross, (long long)(3 * b + m) * (a.ld_dcross ? a.ld_dcross : 256) + col, g * (1.f - u[m]));
   }
   if (a.unc8 && lane < 2) st4<F32>(a.unc8, 8ll * b + 4 * lane, lane == 0 ? f32x4{u[0], u[1], u[2], 0.f} : f32x4{0.f, 0.f, 0.f, 0.f});
-  // softmax over the three modalities
-  const float dot = dw[0] * w[0] + dw[1] * w[1] + dw[2] * w[2];
-  float dl[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dl[k] = w[k] * (dw[k] - dot);
+  // softmax over the three modalities: d l_k = w_k (d w_k - sum_j w_j d w_j) = w_k sum_{j != k} w_j (d w_k - d w_j), the weights summing
+  // to one.  The pairwise form keeps its relative accuracy in a saturated row (w_k -> 1, the others tiny), where d w_k - dot cancels to
+  // the rounding of w_k and the whole d_pre row inherits the error (tests/test_gpu_stackb_step.py).
+  const float d01 = dw[0] - dw[1], d02 = dw[0] - dw[2], d12 = dw[1] - dw[2];
+  const float dl[3] = {w[0] * (w[1] * d01 + w[2] * d02), w[1] * (w[2] * d12 - w[0] * d01), -w[2] * (w[0] * d02 + w[1] * d12)};
   if (lane == 0) {
     st4<F32>(a.d_logits8, 8ll * b, f32x4{dl[0], dl[1], dl[2], 0.f});
     st4<F32>(a.d_logits8, 8ll * b + 4, f32x4{0.f, 0.f, 0.f, 0.f});

@@ -24,6 +24,11 @@ the plans differ in more than that, the difference is a field of ``Part`` / ``La
 The row kernels between the runs, the 128 -> 4 head layers and the weight-gradient records around them are written out in order:
 the order of the ``dw`` / fold / copy records decides the composition of the grouped launches and hence the bits.
 
+``model.keep_backward_tape`` (default off; tests/test_gpu_stackb_step.py) keeps references to what the backward leaves in memory: ``T["bwd"]``, by
+name, the activation-gradient matrices both plans store, and ``T["ops"]``, launch by launch only, the three kinds of matrix a chain keeps in LDS
+(``lnr.``: LayerNorm rows before a residual block's bypass is added; ``dln.``: the gradient a LayerNorm backward reads; ``dxr.``: dz W before the bypass
+gradient is added; each followed by the ``Lin`` name).  References only: no launch, copy or allocation more, and the same order.
+
 Layout conventions are those of the inference executor (csrc/stackb.hip): encoder outputs in column blocks of one (B, 768)
 matrix whose (3B, 256) reading is the row set of the shared-weight attention layers; heads stacked along N.
 """
@@ -96,9 +101,10 @@ def _cols(t, c0, n=None):
 class Runner:
     """Executes runs by one of the two plans.  ``dw(dy, x, target)`` / ``vec(name, n)``: the backward's gradient destinations."""
 
-    def __init__(self, ex: Exec, Q: Params, chain: bool, pc: float):
+    def __init__(self, ex: Exec, Q: Params, chain: bool, pc: float, tape: Optional[dict] = None):
         self.ex, self.Q, self.chain, self.pc = ex, Q, chain, pc
         self.dw = self.vec = None
+        self.tape = tape           # model.keep_backward_tape, launch by launch: the matrices between two launches that no tape entry names
 
     def p_of(self, r: Lin) -> float:
         return self.pc if r.p is None else r.p
@@ -186,7 +192,10 @@ class Runner:
                 r = ly.parts[0].lin
                 xln, mean, rstd = ly.ln
                 if r.residual:                                     # x + LayerNorm(...) (:73): to a temporary, then the sum (the chain's residual=1)
-                    ex.add(xln, src, ex.ln_fwd(ly.out, *Q.ln(r), None, mean, rstd)[0])
+                    tmp = ex.ln_fwd(ly.out, *Q.ln(r), None, mean, rstd)[0]
+                    if self.tape is not None:
+                        self.tape["lnr." + r.name] = tmp               # LayerNorm(...) before the bypass is added
+                    ex.add(xln, src, tmp)
                 else:
                     ex.ln_fwd(ly.out, *Q.ln(r), xln, mean, rstd)
                 src = xln
@@ -214,6 +223,8 @@ class Runner:
                 if pt.dw:
                     self.dw(*pt.dw)
                 if pt.res_add:                                     # (the chain keeps the bypass gradient in columns [256, 512) of its panel)
+                    if self.tape is not None:
+                        self.tape["dxr." + r.name] = out               # dz W before the bypass gradient is added
                     out = ex.add(torch.empty_like(out), bypass, out)
                 if ly.out is None:
                     cur = out
@@ -221,6 +232,8 @@ class Runner:
                     pt.after()
             if ly.lnb is not None:
                 r, y, mean, rstd, dz, ms = ly.lnb
+                if self.tape is not None:
+                    self.tape["dln." + r.name] = cur                   # the gradient the LayerNorm backward reads
                 ex.ln_bwd(cur, y, mean, rstd, Q.ln(r)[0], self.vec(r.ln + ".weight", y.shape[1]), self.vec(r.ln + ".bias", y.shape[1]), ms, dz=dz)
                 bypass, cur = cur, dz
             for rec in ly.dw:
@@ -238,10 +251,13 @@ def forward_train(model, xs: List[torch.Tensor], drop, flat=None) -> Dict:
     # bf16 fused step: the sample-local runs of layers go through the layer-chain kernel (mmdeer_chain), ONE launch per run
     Fg = chain_plan(model, flat, dt)
     Q = Params(L, dt, flat, Fg)
-    run = Runner(ex, Q, Fg is not None, pc)
+    # model.keep_backward_tape (tests/test_gpu_stackb_step.py): references to what the launches leave in memory and no tape entry names --
+    # no launch, copy or allocation more, and the same order
+    ops_tape = {} if getattr(model, "keep_backward_tape", False) else None
+    run = Runner(ex, Q, Fg is not None, pc, ops_tape)
     new = lambda *s, d=None: torch.empty(*s, dtype=d or dt, device=dev)
     stat = lambda n: (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
-    T: Dict = {"P": Q, "B": B, "xs": xs, "ex": ex, "enc": [], "chain": Fg is not None}
+    T: Dict = {"P": Q, "B": B, "xs": xs, "ex": ex, "enc": [], "chain": Fg is not None, "ops": ops_tape}
     E = new(B, 3 * ENC)
     for m, (x, e) in enumerate(zip(xs, L.enc)):
         # encoder m: Linear-ReLU-LayerNorm stem, the residual blocks x + LayerNorm(Dropout(ReLU(Linear x))), output projection
@@ -359,7 +375,8 @@ def backward(model, T: Dict, g4: torch.Tensor, flat=None) -> Dict[str, torch.Ten
     sc = ex.scale_of(pc)
     chain = flat is not None and bool(T.get("chain"))               # the layer-chain plan (see forward_train)
     Fg = Q.Fg if chain else None
-    run = Runner(ex, Q, chain, pc)
+    run = Runner(ex, Q, chain, pc, T.get("ops"))
+    keep = T.get("ops") is not None                                 # model.keep_backward_tape: T["bwd"], by name, at the end
     late = []                      # flat mode: (destination view, source) copies that must wait for the grouped dW launches
     if flat is not None:
         ex.deferred, ex.folds = [], []
@@ -432,16 +449,16 @@ def backward(model, T: Dict, g4: torch.Tensor, flat=None) -> Dict[str, torch.Ten
         dz0, din = new(B, FUS), new(B, r0.K)
         run.bwd(dz4, B, [Layer([Part(r4, dw=(dz4, n1, r4))], lnb=(r0, a1, mean, rstd, dz0, sc), dw=[(dz0, inp, r0)]),
                          Layer([Part(r0)], out=din)], ts=16 if r0.K > 512 else 0)
-        return din
+        return din, dz0
 
-    dT = stage_bwd(L.tri, dZ4, T["tri"], Tt)
+    dT, dz0_tri = stage_bwd(L.tri, dZ4, T["tri"], Tt)
     dT2 = ex.dx(dG, FUS, Q.w(L.gate), new(B, FUS + ENC), FUS + ENC, B, wt=Q.wt(L.gate))
     dw(dG, Tt, L.gate)
     dtext = ex.add(new(B, ENC), dT[:, FUS:], dT2[:, FUS:])
     # d av_fused: through the trimodal input, the gate input and the gate mix; av_fused = relu(.)
     tmp = ex.add(new(B, FUS), dT[:, :FUS], dT2[:, :FUS])
     dz4_av = ex.add(new(B, FUS), tmp, dav_a, mask=Tt[:, :FUS], scale=1.0)
-    dAV = stage_bwd(L.av, dz4_av, T["av"], T["AV"])
+    dAV, dz0_av = stage_bwd(L.av, dz4_av, T["av"], T["AV"])
     # ---- attention tail
     a = T["attn_args"]
     dS, dpre = new(3 * B, ENC), new(B, ENC)
@@ -477,6 +494,7 @@ def backward(model, T: Dict, g4: torch.Tensor, flat=None) -> Dict[str, torch.Ten
     else:
         gwn[:, :3 * ENC].copy_(feat); gwn[:, 3 * ENC:].copy_(unc[:, :3])                   # (memory plumbing: two column blocks of one parameter)
     dS_b = ex.dx(dpre, ENC, Q.wn1(), new(B, 3 * ENC), 3 * ENC, B, wt=Q.wn1_t())
+    dS_a = dS                                                    # the row kernel's part of d self
     dS = ex.add(dSX[:, :ENC] if chain else new(3 * B, ENC), dS, dS_b.view(3 * B, ENC))
     # uncertainty estimator: its 64 -> 1 layer's gradients, then the two dX products on the 3 B rows
     t4w2, t4b2 = z32(8, ENC // 4), z32(8)
@@ -506,17 +524,24 @@ def backward(model, T: Dict, g4: torch.Tensor, flat=None) -> Dict[str, torch.Ten
     dE = ex.add(new(3 * B, ENC), dE_v, dE_est).view(B, 3 * ENC)
     # ---- encoders: dh = dE W_out, then per residual block (top down) dz = LayerNorm'(dh) masked, dh += dz W, and the stem's
     # LayerNorm backward at the end; the weight gradients read the stored dz / h rows
+    denc = []
     for m, (t, e) in enumerate(zip(T["enc"], L.enc)):
         dEm = dE[:, m * ENC:(m + 1) * ENC]
         hs, nres = t["h"], len(e.res)
-        layers, part = [], Part(e.out, dw=(dEm, hs[-1], e.out), res_dup=int(nres > 0))
+        layers, part, dzs = [], Part(e.out, dw=(dEm, hs[-1], e.out), res_dup=int(nres > 0)), []
         for l in reversed(range(nres)):
             dz = new(B, ENC)
             layers.append(Layer([part], lnb=(e.res[l], t["y"][l], *t["st"][l], dz, sc), dw=[(dz, hs[l], e.res[l])]))
+            dzs.append(dz)
             part = Part(e.res[l], res_add=1, res_dup=int(l > 0))
         dz0 = new(B, ENC)
         layers.append(Layer([part], lnb=(e.stem, t["y0"], t["m0"], t["r0"], dz0, 1.0), dw=[(dz0, t["xin"], e.stem)]))
         run.bwd(dEm, B, layers)
+        denc.append({"dz": dzs[::-1], "dz0": dz0})               # dz[l]: of residual block l
+    if keep:
+        T["bwd"] = dict(dev_=dev_, dH3=dH3, dH0=dH0, dfused=dfused, dG=dG, dZ4=dZ4, dav_a=dav_a, dz0_tri=dz0_tri, dT=dT, dT2=dT2, dtext=dtext,
+                        tmp=tmp, dz4_av=dz4_av, dz0_av=dz0_av, dAV=dAV, dS_a=dS_a, dX=dX, dpre=dpre, dlog8=dlog8, dz8e=dz8e, dh2=dh2, unc8=unc8,
+                        dS_b=dS_b, dS=dS, dH1=dH1, dE_est=dE_est, dVV=dVV, dE_v=dE_v, dE=dE, enc=denc)
     if flat is not None:
         ex.flush_dw()
         ex.deferred = None
