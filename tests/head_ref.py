@@ -6,7 +6,11 @@ rounded to fp32 before alpha - 1 is formed, as every fp32 implementation does: b
 is exactly 0 and the uncertainties are inf.  Runs on whatever device its tensors are on.  A helper module, not a test module;
 it also holds the case tables of tests/golden/deer_head.npz and the gradient checker of its tests.
 
-``rnd``: optional rounding (e.g. ``bf16``) applied where the HIP path stores bf16: the input, the weights and each hidden layer."""
+``rnd``: optional rounding (e.g. ``bf16``) applied where the HIP path stores bf16: the input, the weights and each hidden layer
+going forward; coming back the gradient at each hidden layer, its masked form and dX.
+
+``masks``: the dropout decisions of a training forward, float64 keep * scale per site (``sites_layer`` / ``sites_multi`` list
+them, temporal_ref.draw draws them); None is evaluation mode."""
 from __future__ import annotations
 
 import numpy as np
@@ -48,6 +52,23 @@ class _Round(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return g, None
+
+
+class _RoundGrad(torch.autograd.Function):
+    """identity; the gradient passing through is rounded (a gradient the HIP path stores in bf16)"""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.fn(g), None
+
+
+def _g(x, rnd):
+    return x if rnd is None else _RoundGrad.apply(x, rnd)
 
 
 def _f32(x: torch.Tensor) -> torch.Tensor:
@@ -126,27 +147,54 @@ def _tail_products(x, w, devid, mask_scale):
     return dx, dw, d.sum(0)
 
 
-def _lin(x, P, name, rnd, relu=True):
-    y = x @ _r(P[name + ".weight"], rnd).t() + P[name + ".bias"]
-    return _r(torch.relu(y), rnd) if relu else y
+def _lin(x, P, name, rnd, relu=True, keep=None):
+    y = _g(x, rnd) @ _r(P[name + ".weight"], rnd).t() + P[name + ".bias"]
+    if not relu:
+        return y                    # the tail operator: its evidence gradient stays fp32 (csrc/nig_tail.hip), only dx is stored
+    y = torch.relu(_g(y, rnd))
+    if keep is not None:
+        y = y * keep.to(y.device)
+    return _g(_r(y, rnd), rnd)
 
 
-def deer_layer(P: dict, x: torch.Tensor, prefix: str = "", rnd=None) -> dict:
-    """DEERLayer with dropout off; parameters under their state_dict names (+ prefix).  -> NIG_KEYS -> (B, output_dim)."""
+def sites_layer(B: int, hidden_dim: int, p: float) -> list:
+    """DEERLayer's two sites, (name, site, rows, cols, p): behind evidence_net.0 and evidence_net.3."""
+    from mmdeer import head
+    return [("ev0", head._SITE_EV0, B, hidden_dim, p), ("ev1", head._SITE_EV1, B, hidden_dim // 2, p)]
+
+
+def sites_multi(B: int, hidden_dim: int, emotion_dims: int, p: float) -> list:
+    """MultiDimensionalDEER's sites: the two shared layers, layer 0 of all heads as ONE (B, D hidden / 2) draw at _SITE_H0 (head d
+    in columns [d hidden / 2, (d + 1) hidden / 2)), layer 1 of head d its own (B, hidden / 4) draw at _SITE_H1 + d."""
+    from mmdeer import head
+    return ([("fp0", head._SITE_FP0, B, hidden_dim, p), ("fp1", head._SITE_FP1, B, hidden_dim, p),
+             ("h0", head._SITE_H0, B, emotion_dims * (hidden_dim // 2), p)] +
+            [(f"h1.{d}", head._SITE_H1 + d, B, hidden_dim // 4, p) for d in range(emotion_dims)])
+
+
+def deer_layer(P: dict, x: torch.Tensor, prefix: str = "", rnd=None, masks=None) -> dict:
+    """DEERLayer; parameters under their state_dict names (+ prefix); ``masks`` None or {"ev0", "ev1"}.
+    -> NIG_KEYS -> (B, output_dim)."""
     p = prefix + "evidence_net."
-    h = _lin(_r(x, rnd), P, p + "0", rnd)
-    h = _lin(h, P, p + "3", rnd)
+    m = masks or {}
+    h = _lin(_r(x, rnd), P, p + "0", rnd, keep=m.get("ev0"))
+    h = _lin(h, P, p + "3", rnd, keep=m.get("ev1"))
     e = _lin(h, P, p + "6", rnd, relu=False)
     return dict(zip(NIG_KEYS, nig(e.reshape(x.shape[0], -1, 4))))
 
 
-def multi_dim(P: dict, x: torch.Tensor, emotion_dims: int = 3, rnd=None) -> dict:
-    """MultiDimensionalDEER with dropout off -> the reference's output dictionary."""
-    f = _lin(_r(x, rnd), P, "feature_processor.0", rnd)
-    f = _lin(f, P, "feature_processor.3", rnd)
+def multi_dim(P: dict, x: torch.Tensor, emotion_dims: int = 3, rnd=None, masks=None) -> dict:
+    """MultiDimensionalDEER -> the reference's output dictionary; ``masks`` None or {"fp0", "fp1", "h0", "h1.<d>"}."""
+    m = masks or {}
+    f = _lin(_r(x, rnd), P, "feature_processor.0", rnd, keep=m.get("fp0"))
+    f = _lin(f, P, "feature_processor.3", rnd, keep=m.get("fp1"))
     out = {}
     for d, n in enumerate(DIM_NAMES[:emotion_dims]):
-        for k, v in deer_layer(P, f, f"deer_heads.{d}.", rnd).items():
+        hm = None
+        if masks is not None:
+            w = m["h0"].shape[1] // emotion_dims
+            hm = {"ev0": m["h0"][:, d * w:(d + 1) * w], "ev1": m[f"h1.{d}"]}
+        for k, v in deer_layer(P, f, f"deer_heads.{d}.", rnd, hm).items():
             out[f"{n}_{k}"] = v
     out["mu_all"] = torch.cat([out[f"{n}_mu"] for n in DIM_NAMES[:emotion_dims]], dim=1)
     out["uncertainty_all"] = torch.cat([out[f"{n}_uncertainty"] for n in DIM_NAMES[:emotion_dims]], dim=1)

@@ -1,0 +1,367 @@
+"""The references tests/test_gpu_dropstep.py holds the dropout training step of the audio, text and video encoders and of the
+stand-alone DEER heads to (tests/dropstep_ref.py and the training forms of temporal_ref / text_ref / video_ref / head_ref), checked on
+their own: no GPU, no launch.
+
+ * all-ones masks are the unmasked forward, bit for bit (outputs and gradients, float64 and bf16-emulating);
+ * with the masks of a step, outputs and autograd gradients equal an INDEPENDENT float64 composition of torch modules (two chained
+   one-layer nn.LSTM with the mask multiplied in between; nn.Conv1d / nn.BatchNorm1d in .train() / ReLU / mask; nn.Linear chains)
+   to a relative distance of 1e-12;
+ * every site mistake the modules could make moves the reference by at least ten times what the GPU test tolerates
+   (``test_step_test_is_sensitive``; the measured factors are in its docstring);
+ * no ReLU input that reaches a gradient lies within stackb_ref.RELU_BAND of zero at the chosen input seeds;
+ * the sites one step can draw are pairwise distinct, at the largest geometry the modules accept and across a ComposedDEER."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+from torch import nn
+
+from mmdeer import fusions, generic_fusion, head, side, temporal, text, video
+
+from . import dropstep_ref as D
+from . import head_ref, text_ref
+from .stackb_ref import RELU_BAND
+
+F64 = torch.float64
+AD = D.ADAPTERS
+
+
+def _ones(masks):
+    return {k: torch.ones_like(v) for k, v in masks.items()}
+
+
+# ------------------------------------------------------------------------------------------------------- masks = None is unchanged
+@pytest.mark.parametrize("emulate", [False, True], ids=["float64", "bf16"])
+@pytest.mark.parametrize("name", list(AD))
+def test_all_ones_masks_are_the_unmasked_form_exactly(name, emulate):
+    """The training form with every unit kept at scale 1 returns what the existing evaluation form returns, torch.equal (the video
+    encoder: the existing train=True form -- batch statistics and moved buffers are not dropout's doing)."""
+    ad = AD[name]
+    case = ad.cases[0]
+    none = {} if name == "video" else None
+    r0, r1 = D.ref_step(ad, case, none, emulate), D.ref_step(ad, case, _ones(ad.masks(case)), emulate)
+    for k in r0["out"]:
+        assert r0["out"][k].dtype == F64 and torch.equal(r0["out"][k], r1["out"][k]), k
+    for k, g in r0["grads"].items():
+        assert (g is None and r1["grads"][k] is None) or torch.equal(g, r1["grads"][k]), k
+    for k in r0["dx"]:
+        assert torch.equal(r0["dx"][k], r1["dx"][k]), k
+    for k in r0["buffers"]:
+        assert torch.equal(r0["buffers"][k], r1["buffers"][k]), k
+
+
+def test_masks_none_is_the_evaluation_mode_of_the_video_reference():
+    ad = AD["video"]
+    case = ad.cases[0]
+    r = D.ref_step(ad, case, None)
+    P = D._params(ad.state(case))
+    assert all(torch.equal(r["buffers"][k], P[k]) for k in r["buffers"])                  # running statistics read, not moved
+    assert not torch.equal(r["out"]["out"], D.ref_step(ad, case, {})["out"]["out"])
+
+
+def test_the_draw_is_keep_times_the_float32_scale():
+    for p in (0.3, 0.5):
+        m = D.temporal_ref.drop_mask(120, 37, 512, p, D.DROP_SEED, D.STEP)
+        scale = float(np.float32(1.0 / (1.0 - float(np.float32(p)))))
+        assert m.dtype == F64 and set(m.unique().tolist()) == {0.0, scale}
+        assert abs(float((m > 0).double().mean()) - (1 - p)) < 0.02
+        assert not torch.equal(m, D.temporal_ref.drop_mask(120, 37, 512, p, D.DROP_SEED, D.STEP + 1))
+
+
+# ------------------------------------------------------------------------------------------------------- independent composition
+def _load(m, sd):
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=False)
+    return m.double()
+
+
+def _attn(seq, h):
+    a = seq(h)                                                   # Linear, Tanh, Linear, Softmax(dim=1) -> (B, T, 1)
+    return (a * h).sum(1)
+
+
+def _audio_torch(ad, case, X, masks):
+    B, T, _ = case
+    m = _load(side.EnhancedAudioEncoder(), ad.state(case))
+    layers = [nn.LSTM(84, 256, 1, batch_first=True, bidirectional=True).double(), nn.LSTM(512, 256, 1, batch_first=True, bidirectional=True).double()]
+    names = {}
+    for l, lstm in enumerate(layers):
+        for n, p in lstm.named_parameters():
+            src = n.replace("_l0", f"_l{l}")
+            p.data.copy_(getattr(m.lstm, src).data)
+            names["lstm." + src] = p
+    h = layers[0](X["x"])[0] * masks["inter.0"].reshape(T, B, 512).transpose(0, 1)
+    h = layers[1](h)[0]
+    op = m.output_projection
+    y = op[4](op[3](torch.relu(op[0](_attn(m.attention, h))) * masks["op"]))
+    params = {n: p for n, p in m.named_parameters() if not n.startswith("lstm.")}
+    params.update(names)
+    return {"out": y}, params, {}
+
+
+def _text_torch(ad, case, X, masks):
+    m = _load(text.TemporalTextEncoder(), ad.state(case))
+    ids, mask = X["ids"], X["mask"]
+    keep = (mask != 0).double().unsqueeze(-1)
+    if ad.by_ids:
+        x = (m.embedding(ids.clamp(0, m.vocab_size - 1)) + m.positional_encoding(torch.arange(ids.shape[1]).clamp(max=m.max_length - 1))[None]) * keep
+    else:
+        x = X["E"] * keep
+    ta = m.token_attention
+    pm = torch.softmax(ta[2](torch.tanh(ta[0](x)))[..., 0], dim=1) * keep[..., 0]
+    a = pm / (pm.sum(1, keepdim=True) + 1e-10)
+    att = (a.unsqueeze(-1) * x).sum(1)
+    f = text_ref.stats(ids if not ad.by_ids else ids.clamp(0, m.vocab_size - 1), mask, m.max_length)[0]
+    pb = torch.relu(m.bert_projection[0](att)) * masks["bert"]
+    pl = torch.relu(m.linguistic_projection[0](f)) * masks["ling"]
+    op = m.output_projection
+    return {"out": op[3](torch.relu(op[0](torch.cat([pb, pl], 1))) * masks["out"])}, dict(m.named_parameters()), {}
+
+
+def _video_torch(ad, case, X, masks):
+    B, T, _ = case
+    m = _load(video.TemporalVideoEncoder(), ad.state(case)).train()
+    m.temporal_cnn[1].num_batches_tracked.zero_()
+    m.temporal_cnn[5].num_batches_tracked.zero_()
+    bt = lambda k: masks[k].reshape(T, B, 512).transpose(0, 1)                     # noqa: E731  time-major rows -> (B, T, C)
+    h = torch.relu(m.spatial_projection[0](X["x"])) * bt("sp")
+    if T > 1:
+        cnn = m.temporal_cnn
+        c = torch.relu(cnn[1](cnn[0](h.transpose(1, 2)))) * bt("cnn").transpose(1, 2)
+        c = torch.relu(cnn[5](cnn[4](c))).transpose(1, 2)
+        agg = _attn(m.temporal_attention, c)
+    else:
+        agg = h[:, 0]
+    op = m.output_projection
+    y = op[3](torch.relu(op[0](agg)) * masks["op"])
+    buffers = {k: v.double() for k, v in m.state_dict().items() if "running_" in k and k.startswith("temporal_cnn.")}
+    buffers.update({k: v.double() for k, v in m.state_dict().items() if k.endswith("num_batches_tracked") and k.startswith("temporal_cnn.")})
+    return {"out": y}, {n: p for n, p in m.named_parameters() if not n.startswith("spatial_backbone.")}, buffers
+
+
+def _nig_torch(e):
+    sp = lambda t: nn.functional.softplus(t, threshold=20.0)                          # noqa: E731
+    mu, nu, beta = e[..., 0], sp(e[..., 1]) + 1e-6, sp(e[..., 3]) + 1e-6
+    alpha = sp(e[..., 2]) + 1.0
+    alpha = alpha + (alpha.float().double() - alpha).detach()                         # alpha as fp32 stores it (head_ref's statement)
+    alea = beta / (alpha - 1.0)
+    epi = beta / (nu * (alpha - 1.0))
+    return dict(zip(head_ref.NIG_KEYS, (mu, nu, alpha, beta, alea, epi, alea + epi)))
+
+
+def _net_torch(net, x, k0, k1):
+    h = torch.relu(net[0](x)) * k0
+    h = torch.relu(net[3](h)) * k1
+    return _nig_torch(net[6](h).reshape(x.shape[0], -1, 4))
+
+
+def _layer_torch(ad, case, X, masks):
+    I, O_, Hd = ad.geometry(case)
+    m = _load(head.DEERLayer(I, output_dim=O_, hidden_dim=Hd), ad.state(case))
+    return _net_torch(m.evidence_net, X["x"], masks["ev0"], masks["ev1"]), dict(m.named_parameters()), {}
+
+
+def _multi_torch(ad, case, X, masks):
+    I, Dm, Hd = ad.geometry(case)
+    m = _load(head.MultiDimensionalDEER(I, emotion_dims=Dm, hidden_dim=Hd), ad.state(case))
+    fp = m.feature_processor
+    f = torch.relu(fp[3](torch.relu(fp[0](X["x"])) * masks["fp0"])) * masks["fp1"]
+    out, w = {}, Hd // 2
+    for d, n in enumerate(head_ref.DIM_NAMES[:Dm]):
+        for k, v in _net_torch(m.deer_heads[d].evidence_net, f, masks["h0"][:, d * w:(d + 1) * w], masks[f"h1.{d}"]).items():
+            out[f"{n}_{k}"] = v
+    out["mu_all"] = torch.cat([out[f"{n}_mu"] for n in head_ref.DIM_NAMES[:Dm]], 1)
+    out["uncertainty_all"] = torch.cat([out[f"{n}_uncertainty"] for n in head_ref.DIM_NAMES[:Dm]], 1)
+    return out, dict(m.named_parameters()), {}
+
+
+TORCH = {"audio": _audio_torch, "text_embeddings": _text_torch, "text_ids": _text_torch, "video": _video_torch,
+         "deer_layer": _layer_torch, "multi_dim": _multi_torch}
+
+
+@pytest.mark.parametrize("name,case", D.ALL_CASES, ids=D.CASE_IDS)
+def test_masked_reference_equals_an_independent_torch_composition(name, case):
+    ad = AD[name]
+    masks = ad.masks(case)
+    r = D.ref_step(ad, case, masks)
+    X = {k: torch.from_numpy(v) for k, v in ad.inputs(case, ad.seed(case)).items()}
+    X = {k: v.double().requires_grad_(True) if k in ad.diff_inputs else v for k, v in X.items()}
+    outs, params, buffers = TORCH[name](ad, case, X, masks)
+    assert list(outs) == list(r["out"])
+    W = ad.weights(case, outs)
+    sum((outs[k] * W[k]).sum() for k in outs).backward()
+    worst = 0.0
+    for k in outs:
+        worst = max(worst, D.rel(outs[k], r["out"][k]))
+        assert D.rel(outs[k], r["out"][k]) <= 1e-12, k
+    live = 0
+    for k, g in r["grads"].items():
+        if g is None:
+            assert params[k].grad is None or not bool(params[k].grad.any()), k
+            continue
+        if k in ad.zero_grads or k in ad.noise_grads or not bool(g.any()):        # analytic zeros: noise (or nothing) on both sides
+            scale = float(r["grads"][k.replace("bias", "weight")].abs().max()) if k.endswith("bias") else 1.0
+            assert float(g.abs().max()) <= 1e-9 * scale and (params[k].grad is None or float(params[k].grad.abs().max()) <= 1e-9 * scale), k
+            continue
+        live += 1
+        worst = max(worst, D.rel(params[k].grad, g))
+        assert D.rel(params[k].grad, g) <= 1e-12, k
+    assert live >= 6
+    for k in ad.diff_inputs:
+        worst = max(worst, D.rel(X[k].grad, r["dx"][k]))
+        assert D.rel(X[k].grad, r["dx"][k]) <= 1e-12, k
+    if name == "video" and case[1] > 1:
+        assert len(buffers) == 6
+        for k, v in buffers.items():
+            assert D.rel(v, r["buffers"][k]) <= 1e-12, k
+    print(f"{name} {case}: largest relative distance {worst:.1e}")
+
+
+# ------------------------------------------------------------------------------------------------------------------- sensitivity
+def _renumber(which, to):
+    def f(ad, case, sites, masks):
+        s2 = [(n, to(s) if n == which else s, r, c, p) for n, s, r, c, p in sites]
+        return ad.masks(case, sites=s2)
+    return f
+
+
+def _next_step(ad, case, sites, masks):
+    return ad.masks(case, step=D.STEP + 1)
+
+
+def _scale_one(ad, case, sites, masks):
+    return {k: (v > 0).double() for k, v in masks.items()}
+
+
+def _batch_major(which):
+    def f(ad, case, sites, masks):
+        B, T = case[0], case[1]
+        m = dict(masks)
+        m[which] = masks[which].reshape(B, T, -1).transpose(0, 1).reshape(T * B, -1)      # the unit (b, t) takes the draw of row b * T + t
+        return m
+    return f
+
+
+def _second_batchnorm(ad, case, sites, masks):
+    return dict(masks, cnn2=masks["cnn"])
+
+
+def _exchange(a, b):
+    def f(ad, case, sites, masks):
+        num = {n: s for n, s, *_ in sites}
+        return ad.masks(case, sites=[(n, num[b] if n == a else num[a] if n == b else s, r, c, p) for n, s, r, c, p in sites])
+    return f
+
+
+def _global_columns(ad, case, sites, masks):
+    _, Dm, Hd = ad.geometry(case)
+    w = Hd // 4
+    wide = ad.masks(case, sites=[(n, s, r, Dm * w, p) for n, s, r, c, p in sites if n.startswith("h1.")])
+    return dict(masks, **{f"h1.{d}": wide[f"h1.{d}"][:, d * w:(d + 1) * w] for d in range(Dm)})
+
+
+def _heads_rotated(ad, case, sites, masks):
+    Dm = ad.geometry(case)[1]
+    return ad.masks(case, sites=[(n, head._SITE_H1 + (int(n[3:]) + 1) % Dm if n.startswith("h1.") else s, r, c, p) for n, s, r, c, p in sites])
+
+
+def _mutations(name, case):
+    ad = AD[name]
+    out = {f"{n} at the neighbouring site": _renumber(n, lambda s: s + 1) for n, *_ in ad.sites(case)}
+    out.update({"step + 1": _next_step, "scale 1": _scale_one})
+    if name in ("audio", "video") and case[1] > 1:
+        for n in (("inter.0",) if name == "audio" else ("sp", "cnn")):
+            out[f"{n} batch-major"] = _batch_major(n)
+    if name == "video" and case[1] > 1:
+        out["a mask on the second BatchNorm layer too"] = _second_batchnorm
+    if name.startswith("text"):
+        out["bert and ling exchanged"] = _exchange("bert", "ling")
+    if name == "multi_dim":
+        out["heads' layer-1 columns indexed globally"] = _global_columns
+        out["head d at head d + 1's site"] = _heads_rotated
+    return out
+
+
+SENSITIVITY_CASES = [("audio", (5, 3, 0.3)), ("audio", (5, 1, 0.3)), ("text_embeddings", (5, 7, 0.3)), ("text_ids", (5, 7, 0.3)),
+                     ("video", (5, 3, 0.3)), ("video", (5, 1, 0.3)), ("deer_layer", ("dl96x3x64", 5, 0.3)), ("multi_dim", ("md192x3x128", 5, 0.3))]
+
+
+def _moved(ad, base, r2):
+    """the largest fraction of a test-A bound by which a compared quantity moved"""
+    worst = ("", 0.0)
+    for k, v in base["out"].items():
+        if bool(torch.isfinite(v).all()):
+            worst = max(worst, (f"output {k}", D.out_fraction(r2["out"][k], v)), key=lambda t: t[1])
+    for k, g in list(base["grads"].items()) + [("input " + k, v) for k, v in base["dx"].items()]:
+        g2 = r2["grads"][k] if k in r2["grads"] else r2["dx"][k[6:]]
+        if g is None or k in ad.zero_grads or k in ad.noise_grads or not bool(g.any()):
+            continue
+        worst = max(worst, (k, D.grad_fraction(g2, g)), key=lambda t: t[1])
+    # the video encoder's output and gradients do not see a common factor on a mask (BatchNorm and LayerNorm divide it out): its
+    # running statistics do
+    for k, v in base["buffers"].items():
+        if "running_" in k:
+            worst = max(worst, (k, D.buffer_fraction(r2["buffers"][k], v)), key=lambda t: t[1])
+    return worst
+
+
+@pytest.mark.parametrize("name,case", SENSITIVITY_CASES, ids=[f"{n}-{AD[n].case_id(c)}" for n, c in SENSITIVITY_CASES])
+def test_step_test_is_sensitive(name, case):
+    """Each mistake moves at least one quantity test A compares by at least 10 x its bound there.  Measured (the smallest factor over
+    the case's mutations, and the mutation that gives it; pytest -s prints all of them):
+    audio 5 x 3: 22265 (inter-layer rows batch-major); audio 5 x 1: 22465 (scale 1); text by embeddings: 2629 (scale 1); text by ids:
+    17674 (scale 1); video 5 x 3: 24356 (output_projection's site + 1; scale 1 shows only in the running buffers, by 100288); video
+    5 x 1: 1518 (scale 1); DEERLayer: 1853 (scale 1); MultiDimensionalDEER: 1782 (head 1's layer-1 site + 1)."""
+    ad = AD[name]
+    sites, masks = ad.sites(case), ad.masks(case)
+    base = D.ref_step(ad, case, masks)
+    least = None
+    for what, mutate in _mutations(name, case).items():
+        m2 = mutate(ad, case, copy.deepcopy(sites), masks)
+        assert set(m2) >= set(masks)
+        k, f = _moved(ad, base, D.ref_step(ad, case, m2))
+        print(f"{name} {case}: {what}: {k} moved by {f:.0f} x its bound")
+        assert f >= 10.0, (what, k, f)
+        least = (what, f) if least is None or f < least[1] else least
+    print(f"{name} {case}: least {least[1]:.0f} x ({least[0]})")
+
+
+# ------------------------------------------------------------------------------------------------------------------- ReLU band
+@pytest.mark.parametrize("name,case", D.ALL_CASES, ids=D.CASE_IDS)
+def test_no_relu_input_of_a_case_lies_in_the_band(name, case):
+    """At the chosen input seed no ReLU input of the float64 step that reaches a gradient lies within RELU_BAND (1e-5 of the layer's
+    largest input) of zero, so test A compares gradients across decisions both sides take alike, and needs no disputed-unit rule.
+    The seed is the first from 0 with that property (seed 0 for 13 of the 20 cases, 1 for six; the video encoder's 37 x 3 case, with
+    150 k such units, had 3 .. 11 of them in the band at seeds 0 .. 34 and none at 35)."""
+    ad = AD[name]
+    assert D.band_count(ad, case, ad.seed(case), RELU_BAND) == 0
+    if ad.seed(case) > 0 and case[0] != 37:
+        assert D.band_count(ad, case, ad.seed(case) - 1, RELU_BAND) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- disjoint sites
+def test_sites_of_one_step_are_pairwise_distinct():
+    """Within a module at the largest num_layers / emotion_dims it accepts, and across everything one model's step can combine: the
+    three encoders, a fusion module and a head (ComposedDEER) -- two draws at one site with one seed and step are the same mask."""
+    L = side.MAX_LSTM_LAYERS
+    with pytest.raises(NotImplementedError):
+        side.EnhancedAudioEncoder({"num_layers": L + 1})
+    with pytest.raises(NotImplementedError):
+        temporal.TemporalAudioEncoder({"num_layers": L + 1})
+    with pytest.raises(NotImplementedError):
+        head.MultiDimensionalDEER(64, emotion_dims=4)
+    audio_seq = [s for _, s, *_ in D.temporal_ref.sites(5, 3, 0.3, num_layers=L)]
+    audio_one = [s for _, s, *_ in D.temporal_ref.sites(5, 1, 0.3, num_layers=L)]
+    txt = [s for _, s, *_ in text_ref.sites(5, 512, 0.3)]
+    vid = [s for _, s, *_ in D.video_ref.sites(5, 3, 0.3)]
+    layer = [s for _, s, *_ in head_ref.sites_layer(5, 1024, 0.3)]
+    multi = [s for _, s, *_ in head_ref.sites_multi(5, 2048, 3, 0.3)]
+    assert len(audio_seq) == len(audio_one) == L and len(multi) == 6
+    for one in (audio_seq, audio_one, txt, vid, layer, multi):
+        assert len(set(one)) == len(one), one
+    fusion = [fusions._SITE_ENC, fusions._SITE_CONCAT, generic_fusion._SITE_AV, generic_fusion._SITE_AVF, generic_fusion._SITE_TRI_ATTN,
+              generic_fusion._SITE_TRIF, generic_fusion._SITE_OUT]
+    # audio_seq and audio_one share _SITE_OP: one encoder runs one of the two paths per forward
+    everything = sorted(set(audio_seq) | set(audio_one)) + txt + vid + layer + multi + fusion
+    assert len(set(everything)) == len(everything), sorted(everything)
+    assert max(everything) < 256 and min(everything) > 9              # 1 .. 9: the fused model's own sites

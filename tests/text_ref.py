@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from .temporal_ref import _Round, bf16  # noqa: F401  (bf16: for the tests that import this module)
+from .temporal_ref import _Round, _RoundGrad, bf16, draw, layer_norm  # noqa: F401  (bf16, draw: for the tests that import this module)
 
 EPS = 1e-10
 
@@ -70,33 +70,57 @@ def stats(ids, mask, max_length):
     return out, counts
 
 
-def _linear(x, P, name, emulate, relu=False):
-    y = _r(x, emulate) @ _r(P[name + ".weight"], emulate).t() + P[name + ".bias"]
-    return _r(torch.relu(y) if relu else y, emulate)
+def _g(x, emulate):
+    """a gradient the HIP path stores in bf16 on its way back (identity going forward)"""
+    return _RoundGrad.apply(x) if emulate else x
 
 
-def tail(P, x, ids_stats, mask, max_length=128, emulate_bf16=False):
-    """From the masked rows x (B, L, E): pool, projections, LayerNorm.  Returns (output (B, H), weights (B, L), features (B, 10))."""
+def _linear(x, P, name, emulate, relu=False, keep=None):
+    """drop?(relu?(x W^T + b)); ``keep``: float64 keep * scale or None.  The bf16 form rounds what fusions._LinearFn stores: x, W
+    and the output; coming back the incoming gradient, the masked gradient ``ga`` and dX."""
+    y = _g(_g(_r(x, emulate), emulate) @ _r(P[name + ".weight"], emulate).t() + P[name + ".bias"], emulate)
+    y = torch.relu(y) if relu else y
+    if keep is not None:
+        y = y * keep.to(y.device)
+    return _g(_r(y, emulate), emulate)
+
+
+def sites(B: int, hidden_dim: int, p: float) -> list:
+    """The three sites one training forward of TemporalTextEncoder draws, (name, site, rows, cols, p): the reference's three
+    nn.Dropout modules, each on B rows (see temporal_ref.draw)."""
+    from mmdeer import text
+    return [("bert", text._SITE_BERT, B, hidden_dim, p), ("ling", text._SITE_LING, B, hidden_dim // 4, p), ("out", text._SITE_OUT, B, hidden_dim, p)]
+
+
+def tail(P, x, ids_stats, mask, max_length=128, emulate_bf16=False, masks=None):
+    """From the masked rows x (B, L, E): pool, projections, LayerNorm.  ``masks`` None: evaluation mode; given ({"bert", "ling",
+    "out"}: float64 keep * scale, see ``sites``): the training forward with those dropout decisions.
+    Returns (output (B, H), weights (B, L), features (B, 10))."""
     e = emulate_bf16
+    k = (lambda n: None) if masks is None else (lambda n: masks[n])
+    x = _g(x, e)                                                       # dx of mmdeer_token_pool_bwd + dX of the W1 GEMM, summed, as bf16
     z = _linear(x, P, "token_attention.0", e)
-    att, a, _ = masked_pool(x, z, mask, P["token_attention.2.weight"], P["token_attention.2.bias"])
-    pb = _linear(_r(att, e), P, "bert_projection.0", e, relu=True)
+    att, a, _ = masked_pool(_g(x, e), z, mask, P["token_attention.2.weight"], P["token_attention.2.bias"])
+    pb = _linear(_g(_r(att, e), e), P, "bert_projection.0", e, relu=True, keep=k("bert"))
     f, _ = stats(ids_stats, mask, max_length)
     f = f.to(x.device).to(x.dtype)
-    pl = _linear(f, P, "linguistic_projection.0", e, relu=True)
-    y = _linear(torch.cat([pb, pl], dim=1), P, "output_projection.0", e, relu=True)
-    y = torch.nn.functional.layer_norm(y, (y.shape[1],), P["output_projection.3.weight"], P["output_projection.3.bias"], 1e-5)
+    pl = _linear(f, P, "linguistic_projection.0", e, relu=True, keep=k("ling"))
+    y = _linear(torch.cat([pb, pl], dim=1), P, "output_projection.0", e, relu=True, keep=k("out"))
+    # the bf16 form rounds the LayerNorm rows too: side._LayerNormFn stores them in the compute dtype
+    y = layer_norm(y, P["output_projection.3.weight"], P["output_projection.3.bias"], e)
     return y, a, f
 
 
-def encoder(P, ids, mask, max_length=128, emulate_bf16=False):
-    """Eval-mode forward(ids, mask) of the no-BERT encoder, parameters under their state_dict names."""
+def encoder(P, ids, mask, max_length=128, emulate_bf16=False, masks=None):
+    """forward(ids, mask) of the no-BERT encoder, parameters under their state_dict names; evaluation mode, or with ``masks`` the
+    training forward (see ``tail``)."""
     V = P["embedding.weight"].shape[0]
     x = gather(ids, mask, P["embedding.weight"], P["positional_encoding.weight"], emulate_bf16)
-    return tail(P, x, ids.clamp(0, V - 1), mask, max_length, emulate_bf16)
+    return tail(P, x, ids.clamp(0, V - 1), mask, max_length, emulate_bf16, masks)
 
 
-def encoder_embeddings(P, E, ids, mask, max_length=128, emulate_bf16=False):
-    """Eval-mode BERT branch downstream of last_hidden_state: E (B, L, 768) contextual embeddings, ids unclamped (statistics only)."""
+def encoder_embeddings(P, E, ids, mask, max_length=128, emulate_bf16=False, masks=None):
+    """BERT branch downstream of last_hidden_state: E (B, L, 768) contextual embeddings, ids unclamped (statistics only);
+    evaluation mode, or with ``masks`` the training forward (see ``tail``)."""
     x = _r(E * (mask != 0).to(E.dtype).unsqueeze(-1), emulate_bf16)
-    return tail(P, x, ids, mask, max_length, emulate_bf16)
+    return tail(P, x, ids, mask, max_length, emulate_bf16, masks)

@@ -225,6 +225,10 @@ class EnhancedAudioEncoder(nn.Module):
         self.dropout_seed, self._train_step = config.get("dropout_seed", 0), 0     # counter-hash dropout: seed + one tick per training forward
         if not self.bidirectional or self.hidden_dim % 8:
             raise NotImplementedError("built for the reference default: bidirectional, hidden_dim % 8 == 0")
+        if not 1 <= self.num_layers <= MAX_LSTM_LAYERS:
+            # the inter-layer dropout of layer l draws at site _SITE_LSTM + l (T > 1: temporal._SITE_SEQ + l); a tenth layer's site
+            # would be _SITE_OP itself (the same (B, 512) mask twice in one step) and, on the sequence path, the text encoder's first
+            raise NotImplementedError(f"num_layers = {self.num_layers}: must be in [1, {MAX_LSTM_LAYERS}] (one dropout site per inter-layer gap)")
         self.lstm = nn.LSTM(input_size=84, hidden_size=self.hidden_dim // 2, num_layers=self.num_layers, batch_first=True,
                             dropout=self.dropout if self.num_layers > 1 else 0, bidirectional=True)
         self.attention = nn.Sequential(nn.Linear(self.hidden_dim, self.hidden_dim // 2), nn.Tanh(),
@@ -273,6 +277,7 @@ class EnhancedAudioEncoder(nn.Module):
 
 
 _SITE_LSTM, _SITE_OP = 112, 120
+MAX_LSTM_LAYERS = 9      # inter-layer sites _SITE_LSTM + 0 .. 7 stay below _SITE_OP, temporal._SITE_SEQ + 0 .. 7 below text._SITE_BERT
 
 
 class _ZeroGradFn(torch.autograd.Function):
