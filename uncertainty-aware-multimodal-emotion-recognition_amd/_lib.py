@@ -81,6 +81,11 @@ _BERT_NAMES = {"mmdeer_bert_embed_args": "BertEmbedArgs", "mmdeer_bert_attn_args
 BERT_CONSTANTS, _BERT_CLASSES, BERT_SYMBOLS = _header.parse(_header.read(_header.BERT_HEADER_PATH), _BERT_NAMES, {})
 globals().update({cls.__name__: cls for cls in _BERT_CLASSES.values()})    # BertEmbedArgs, BertAttnArgs, BertAddLnArgs, BertGeluArgs
 BERT_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _BERT_CLASSES.items()}
+# include/mmdeer_bert_bwd.h, the companion header of the BERT trunk's backward operators: tables of its own again
+_BERT_BWD_NAMES = {"mmdeer_bert_attn_bwd_args": "BertAttnBwdArgs", "mmdeer_bert_add_ln_bwd_args": "BertAddLnBwdArgs", "mmdeer_bert_gelu_bwd_args": "BertGeluBwdArgs"}
+BERT_BWD_CONSTANTS, _BERT_BWD_CLASSES, BERT_BWD_SYMBOLS = _header.parse(_header.read(_header.BERT_BWD_HEADER_PATH), _BERT_BWD_NAMES, {})
+globals().update({cls.__name__: cls for cls in _BERT_BWD_CLASSES.values()})    # BertAttnBwdArgs, BertAddLnBwdArgs, BertGeluBwdArgs
+BERT_BWD_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _BERT_BWD_CLASSES.items()}
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -95,7 +100,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -129,7 +134,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         lib = bind(C.CDLL(path), require_all=True)
         if lib.mmdeer_abi_version() != ABI_VERSION:
             raise RuntimeError("libmmdeer_hip.so ABI version mismatch")
-        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
+        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS, **BERT_BWD_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
             if lib.mmdeer_sizeof(cname.encode()) != C.sizeof(cls):
                 raise RuntimeError(f"mmdeer: ctypes layout of mmdeer_{cname} ({C.sizeof(cls)} bytes) differs from the library's "
                                    f"({lib.mmdeer_sizeof(cname.encode())})")

@@ -1,6 +1,6 @@
 """The BERT trunk of the text encoder: ``transformers.BertModel`` as the reference's ``EnhancedTextEncoder`` instantiates it
-(reference src/models/encoders.py:553-761, ``self.bert``), forward only, on HIP.  ``BertEncoder`` has the parameters of
-``BertModel`` under the same names and shapes, so a checkpoint of the reference's ``self.bert`` loads with ``strict=True``;
+(reference src/models/encoders.py:553-761, ``self.bert``) on HIP: the forward, and with ``finetune_layers=k`` the backward of its last
+``k`` layers.  ``BertEncoder`` has the parameters of ``BertModel`` under the same names and shapes, so a checkpoint of the reference's ``self.bert`` loads with ``strict=True``;
 tokenisation and pretrained weights stay outside this package (no ``from_pretrained`` here: build from a config, load a state dict).
 
 Per forward 1 + 8 * layers launches on the current stream, no host synchronisation and no ``.item()``, so a forward can be
@@ -17,12 +17,45 @@ captured with ``torch.cuda.graph`` (run one forward before the capture: it build
       mmdeer_gemm             y = h Wo2^T + bo2
       mmdeer_bert_add_ln_fwd  x = LayerNorm(y + x)
 
-The trunk is FROZEN: every parameter is created with ``requires_grad=False``, a call with grad enabled while a parameter requires
-grad raises, and the output carries no graph (its backward -- the reference fine-tunes layers 6-11 -- is not built).  A frozen
-trunk is an eval trunk: there is NO dropout inside it in either mode (``.train()`` changes nothing).  The pooler's parameters are
-kept for the checkpoint and never read.  One deviation from ``BertModel``: a sample whose mask has no valid token gets zeros
-from every attention layer where the reference averages V uniformly (include/mmdeer_bert.h); everything downstream of the trunk
-multiplies by the mask.  Masks are binary (nonzero = valid).  No CPU path: CPU tensors raise."""
+By default (``finetune_layers=0``) the trunk is FROZEN: every parameter is created with ``requires_grad=False``, a call with grad
+enabled while a parameter requires grad raises, and the output carries no graph.  The pooler's parameters are kept for the
+checkpoint and never read.
+
+``BertEncoder(config, compute_dtype, finetune_layers=k)``, 1 <= k <= num_hidden_layers, fine-tunes the last ``k`` layers (the
+reference's ``_setup_bert_fine_tuning`` freezes the embeddings and layers 0-5 of 12 and trains layers 6-11: k = 6).  Their
+parameters are created with ``requires_grad=True``; the embeddings, the layers below and the pooler stay frozen, and a call with
+grad enabled raises ``ValueError`` naming the parameter when one of those requires grad.  With grad enabled the layers below the
+tail run as ever under ``no_grad`` and the tail is ONE autograd node (``_TailFn``) over all its layers.  Its forward issues the
+same launches on the same packed operands and only writes to fresh buffers where the forward-only path overwrites (x1 no longer
+takes y's buffer, the GELU is not in place), so ``last_hidden_state`` is bit-equal to the frozen trunk's.  It keeps per tail layer
+x, qkv, ctx, y, x1, the pre-GELU h, gelu(h) and y2 on the tape: 8 H + 2 I elements per token, 100 MB per layer at 4096 tokens of
+BERT-base in bf16 (12 288 elements x 4096 x 2 bytes), 600 MB for k = 6; a layer's tape is released as the backward leaves it.
+The backward, per tail layer from the top, given g (the gradient of the layer's output) and g2 (None at the top):
+
+    mmdeer_bert_add_ln_bwd   (g, g2; y2, x1, gamma2) -> ds2, dgamma2, dbeta2            (include/mmdeer_bert_bwd.h)
+    mmdeer_gemm              dWo2 = ds2^T gelu(h), dbo2 from the same launch (bias_grad)
+    mmdeer_gemm              dh = ds2 Wo2
+    mmdeer_bert_gelu_bwd     dh' = dh gelu'(h), in place
+    mmdeer_gemm              dWi = dh'^T x1, dbi
+    mmdeer_gemm              dx1 = dh' Wi
+    mmdeer_bert_add_ln_bwd   (dx1, ds2; y, x, gamma1) -> ds1, dgamma1, dbeta1
+    mmdeer_gemm              dWo = ds1^T ctx, dbo
+    mmdeer_gemm              dctx = ds1 Wo
+    mmdeer_bert_attn_bwd     dqkv  (two launches)
+    mmdeer_gemm              dWqkv [3H, H] = dqkv^T x, dbqkv: returned as the row slices of query / key / value
+    mmdeer_gemm              dx = dqkv Wqkv, only above the lowest tail layer; the next layer starts with g = dx, g2 = ds1
+
+Activation gradients are stored in the compute dtype; parameter gradients are summed in fp32 in a fixed order (no atomics: two
+backward runs store the same bits) and returned in the parameters' dtype.  A tail parameter switched back to
+``requires_grad=False`` gets no gradient.  There is no gradient with respect to the ids, and ``hidden_states`` are graph-free copies.
+
+THE ONE DIFFERENCE in training: there is NO dropout inside the trunk in either mode (``.train()`` changes nothing).  The
+reference's BERT trains with ``hidden_dropout_prob = attention_probs_dropout_prob = 0.1``; this trunk fine-tunes as
+``BertConfig(hidden_dropout_prob=0, attention_probs_dropout_prob=0)`` does.
+
+One deviation from ``BertModel`` in the forward: a sample whose mask has no valid token gets zeros from every attention layer where
+the reference averages V uniformly (include/mmdeer_bert.h), and, mirrored in the backward, zeros in all of its dqkv; everything
+downstream of the trunk multiplies by the mask.  Masks are binary (nonzero = valid).  No CPU path: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -71,11 +104,16 @@ def _named(**children) -> nn.Module:
 
 
 class BertEncoder(nn.Module):
-    """``BertModel(BertConfig(**config))`` forward on HIP (the module docstring has the launch plan and what is not built)."""
+    """``BertModel(BertConfig(**config))`` on HIP; ``finetune_layers=k`` trains its last ``k`` layers (the module docstring has both
+    launch plans and what is not built)."""
 
-    def __init__(self, config=None, compute_dtype: str = "bf16"):
+    def __init__(self, config=None, compute_dtype: str = "bf16", finetune_layers: int = 0):
         super().__init__()
         c = self.config = _config(config)
+        if isinstance(finetune_layers, bool) or not isinstance(finetune_layers, int) or not 0 <= finetune_layers <= int(c["num_hidden_layers"]):
+            raise ValueError(f"BertEncoder: finetune_layers must be an integer in 0 .. num_hidden_layers = {int(c['num_hidden_layers'])} "
+                             f"(got {finetune_layers!r})")
+        self.finetune_layers = finetune_layers
         ops._act_dtype(compute_dtype)
         self.compute_dtype = compute_dtype
         H, I, heads = int(c["hidden_size"]), int(c["intermediate_size"]), int(c["num_attention_heads"])
@@ -107,6 +145,9 @@ class BertEncoder(nn.Module):
         self._init_weights(float(c["initializer_range"]))
         for p in self.parameters():
             p.requires_grad_(False)
+        for lyr in self.encoder.layer[len(self.encoder.layer) - finetune_layers:]:
+            for p in lyr.parameters():
+                p.requires_grad_(True)
         self._packed, self._packed_key = None, None
 
     @torch.no_grad()
@@ -128,17 +169,28 @@ class BertEncoder(nn.Module):
     def _operands(self):
         """The packed operands: the [3H, H] QKV weight and its bias, compute-dtype copies of the matrices, fp32 vectors.  Built once and
         rebuilt when a parameter changed: the key is every parameter's (_version, data_ptr), which an in-place update
-        (load_state_dict, an optimiser step) and a replaced storage (.to(), .data = ...) both move."""
-        key = tuple((p._version, p.data_ptr()) for p in self.parameters())
+        (load_state_dict, an optimiser step) and a replaced storage (.to(), .data = ...) both move.  The key is kept per layer and
+        for the embeddings, so a step on the tail repacks the tail's layers only: the returned dict is a new object whenever
+        anything changed, and holds the SAME entry for every layer (and the embeddings) that did not."""
+        dt = ops._act_dtype(self.compute_dtype)
+        stamp = lambda m: tuple((p._version, p.data_ptr()) for p in m.parameters())                        # noqa: E731
+        key = (dt, stamp(self.embeddings), tuple(stamp(lyr) for lyr in self.encoder.layer))
         if self._packed is not None and key == self._packed_key:
             return self._packed
-        dt = ops._act_dtype(self.compute_dtype)
+        same = self._packed is not None and self._packed_key[0] == dt
         mat = lambda *ws: torch.cat([w.detach() for w in ws], dim=0).to(dt).contiguous()                 # noqa: E731
         vec = lambda *vs: torch.cat([v.detach().reshape(-1) for v in vs], dim=0).float().contiguous()     # noqa: E731
         e = self.embeddings
-        packed = {"emb": tuple(t.detach().float().contiguous() for t in (e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight,
-                                                e.LayerNorm.weight, e.LayerNorm.bias)), "layers": []}
-        for lyr in self.encoder.layer:
+        if same and key[1] == self._packed_key[1]:
+            emb = self._packed["emb"]
+        else:
+            emb = tuple(t.detach().float().contiguous() for t in (e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight,
+                                                                  e.LayerNorm.weight, e.LayerNorm.bias))
+        packed = {"emb": emb, "layers": []}
+        for i, lyr in enumerate(self.encoder.layer):
+            if same and key[2][i] == self._packed_key[2][i]:
+                packed["layers"].append(self._packed["layers"][i])
+                continue
             s, so = getattr(lyr.attention, "self"), lyr.attention.output
             packed["layers"].append({
                 "wqkv": mat(s.query.weight, s.key.weight, s.value.weight), "bqkv": vec(s.query.bias, s.key.bias, s.value.bias),
@@ -172,9 +224,20 @@ class BertEncoder(nn.Module):
             raise ValueError(f"L = {L} is above max_position_embeddings = {self.config['max_position_embeddings']}")
         if L > MAX_TOKENS:
             raise ValueError(f"L = {L} is above the {MAX_TOKENS} tokens the attention kernel takes")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        nl = len(self.encoder.layer)
+        first_tail = nl - self.finetune_layers
+        tail = torch.is_grad_enabled() and self.finetune_layers > 0
+        if torch.is_grad_enabled() and self.finetune_layers == 0 and any(p.requires_grad for p in self.parameters()):
             raise ValueError("the BERT trunk is forward only: its backward is not built.  Keep its parameters at requires_grad=False "
-                             "(or call it under torch.no_grad())")
+                             "(or call it under torch.no_grad()), or build it with finetune_layers=k to train its last k layers")
+        if tail:
+            below = f"encoder.layer.{first_tail}."
+            for name, p in self.named_parameters():
+                if p.requires_grad and not (name.startswith("encoder.layer.") and int(name.split(".")[2]) >= first_tail):
+                    what = "an embedding parameter" if name.startswith("embeddings.") else f"a parameter outside the fine-tuned tail ({below}* and up)"
+                    raise ValueError(f"BertEncoder(finetune_layers={self.finetune_layers}): {name} requires grad, but it is {what}: only the last "
+                                     f"{self.finetune_layers} layers have a backward.  Set it to requires_grad=False")
+            tail = any(p.requires_grad for lyr in self.encoder.layer[first_tail:] for p in lyr.parameters())
         ops._check_dev(input_ids, attention_mask, token_type_ids, self.embeddings.word_embeddings.weight)
         dt, f32, H = ops._act_dtype(self.compute_dtype), int(self.compute_dtype == "fp32"), self.hidden_size
         dev = input_ids.device
@@ -201,7 +264,7 @@ class BertEncoder(nn.Module):
             at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
             ge = _lib.BertGeluArgs()
             ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), h.data_ptr(), M, I, I, I, f32, stream
-            for p in w["layers"]:
+            for p in w["layers"][:first_tail if tail else nl]:
                 ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=self.compute_dtype)
                 _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
                 ops.linear_into(ctx, p["wo"], p["bo"], y, compute=self.compute_dtype)
@@ -213,4 +276,137 @@ class BertEncoder(nn.Module):
                 if output_hidden_states:
                     states.append(x.clone())
             shaped = lambda t: t.reshape(B, L, H)             # noqa: E731
-            return BertEncoderOutput(shaped(x), tuple(shaped(s) for s in states) if output_hidden_states else None)
+            if not tail:
+                return BertEncoderOutput(shaped(x), tuple(shaped(s) for s in states) if output_hidden_states else None)
+        del qkv, ctx, h, y
+        params = [p for lyr in self.encoder.layer[first_tail:] for p in lyr.parameters()]
+        out = _TailFn.apply(self, x, m, B, L, w["layers"][first_tail:], states, *params)
+        return BertEncoderOutput(shaped(out), tuple(shaped(s) for s in states) if output_hidden_states else None)
+
+
+def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool):
+    """mmdeer_bert_add_ln_bwd -> (ds, dgamma, dbeta); the sums only when wanted"""
+    lib, (M, N) = _lib.load(), y.shape
+    ds = torch.empty_like(y)
+    dgamma = dbeta = scratch = None
+    a = _lib.BertAddLnBwdArgs()
+    if want_sums:
+        dgamma, dbeta = torch.empty(N, device=y.device), torch.empty(N, device=y.device)
+        a.scratch_elems = lib.mmdeer_bert_add_ln_bwd_scratch(M, N)
+        scratch = torch.empty(a.scratch_elems, device=y.device)
+    a.y, a.x, a.g, a.g2, a.gamma, a.ds = y.data_ptr(), x.data_ptr(), g.data_ptr(), _lib.ptr(g2), gamma.data_ptr(), ds.data_ptr()
+    a.dgamma, a.dbeta, a.scratch, a.eps = _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch), enc.eps
+    a.M, a.N, a.ld_y, a.ld_x, a.ld_g, a.ld_g2, a.ld_ds = M, N, y.stride(0), x.stride(0), g.stride(0), g2.stride(0) if g2 is not None else 0, N
+    a.act_f32, a.stream = int(enc.compute_dtype == "fp32"), _lib.current_stream()
+    _lib.check(lib.mmdeer_bert_add_ln_bwd(C.byref(a)))
+    return ds, dgamma, dbeta
+
+
+# the parameters of one BertLayer in nn.Module.parameters() order, as _TailFn receives them
+_Q_W, _Q_B, _K_W, _K_B, _V_W, _V_B, _O_W, _O_B, _LN1_W, _LN1_B, _I_W, _I_B, _O2_W, _O2_B, _LN2_W, _LN2_B = range(16)
+
+
+class _TailFn(torch.autograd.Function):
+    """The fine-tuned tail as one autograd node (the module docstring has both launch plans).  ``packed``: the tail layers' packed
+    operands; ``states``: the caller's list of hidden-state copies, or None."""
+
+    @staticmethod
+    def forward(ctx, enc, x, m, B, L, packed, states, *params):
+        lib, stream, c = _lib.load(), _lib.current_stream(), enc.compute_dtype
+        f32, (M, H), I = int(c == "fp32"), x.shape, int(enc.config["intermediate_size"])
+        new = lambda n: torch.empty(M, n, dtype=x.dtype, device=x.device)      # noqa: E731
+        tape = []
+        for p in packed:
+            qkv, cx, y, x1, h, gh, y2, out = new(3 * H), new(H), new(H), new(H), new(I), new(I), new(H), new(H)
+            ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=c)
+            at = _lib.BertAttnArgs()
+            at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), cx.data_ptr()
+            at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
+            _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
+            ops.linear_into(cx, p["wo"], p["bo"], y, compute=c)
+            enc._add_ln(y, x, p["g1"], p["b1"], x1)
+            ops.linear_into(x1, p["wi"], p["bi"], h, compute=c)
+            ge = _lib.BertGeluArgs()
+            ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), gh.data_ptr(), M, I, I, I, f32, stream
+            _lib.check(lib.mmdeer_bert_gelu_fwd(C.byref(ge)))
+            ops.linear_into(gh, p["wo2"], p["bo2"], y2, compute=c)
+            enc._add_ln(y2, x1, p["g2"], p["b2"], out)
+            tape.append((x, qkv, cx, y, x1, h, gh, y2))
+            x = out
+            if states is not None:
+                states.append(x.clone())
+        ctx.enc, ctx.mask, ctx.BL, ctx.packed, ctx.tape = enc, m, (B, L), packed, tape
+        ctx.dtypes = [p.dtype for p in params]
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import opseq
+        enc, m, (B, L), c = ctx.enc, ctx.mask, ctx.BL, ctx.enc.compute_dtype
+        needs = ctx.needs_input_grad[7:]
+        lib, f32 = _lib.load(), int(c == "fp32")
+        dt = ops._act_dtype(c)
+        ex = opseq.Exec(c)
+        nl = len(ctx.packed)
+        lowest = min(i // 16 for i, need in enumerate(needs) if need)
+        grads = [None] * (16 * nl)
+        g, g2 = g.reshape(B * L, -1).to(dt).contiguous(), None
+        M, H = g.shape
+        I = int(enc.config["intermediate_size"])
+        dev = g.device
+
+        def dw(li, wi, bi, dy, xin, n, k):
+            """dW (n, k) = dy^T xin and its bias gradient, where either is wanted"""
+            if needs[16 * li + wi] or needs[16 * li + bi]:
+                gw, gb = torch.empty(n, k, device=dev), torch.empty(n, device=dev)
+                ex.dw(dy, dy.stride(0), xin, xin.stride(0), gw, gb, M, n, k)
+                grads[16 * li + wi], grads[16 * li + bi] = gw, gb
+            return None
+
+        ws_bytes = lib.mmdeer_bert_attn_bwd_workspace(B, L, H)
+        ws = torch.empty(max(ws_bytes // 4, 4), device=dev)
+        for li in range(nl - 1, lowest - 1, -1):
+            p = ctx.packed[li]
+            x, qkv, cx, y, x1, h, gh, y2 = ctx.tape.pop()
+            sums = lambda a, b: needs[16 * li + a] or needs[16 * li + b]      # noqa: E731
+            ds2, grads[16 * li + _LN2_W], grads[16 * li + _LN2_B] = _ln_bwd(enc, g, g2, y2, x1, p["g2"], sums(_LN2_W, _LN2_B))
+            del g, g2, y2
+            dw(li, _O2_W, _O2_B, ds2, gh, H, I)
+            del gh
+            dh = torch.empty(M, I, dtype=dt, device=dev)
+            ex.dx(ds2, H, p["wo2"], dh, I, M)
+            ga = _lib.BertGeluBwdArgs()
+            ga.x, ga.g, ga.dx, ga.M, ga.N, ga.ld_x, ga.ld_g, ga.ld_dx = h.data_ptr(), dh.data_ptr(), dh.data_ptr(), M, I, I, I, I
+            ga.act_f32, ga.stream = f32, ex.s
+            _lib.check(lib.mmdeer_bert_gelu_bwd(C.byref(ga)))
+            del h
+            dw(li, _I_W, _I_B, dh, x1, I, H)
+            dx1 = torch.empty(M, H, dtype=dt, device=dev)
+            ex.dx(dh, I, p["wi"], dx1, H, M)
+            del dh
+            ds1, grads[16 * li + _LN1_W], grads[16 * li + _LN1_B] = _ln_bwd(enc, dx1, ds2, y, x, p["g1"], sums(_LN1_W, _LN1_B))
+            del dx1, ds2, y, x1
+            dw(li, _O_W, _O_B, ds1, cx, H, H)
+            dctx = torch.empty(M, H, dtype=dt, device=dev)
+            ex.dx(ds1, H, p["wo"], dctx, H, M)
+            dqkv = torch.empty(M, 3 * H, dtype=dt, device=dev)
+            ab = _lib.BertAttnBwdArgs()
+            ab.qkv, ab.mask, ab.dctx, ab.dqkv = qkv.data_ptr(), m.data_ptr(), dctx.data_ptr(), dqkv.data_ptr()
+            ab.workspace, ab.workspace_bytes = ws.data_ptr(), ws_bytes
+            ab.B, ab.L, ab.H, ab.ld_qkv, ab.ld_dctx, ab.ld_dqkv, ab.act_f32, ab.stream = B, L, H, 3 * H, H, 3 * H, f32, ex.s
+            _lib.check(lib.mmdeer_bert_attn_bwd(C.byref(ab)))
+            del dctx, cx, qkv
+            if any(needs[16 * li + i] for i in (_Q_W, _Q_B, _K_W, _K_B, _V_W, _V_B)):
+                gw, gb = torch.empty(3 * H, H, device=dev), torch.empty(3 * H, device=dev)
+                ex.dw(dqkv, 3 * H, x, H, gw, gb, M, 3 * H, H)
+                for j, (wi, bi) in enumerate(((_Q_W, _Q_B), (_K_W, _K_B), (_V_W, _V_B))):
+                    grads[16 * li + wi], grads[16 * li + bi] = gw[j * H:(j + 1) * H], gb[j * H:(j + 1) * H]
+            del x
+            if li > lowest:
+                g = torch.empty(M, H, dtype=dt, device=dev)
+                ex.dx(dqkv, 3 * H, p["wqkv"], g, H, M)
+                g2 = ds1
+            del dqkv, ds1
+        ctx.tape.clear()
+        out = [gr.to(d) if gr is not None and need else None for gr, d, need in zip(grads, ctx.dtypes, needs)]
+        return (None, None, None, None, None, None, None, *out)

@@ -1,10 +1,10 @@
 """Temporal text encoder: ``encoders.EnhancedTextEncoder`` (reference src/models/encoders.py:553-761) on token-level text --
 ids and a mask (the reference's no-BERT configuration: ``nn.Embedding(30000, 768, padding_idx=0)`` + ``nn.Embedding(128, 768)``),
 a (B, L, 768) matrix of contextual embeddings from the caller's own BERT (the reference's BERT branch downstream of
-``last_hidden_state``), or -- constructed with ``bert=BertEncoder(...)`` (mmdeer.bert: the trunk's forward on HIP, frozen) -- the
+``last_hidden_state``), or -- constructed with ``bert=BertEncoder(...)`` (mmdeer.bert: the trunk on HIP, frozen or with its last layers fine-tuned) -- the
 reference's BERT configuration itself: ids and a mask through the trunk, then the same path on its ``last_hidden_state``
 -> the (B, 512) block that ``ComposedDEER`` / ``generic_fusion`` take.  Tokenisation and pretrained weights are outside this
-package; so is the trunk's backward.
+package.
 
 Per forward: ``mmdeer_token_embed_fwd`` (gather + position + mask, or mask alone), one ``mmdeer_gemm`` over all B * L rows for
 the pool's ``W1 x + b1``, ``mmdeer_token_pool_fwd`` (masked softmax over tokens, renormalisation, weighted sum),
@@ -176,9 +176,12 @@ class TemporalTextEncoder(nn.Module):
 
     ``bert=BertEncoder(...)`` (``hidden_size`` 768) makes it the reference's BERT configuration: the module holds the trunk as
     ``self.bert`` and creates no ``embedding`` / ``positional_encoding`` tables, so its ``state_dict`` keys are the reference's
-    (``bert.*``, ``token_attention.*``, ...).  ``forward(input_ids, attention_mask)`` then runs the trunk under ``no_grad`` (it is
-    forward only and has no dropout) and ``forward_embeddings`` on its ``last_hidden_state`` as it comes, fp32 or bf16; everything
-    behind the trunk trains as without it."""
+    (``bert.*``, ``token_attention.*``, ...).  ``forward(input_ids, attention_mask)`` then runs the trunk and ``forward_embeddings`` on its
+    ``last_hidden_state`` as it comes, fp32 or bf16; everything behind the trunk trains as without it.  A frozen trunk
+    (``finetune_layers == 0``) runs under ``no_grad``, as does any trunk while grad is disabled.  A trunk built with
+    ``finetune_layers=k`` is called with grad when grad is enabled: the gradient of the embeddings that ``forward_embeddings``
+    produces flows on into the trunk's last ``k`` layers (the reference fine-tunes layers 6-11 of 12: k = 6).  The trunk has no
+    dropout in either mode, where the reference's BERT trains with 0.1."""
 
     def __init__(self, config: Optional[Dict] = None, compute_dtype: str = "fp32", bert: Optional[BertEncoder] = None):
         super().__init__()
@@ -253,7 +256,7 @@ class TemporalTextEncoder(nn.Module):
         if B == 0:
             return torch.zeros(0, self.hidden_dim, device=input_ids.device)
         if self.bert is not None:
-            with torch.no_grad():
+            with torch.set_grad_enabled(torch.is_grad_enabled() and self.bert.finetune_layers > 0):     # the reference: set_grad_enabled(self.training)
                 hidden = self.bert(input_ids, attention_mask).last_hidden_state
             return self.forward_embeddings(hidden, input_ids, attention_mask)
         if B * L > MAX_ROWS and torch.is_grad_enabled() and (self.embedding.weight.requires_grad or self.positional_encoding.weight.requires_grad):
