@@ -25,9 +25,9 @@ checkpoint and never read.
 reference's ``_setup_bert_fine_tuning`` freezes the embeddings and layers 0-5 of 12 and trains layers 6-11: k = 6).  Their
 parameters are created with ``requires_grad=True``; the embeddings, the layers below and the pooler stay frozen, and a call with
 grad enabled raises ``ValueError`` naming the parameter when one of those requires grad.  With grad enabled the layers below the
-tail run as ever under ``no_grad`` and the tail is ONE autograd node (``_TailFn``) over all its layers.  Its forward issues the
-same launches on the same packed operands and only writes to fresh buffers where the forward-only path overwrites (x1 no longer
-takes y's buffer, the GELU is not in place), so ``last_hidden_state`` is bit-equal to the frozen trunk's.  It keeps per tail layer
+tail run as ever under ``no_grad`` and the tail is ONE autograd node (``_TailFn``) over all its layers.  A layer's forward is
+stated once (``_layer_fwd``): the forward-only path calls it with aliased buffers (x1 takes y's buffer, the GELU is in place, the
+output returns to x's) and the tail with fresh ones, so ``last_hidden_state`` is bit-equal to the frozen trunk's.  It keeps per tail layer
 x, qkv, ctx, y, x1, the pre-GELU h, gelu(h) and y2 on the tape: 8 H + 2 I elements per token, 100 MB per layer at 4096 tokens of
 BERT-base in bf16 (12 288 elements x 4096 x 2 bytes), 600 MB for k = 6; a layer's tape is released as the backward leaves it.
 The backward, per tail layer from the top, given g (the gradient of the layer's output) and g2 (None at the top):
@@ -259,20 +259,9 @@ class BertEncoder(nn.Module):
             a.V, a.P, a.T = self.config["vocab_size"], self.config["max_position_embeddings"], self.config["type_vocab_size"]
             _lib.check(lib.mmdeer_bert_embed_fwd(C.byref(a)))
             states = [x.clone()] if output_hidden_states else None
-            at = _lib.BertAttnArgs()
-            at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), ctx.data_ptr()
-            at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
-            ge = _lib.BertGeluArgs()
-            ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), h.data_ptr(), M, I, I, I, f32, stream
             for p in w["layers"][:first_tail if tail else nl]:
-                ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=self.compute_dtype)
-                _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
-                ops.linear_into(ctx, p["wo"], p["bo"], y, compute=self.compute_dtype)
-                self._add_ln(y, x, p["g1"], p["b1"], y)              # x1 takes y's buffer; x is free from here
-                ops.linear_into(y, p["wi"], p["bi"], h, compute=self.compute_dtype)
-                _lib.check(lib.mmdeer_bert_gelu_fwd(C.byref(ge)))
-                ops.linear_into(h, p["wo2"], p["bo2"], x, compute=self.compute_dtype)
-                self._add_ln(x, y, p["g2"], p["b2"], x)              # the layer's output, in x's buffer again
+                # x1 takes y's buffer (x is free from there), the GELU is in place, and y2 and the layer's output take x's
+                _layer_fwd(self, x, p, m, B, L, qkv, ctx, y, x1=y, h=h, gh=h, y2=x, out=x)
                 if output_hidden_states:
                     states.append(x.clone())
             shaped = lambda t: t.reshape(B, L, H)             # noqa: E731
@@ -282,6 +271,26 @@ class BertEncoder(nn.Module):
         params = [p for lyr in self.encoder.layer[first_tail:] for p in lyr.parameters()]
         out = _TailFn.apply(self, x, m, B, L, w["layers"][first_tail:], states, *params)
         return BertEncoderOutput(shaped(out), tuple(shaped(s) for s in states) if output_hidden_states else None)
+
+
+def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out):
+    """One BertLayer's forward on the caller's buffers: the eight launches of the module docstring.  ``p``: the layer's packed
+    operands.  Buffers may alias as the frozen path's do (x1 = y, gh = h, y2 = out = x): each is written after its last reader."""
+    lib, c, stream = _lib.load(), enc.compute_dtype, _lib.current_stream()
+    f32, (M, H), I = int(c == "fp32"), x.shape, h.shape[1]
+    ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=c)
+    at = _lib.BertAttnArgs()
+    at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), ctx.data_ptr()
+    at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
+    _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
+    ops.linear_into(ctx, p["wo"], p["bo"], y, compute=c)
+    enc._add_ln(y, x, p["g1"], p["b1"], x1)
+    ops.linear_into(x1, p["wi"], p["bi"], h, compute=c)
+    ge = _lib.BertGeluArgs()
+    ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), gh.data_ptr(), M, I, I, I, f32, stream
+    _lib.check(lib.mmdeer_bert_gelu_fwd(C.byref(ge)))
+    ops.linear_into(gh, p["wo2"], p["bo2"], y2, compute=c)
+    enc._add_ln(y2, x1, p["g2"], p["b2"], out)
 
 
 def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool):
@@ -312,25 +321,12 @@ class _TailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, x, m, B, L, packed, states, *params):
-        lib, stream, c = _lib.load(), _lib.current_stream(), enc.compute_dtype
-        f32, (M, H), I = int(c == "fp32"), x.shape, int(enc.config["intermediate_size"])
+        (M, H), I = x.shape, int(enc.config["intermediate_size"])
         new = lambda n: torch.empty(M, n, dtype=x.dtype, device=x.device)      # noqa: E731
         tape = []
         for p in packed:
             qkv, cx, y, x1, h, gh, y2, out = new(3 * H), new(H), new(H), new(H), new(I), new(I), new(H), new(H)
-            ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=c)
-            at = _lib.BertAttnArgs()
-            at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), cx.data_ptr()
-            at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
-            _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
-            ops.linear_into(cx, p["wo"], p["bo"], y, compute=c)
-            enc._add_ln(y, x, p["g1"], p["b1"], x1)
-            ops.linear_into(x1, p["wi"], p["bi"], h, compute=c)
-            ge = _lib.BertGeluArgs()
-            ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), gh.data_ptr(), M, I, I, I, f32, stream
-            _lib.check(lib.mmdeer_bert_gelu_fwd(C.byref(ge)))
-            ops.linear_into(gh, p["wo2"], p["bo2"], y2, compute=c)
-            enc._add_ln(y2, x1, p["g2"], p["b2"], out)
+            _layer_fwd(enc, x, p, m, B, L, qkv, cx, y, x1, h, gh, y2, out)
             tape.append((x, qkv, cx, y, x1, h, gh, y2))
             x = out
             if states is not None:

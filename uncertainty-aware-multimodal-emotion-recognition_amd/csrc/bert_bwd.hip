@@ -9,10 +9,8 @@
 //   dq kernel    one workgroup per (sample, head, 64 queries), the forward kernel's shape.  Pass 0 walks the keys for the running
 //                maximum, sum and delta and leaves lse and delta in the workspace; pass 1 walks them again for dQ.
 //   dkdv kernel  one workgroup per (sample, head, 64 keys), walks the queries in tiles of 64 with lse and delta from the workspace.
-// bf16 (mfma_f32_32x32x16_bf16, two waves, a wave owns 32 rows of the tile).  The forward's device carries both kernels: a product
-// is computed TRANSPOSED so that its accumulator tile -- registers 8 s .. 8 s + 7 of a lane are the fragment of k-step s, element j of
-// lane half h being row 16 s + 8 (j >> 2) + 4 h + (j & 3) -- is the B operand of the product that sums over those rows, and the
-// A operand of that product is read from a transposed LDS tile in the same order (two 8-byte reads).
+// bf16, on bert_dev.h's tiles and fragments (a product is computed TRANSPOSED so that its accumulator tile is the B operand of the
+// product that sums over its rows):
 //   dq:    S^T = K Q^T and dP^T = V dO^T (A from the row-major K and V tiles, B = this lane's Q and dO rows in registers): a lane holds
 //          16 keys of ONE query, so lse and delta are per-lane scalars; dQ^T += K^T dS^T with K^T from the transposed tile.
 //   dkdv:  S = Q K^T and dP = dO V^T (A from the row-major Q and dO tiles, B = this lane's K and V rows in registers): a lane holds
@@ -22,80 +20,18 @@
 // Rows past L are zero-filled in LDS (lse = +inf for such a query) and never stored.
 // fp32: plain FMA, one thread per query (dq) and one per key (dkdv), K / V and Q / dO in LDS tiles of 32 rows read as broadcasts.
 //
-// add + LN backward: bert.hip's row layout (one wave per row, lane l owns the 4-element chunks l + 64 j), the forward's own two
-// passes for mean and rstd, then two more wave sums for the row's means of G gamma and G gamma xhat.  A wave keeps the column sums
-// of its rows in registers; the four waves of a workgroup add theirs through LDS in wave order and the workgroup stores one partial
-// pair; bert_ln_fold_kernel adds the partials in a fixed order (16 interleaved groups, then the groups).  Which rows a workgroup owns
-// depends on M alone.
-#include <math.h>
-
-#include "../../include/mmdeer_bert.h"
+// add + LN backward: bert_dev.h's row layout, the forward's two passes for mean and rstd (written out: see the kernel), then two more
+// wave sums for the row's means of G gamma and G gamma xhat.  A wave keeps the column sums of its rows in registers; the four waves of a workgroup
+// add theirs through LDS in wave order and the workgroup stores one partial pair; bert_ln_fold_kernel adds the partials in a fixed
+// order (16 interleaved groups, then the groups).  Which rows a workgroup owns depends on M alone.
 #include "../../include/mmdeer_bert_bwd.h"
-#include "elem.h"
+#include "bert_dev.h"
 
 namespace mmdeer {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int HD = MMDEER_BERT_HEAD_DIM;   // 64
-constexpr int BQ = 64;          // rows of the owned tile (queries in dq, keys in dkdv)
-constexpr int DQ_K = 128;       // keys per LDS tile of the bf16 dq kernel
-constexpr int KS_LD = 72;       // bf16 elements per row of a row-major tile: 64 + 8 of padding
-constexpr int KT_LD = 132;      // bf16 elements per row of the transposed K tile: 128 keys + 4
-constexpr int KV_Q = 64;        // queries per LDS tile of the bf16 dkdv kernel
-constexpr int QT_LD = 68;       // bf16 elements per row of a transposed Q / dO tile: 64 queries + 4
-constexpr int F_T = 32;         // rows per LDS tile of the fp32 kernels
 constexpr int DF_LD = 68;       // floats per dO row in LDS of the fp32 dq kernel: 64 + 4, so that the threads' rows start in different banks
 constexpr int LN_PARTS = MMDEER_BERT_LN_BWD_PARTS;
-
-// row-major tile: 16-byte chunk c of row `row` of `rows` rows, zero past L.  src points at the head's 64 columns of token 0.
-__device__ __forceinline__ void stage_rows(bf16_t* dst, const bf16_t* src, int ld, int t0, int rows, int L, int tid) {
-  for (int i = tid; i < rows * 8; i += 128) {
-    const int row = i >> 3, c = i & 7;
-    u32x4 val{0u, 0u, 0u, 0u};
-    if (t0 + row < L) val = *reinterpret_cast<const u32x4*>(src + (long long)(t0 + row) * ld + 8 * c);
-    *reinterpret_cast<u32x4*>(dst + row * KS_LD + 8 * c) = val;
-  }
-}
-// transposed tile [d][row], row stride ld_t: chunk c of the rows 2 rp and 2 rp + 1, one dword per d (the forward's V^T staging)
-__device__ __forceinline__ void stage_transposed(bf16_t* dst, int ld_t, const bf16_t* src, int ld, int t0, int rows, int L, int tid) {
-  for (int i = tid; i < (rows / 2) * 8; i += 128) {
-    const int row = 2 * (i >> 3), c = i & 7;
-    u32x4 va{0u, 0u, 0u, 0u}, vc{0u, 0u, 0u, 0u};
-    if (t0 + row < L) va = *reinterpret_cast<const u32x4*>(src + (long long)(t0 + row) * ld + 8 * c);
-    if (t0 + row + 1 < L) vc = *reinterpret_cast<const u32x4*>(src + (long long)(t0 + row + 1) * ld + 8 * c);
-    const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wc[4] = {vc.x, vc.y, vc.z, vc.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      *reinterpret_cast<unsigned*>(dst + (8 * c + 2 * e) * ld_t + row) = (wa[e] & 0xFFFFu) | (wc[e] << 16);
-      *reinterpret_cast<unsigned*>(dst + (8 * c + 2 * e + 1) * ld_t + row) = (wa[e] >> 16) | (wc[e] & 0xFFFF0000u);
-    }
-  }
-}
-// the A fragment of k-step s2 from a transposed tile, in the accumulator's row order: rows 16 s2 + 4 h + {0..3} and + 8
-__device__ __forceinline__ bf16x8 frag_t(const bf16_t* p) {
-  const u32x2 lo = *reinterpret_cast<const u32x2*>(p), hi = *reinterpret_cast<const u32x2*>(p + 8);
-  return __builtin_bit_cast(bf16x8, u32x4{lo.x, lo.y, hi.x, hi.y});
-}
-// this lane's row of 64 bf16 as the B fragments of the four k-steps; zeros for a row past L
-__device__ __forceinline__ void load_row_frags(bf16x8 (&f)[4], const bf16_t* row, bool live, int h) {
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    u32x4 raw{0u, 0u, 0u, 0u};
-    if (live) raw = *reinterpret_cast<const u32x4*>(row + 16 * ks + 8 * h);
-    f[ks] = __builtin_bit_cast(bf16x8, raw);
-  }
-}
-// the lane's accumulator tile (register 4 g + e is column 32 t + 8 g + 4 h + e of its row) times `scale` into a row of dqkv
-__device__ __forceinline__ void store_tile(bf16_t* out, long long off, const f32x16 (&o)[2], int h, float scale) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      st4<false>(out, off + 32 * t + 8 * g + 4 * h,
-                 f32x4{o[t][4 * g] * scale, o[t][4 * g + 1] * scale, o[t][4 * g + 2] * scale, o[t][4 * g + 3] * scale});
-}
 
 // ------------------------------------------------------------------------------------------------ attention backward, bf16: dQ
 // grid: ((b * heads + head) * nqt + qt); 128 threads.  ws: lse [B * heads * L], then delta [B * heads * L].
@@ -103,59 +39,56 @@ __global__ __launch_bounds__(128) void bert_attn_dq_bf16_kernel(const bf16_t* __
                                                                 const bf16_t* __restrict__ dctx, bf16_t* __restrict__ dqkv,
                                                                 float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx, int ld_dqkv,
                                                                 int nqt, long long nstat) {
-  __shared__ __attribute__((aligned(16))) bf16_t Ks[DQ_K * KS_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t Vs[DQ_K * KS_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t Kt[HD * KT_LD];
-  __shared__ __attribute__((aligned(16))) unsigned char vb[DQ_K];
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[AT_K * ROW_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[AT_K * ROW_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Kt[BERT_HD * KT_LD];
+  __shared__ __attribute__((aligned(16))) unsigned char vb[AT_K];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int heads = H / HD;
-  const int qt = blockIdx.x % nqt, head = (blockIdx.x / nqt) % heads, b = blockIdx.x / (nqt * heads);
-  const long long row0 = (long long)b * L;
-  const int q = qt * BQ + wave * 32 + r;                      // this lane's query row
-  const bool wave_live = qt * BQ + wave * 32 < L;             // wave-uniform: a wave without a query row only stages
+  const int heads = H / BERT_HD;
+  const AttnBlock blk = attn_block(heads, nqt);
+  const long long row0 = (long long)blk.b * L;
+  const int q = blk.tile * AT_OWN + wave * 32 + r;                      // this lane's query row
+  const bool wave_live = blk.tile * AT_OWN + wave * 32 < L;             // wave-uniform: a wave without a query row only stages
   const bool live = q < L;
-  const bf16_t* kbase = qkv + row0 * ld_qkv + H + head * HD;
+  const bf16_t* kbase = qkv + row0 * ld_qkv + H + blk.head * BERT_HD;
   const bf16_t* vbase = kbase + H;
 
   bf16x8 qf[4], dof[4];
-  load_row_frags(qf, qkv + (row0 + (live ? q : 0)) * ld_qkv + head * HD, live, h);
-  load_row_frags(dof, dctx + (row0 + (live ? q : 0)) * ld_dctx + head * HD, live, h);
+  load_row_frags(qf, qkv + (row0 + (live ? q : 0)) * ld_qkv + blk.head * BERT_HD, live, h);
+  load_row_frags(dof, dctx + (row0 + (live ? q : 0)) * ld_dctx + blk.head * BERT_HD, live, h);
   f32x16 o[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) o[0][i] = o[1][i] = 0.f;
   float m = -INFINITY, l = 0.f, dacc = 0.f, lse = INFINITY, delta = 0.f;
 
   for (int pass = 0; pass < 2; ++pass) {
-    for (int k0 = 0; k0 < L; k0 += DQ_K) {
+    for (int k0 = 0; k0 < L; k0 += AT_K) {
       __syncthreads();                                        // the tile before has been read
-      stage_rows(Ks, kbase, ld_qkv, k0, DQ_K, L, tid);
-      stage_rows(Vs, vbase, ld_qkv, k0, DQ_K, L, tid);
-      if (pass) stage_transposed(Kt, KT_LD, kbase, ld_qkv, k0, DQ_K, L, tid);
-      if (tid < DQ_K) vb[tid] = (k0 + tid < L && mask[row0 + k0 + tid] != 0.f) ? 1 : 0;
+      stage_rows(Ks, kbase, ld_qkv, k0, AT_K, L, tid);
+      stage_rows(Vs, vbase, ld_qkv, k0, AT_K, L, tid);
+      if (pass) stage_transposed(Kt, KT_LD, kbase, ld_qkv, k0, AT_K, L, tid);
+      stage_valid(vb, mask + row0, k0, L, tid);
       __syncthreads();
       if (!wave_live) continue;
-      for (int kb = 0; kb < DQ_K / 32 && k0 + 32 * kb < L; ++kb) {
-        // validity of this lane's 16 keys: register i is key 32 kb + (i & 3) + 8 (i >> 2) + 4 h of the tile
+      for (int kb = 0; kb < AT_K / 32 && k0 + 32 * kb < L; ++kb) {
         unsigned vw[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) vw[g] = *reinterpret_cast<const unsigned*>(vb + 32 * kb + 8 * g + 4 * h);
-        if (__builtin_amdgcn_ballot_w64((vw[0] | vw[1] | vw[2] | vw[3]) != 0u) == 0ull) continue;     // no valid key in the block
+        load_valid(vw, vb, kb, h);
+        if (none_valid(vw)) continue;
         f32x16 s, dp;
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (32 * kb + r) * KS_LD + 16 * ks + 8 * h);
+          const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (32 * kb + r) * ROW_LD + 16 * ks + 8 * h);
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
-          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + (32 * kb + r) * KS_LD + 16 * ks + 8 * h);
+          const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + (32 * kb + r) * ROW_LD + 16 * ks + 8 * h);
           dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[ks], dp, 0, 0, 0);
         }
         if (pass == 0) {
           float bm = -INFINITY;
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const bool valid = ((vw[i >> 2] >> (8 * (i & 3))) & 0xFFu) != 0u;
-            s[i] = valid ? s[i] * 0.125f : -INFINITY;
+            s[i] = key_valid(vw, i) ? s[i] * 0.125f : -INFINITY;
             bm = fmaxf(bm, s[i]);
           }
           bm = fmaxf(bm, __shfl_xor(bm, 32));
@@ -178,8 +111,7 @@ __global__ __launch_bounds__(128) void bert_attn_dq_bf16_kernel(const bf16_t* __
           bf16x8 dsf[2];
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const bool valid = ((vw[i >> 2] >> (8 * (i & 3))) & 0xFFu) != 0u;
-            const float p = valid ? __expf(s[i] * 0.125f - lse) : 0.f;   // lse = +inf (no valid key): 0
+            const float p = key_valid(vw, i) ? __expf(s[i] * 0.125f - lse) : 0.f;   // lse = +inf (no valid key): 0
             dsf[i >> 3][i & 7] = (__bf16)(p * (dp[i] - delta));
           }
 #pragma unroll
@@ -194,13 +126,13 @@ __global__ __launch_bounds__(128) void bert_attn_dq_bf16_kernel(const bf16_t* __
       lse = l > 0.f ? m + __logf(l) : INFINITY;
       delta = l > 0.f ? dacc / l : 0.f;
       if (live && h == 0) {
-        const long long at = ((long long)b * heads + head) * L + q;
+        const long long at = ((long long)blk.b * heads + blk.head) * L + q;
         ws[at] = lse;
         ws[nstat + at] = delta;
       }
     }
   }
-  if (wave_live && live) store_tile(dqkv, (row0 + q) * ld_dqkv + head * HD, o, h, 0.125f);
+  if (wave_live && live) store_tile(dqkv, (row0 + q) * ld_dqkv + blk.head * BERT_HD, o, h, 0.125f);
 }
 
 // ------------------------------------------------------------------------------------------------ attention backward, bf16: dK, dV
@@ -209,53 +141,53 @@ __global__ __launch_bounds__(128) void bert_attn_dkdv_bf16_kernel(const bf16_t* 
                                                                   const bf16_t* __restrict__ dctx, bf16_t* __restrict__ dqkv,
                                                                   const float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx,
                                                                   int ld_dqkv, int nkt, long long nstat) {
-  __shared__ __attribute__((aligned(16))) bf16_t Qs[KV_Q * KS_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t Os[KV_Q * KS_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t Qt[HD * QT_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t Ot[HD * QT_LD];
-  __shared__ __attribute__((aligned(16))) float lse_s[KV_Q];
-  __shared__ __attribute__((aligned(16))) float del_s[KV_Q];
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[AT_Q * ROW_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Os[AT_Q * ROW_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Qt[BERT_HD * QT_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Ot[BERT_HD * QT_LD];
+  __shared__ __attribute__((aligned(16))) float lse_s[AT_Q];
+  __shared__ __attribute__((aligned(16))) float del_s[AT_Q];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int heads = H / HD;
-  const int kt = blockIdx.x % nkt, head = (blockIdx.x / nkt) % heads, b = blockIdx.x / (nkt * heads);
-  const long long row0 = (long long)b * L;
-  const int key = kt * BQ + wave * 32 + r;                    // this lane's key
+  const int heads = H / BERT_HD;
+  const AttnBlock blk = attn_block(heads, nkt);
+  const long long row0 = (long long)blk.b * L;
+  const int key = blk.tile * AT_OWN + wave * 32 + r;                    // this lane's key
   const bool live = key < L;
   const bool valid = live && mask[row0 + (live ? key : 0)] != 0.f;
   const bool wave_work = __builtin_amdgcn_ballot_w64(valid) != 0ull;      // wave-uniform: a wave without a valid key only stages
-  const bf16_t* qbase = qkv + row0 * ld_qkv + head * HD;
-  const bf16_t* obase = dctx + row0 * ld_dctx + head * HD;
-  const float* lse_g = ws + ((long long)b * heads + head) * L;
+  const bf16_t* qbase = qkv + row0 * ld_qkv + blk.head * BERT_HD;
+  const bf16_t* obase = dctx + row0 * ld_dctx + blk.head * BERT_HD;
+  const float* lse_g = ws + ((long long)blk.b * heads + blk.head) * L;
 
   bf16x8 kf[4], vf[4];
-  load_row_frags(kf, qkv + (row0 + (live ? key : 0)) * ld_qkv + H + head * HD, live, h);
-  load_row_frags(vf, qkv + (row0 + (live ? key : 0)) * ld_qkv + 2 * H + head * HD, live, h);
+  load_row_frags(kf, qkv + (row0 + (live ? key : 0)) * ld_qkv + H + blk.head * BERT_HD, live, h);
+  load_row_frags(vf, qkv + (row0 + (live ? key : 0)) * ld_qkv + 2 * H + blk.head * BERT_HD, live, h);
   f32x16 dk[2], dv[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) dk[0][i] = dk[1][i] = dv[0][i] = dv[1][i] = 0.f;
 
-  for (int q0 = 0; q0 < L; q0 += KV_Q) {
+  for (int q0 = 0; q0 < L; q0 += AT_Q) {
     __syncthreads();                                          // the tile before has been read
-    stage_rows(Qs, qbase, ld_qkv, q0, KV_Q, L, tid);
-    stage_rows(Os, obase, ld_dctx, q0, KV_Q, L, tid);
-    stage_transposed(Qt, QT_LD, qbase, ld_qkv, q0, KV_Q, L, tid);
-    stage_transposed(Ot, QT_LD, obase, ld_dctx, q0, KV_Q, L, tid);
-    if (tid < KV_Q) {
+    stage_rows(Qs, qbase, ld_qkv, q0, AT_Q, L, tid);
+    stage_rows(Os, obase, ld_dctx, q0, AT_Q, L, tid);
+    stage_transposed(Qt, QT_LD, qbase, ld_qkv, q0, AT_Q, L, tid);
+    stage_transposed(Ot, QT_LD, obase, ld_dctx, q0, AT_Q, L, tid);
+    if (tid < AT_Q) {
       const bool in = q0 + tid < L;
       lse_s[tid] = in ? lse_g[q0 + tid] : INFINITY;           // a query past L: P = 0
       del_s[tid] = in ? lse_g[nstat + q0 + tid] : 0.f;
     }
     __syncthreads();
     if (!wave_work) continue;
-    for (int qb = 0; qb < KV_Q / 32 && q0 + 32 * qb < L; ++qb) {
+    for (int qb = 0; qb < AT_Q / 32 && q0 + 32 * qb < L; ++qb) {
       f32x16 s, dp;
 #pragma unroll
       for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(Qs + (32 * qb + r) * KS_LD + 16 * ks + 8 * h);
+        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(Qs + (32 * qb + r) * ROW_LD + 16 * ks + 8 * h);
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], s, 0, 0, 0);
-        const bf16x8 oa = *reinterpret_cast<const bf16x8*>(Os + (32 * qb + r) * KS_LD + 16 * ks + 8 * h);
+        const bf16x8 oa = *reinterpret_cast<const bf16x8*>(Os + (32 * qb + r) * ROW_LD + 16 * ks + 8 * h);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], dp, 0, 0, 0);
       }
       // register i is query 32 qb + (i & 3) + 8 (i >> 2) + 4 h of the tile
@@ -282,8 +214,8 @@ __global__ __launch_bounds__(128) void bert_attn_dkdv_bf16_kernel(const bf16_t* 
     }
   }
   if (live) {
-    store_tile(dqkv, (row0 + key) * ld_dqkv + H + head * HD, dk, h, 0.125f);
-    store_tile(dqkv, (row0 + key) * ld_dqkv + 2 * H + head * HD, dv, h, 1.0f);
+    store_tile(dqkv, (row0 + key) * ld_dqkv + H + blk.head * BERT_HD, dk, h, 0.125f);
+    store_tile(dqkv, (row0 + key) * ld_dqkv + 2 * H + blk.head * BERT_HD, dv, h, 1.0f);
   }
 }
 
@@ -293,17 +225,17 @@ __global__ __launch_bounds__(64) void bert_attn_dq_f32_kernel(const float* __res
                                                               const float* __restrict__ dctx, float* __restrict__ dqkv,
                                                               float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx, int ld_dqkv,
                                                               int nqt, long long nstat) {
-  __shared__ __attribute__((aligned(16))) float Kf[F_T * HD];
-  __shared__ __attribute__((aligned(16))) float Vf[F_T * HD];
-  __shared__ __attribute__((aligned(16))) float Df[BQ * DF_LD];      // thread t's dO row at t * DF_LD: read by its owner alone
-  __shared__ float mk[F_T];
+  __shared__ __attribute__((aligned(16))) float Kf[AT_F * BERT_HD];
+  __shared__ __attribute__((aligned(16))) float Vf[AT_F * BERT_HD];
+  __shared__ __attribute__((aligned(16))) float Df[AT_OWN * DF_LD];      // thread t's dO row at t * DF_LD: read by its owner alone
+  __shared__ float mk[AT_F];
   const int tid = threadIdx.x;
-  const int heads = H / HD;
-  const int qt = blockIdx.x % nqt, head = (blockIdx.x / nqt) % heads, b = blockIdx.x / (nqt * heads);
-  const long long row0 = (long long)b * L;
-  const int q = qt * BQ + tid;
+  const int heads = H / BERT_HD;
+  const AttnBlock blk = attn_block(heads, nqt);
+  const long long row0 = (long long)blk.b * L;
+  const int q = blk.tile * AT_OWN + tid;
   const bool live = q < L;
-  const float* kbase = qkv + row0 * ld_qkv + H + head * HD;
+  const float* kbase = qkv + row0 * ld_qkv + H + blk.head * BERT_HD;
   const float* vbase = kbase + H;
   f32x4 qv[16], acc[16];
   float* dov = Df + tid * DF_LD;
@@ -312,36 +244,27 @@ __global__ __launch_bounds__(64) void bert_attn_dq_f32_kernel(const float* __res
     f32x4 d{0.f, 0.f, 0.f, 0.f};
     qv[c] = acc[c] = d;
     if (live) {
-      qv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + q) * ld_qkv + head * HD + 4 * c) * 0.125f;     // exact: a power of two
-      d = *reinterpret_cast<const f32x4*>(dctx + (row0 + q) * ld_dctx + head * HD + 4 * c);
+      qv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + q) * ld_qkv + blk.head * BERT_HD + 4 * c) * 0.125f;     // exact: a power of two
+      d = *reinterpret_cast<const f32x4*>(dctx + (row0 + q) * ld_dctx + blk.head * BERT_HD + 4 * c);
     }
     *reinterpret_cast<f32x4*>(dov + 4 * c) = d;
   }
   float m = -INFINITY, l = 0.f, dacc = 0.f, lse = INFINITY, delta = 0.f;
   for (int pass = 0; pass < 2; ++pass) {
-    for (int k0 = 0; k0 < L; k0 += F_T) {
+    for (int k0 = 0; k0 < L; k0 += AT_F) {
       __syncthreads();
-      for (int i = tid; i < F_T * 16; i += 64) {
-        const int key = i >> 4, c = i & 15;
-        f32x4 kv{0.f, 0.f, 0.f, 0.f}, vv{0.f, 0.f, 0.f, 0.f};
-        if (k0 + key < L) {
-          kv = *reinterpret_cast<const f32x4*>(kbase + (long long)(k0 + key) * ld_qkv + 4 * c);
-          vv = *reinterpret_cast<const f32x4*>(vbase + (long long)(k0 + key) * ld_qkv + 4 * c);
-        }
-        *reinterpret_cast<f32x4*>(Kf + key * HD + 4 * c) = kv;
-        *reinterpret_cast<f32x4*>(Vf + key * HD + 4 * c) = vv;
-      }
-      if (tid < F_T) mk[tid] = k0 + tid < L ? mask[row0 + k0 + tid] : 0.f;
+      stage_rows_f32(Kf, kbase, ld_qkv, Vf, vbase, ld_qkv, k0, L, tid);
+      if (tid < AT_F) mk[tid] = k0 + tid < L ? mask[row0 + k0 + tid] : 0.f;
       __syncthreads();
-      for (int key = 0; key < F_T; ++key) {
+      for (int key = 0; key < AT_F; ++key) {
         if (mk[key] == 0.f) continue;                         // the same for every thread
         f32x4 d4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 16; ++c) d4 += qv[c] * *reinterpret_cast<const f32x4*>(Kf + key * HD + 4 * c);
+        for (int c = 0; c < 16; ++c) d4 += qv[c] * *reinterpret_cast<const f32x4*>(Kf + key * BERT_HD + 4 * c);
         const float s = (d4.x + d4.y) + (d4.z + d4.w);
         f32x4 e4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 16; ++c) e4 += *reinterpret_cast<const f32x4*>(dov + 4 * c) * *reinterpret_cast<const f32x4*>(Vf + key * HD + 4 * c);
+        for (int c = 0; c < 16; ++c) e4 += *reinterpret_cast<const f32x4*>(dov + 4 * c) * *reinterpret_cast<const f32x4*>(Vf + key * BERT_HD + 4 * c);
         const float dp = (e4.x + e4.y) + (e4.z + e4.w);
         if (pass == 0) {
           const float m_new = fmaxf(m, s);                    // s is finite, so m_new is
@@ -352,7 +275,7 @@ __global__ __launch_bounds__(64) void bert_attn_dq_f32_kernel(const float* __res
         } else {
           const float ds = expf(s - lse) * (dp - delta);
 #pragma unroll
-          for (int c = 0; c < 16; ++c) acc[c] += ds * *reinterpret_cast<const f32x4*>(Kf + key * HD + 4 * c);
+          for (int c = 0; c < 16; ++c) acc[c] += ds * *reinterpret_cast<const f32x4*>(Kf + key * BERT_HD + 4 * c);
         }
       }
     }
@@ -360,7 +283,7 @@ __global__ __launch_bounds__(64) void bert_attn_dq_f32_kernel(const float* __res
       lse = l > 0.f ? m + logf(l) : INFINITY;
       delta = l > 0.f ? dacc / l : 0.f;
       if (live) {
-        const long long at = ((long long)b * heads + head) * L + q;
+        const long long at = ((long long)blk.b * heads + blk.head) * L + q;
         ws[at] = lse;
         ws[nstat + at] = delta;
       }
@@ -368,7 +291,7 @@ __global__ __launch_bounds__(64) void bert_attn_dq_f32_kernel(const float* __res
   }
   if (live) {
 #pragma unroll
-    for (int c = 0; c < 16; ++c) *reinterpret_cast<f32x4*>(dqkv + (row0 + q) * ld_dqkv + head * HD + 4 * c) = acc[c] * 0.125f;
+    for (int c = 0; c < 16; ++c) *reinterpret_cast<f32x4*>(dqkv + (row0 + q) * ld_dqkv + blk.head * BERT_HD + 4 * c) = acc[c] * 0.125f;
   }
 }
 
@@ -377,71 +300,62 @@ __global__ __launch_bounds__(64) void bert_attn_dkdv_f32_kernel(const float* __r
                                                                 const float* __restrict__ dctx, float* __restrict__ dqkv,
                                                                 const float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx,
                                                                 int ld_dqkv, int nkt, long long nstat) {
-  __shared__ __attribute__((aligned(16))) float Qf[F_T * HD];
-  __shared__ __attribute__((aligned(16))) float Of[F_T * HD];
-  __shared__ float lse_s[F_T];
-  __shared__ float del_s[F_T];
+  __shared__ __attribute__((aligned(16))) float Qf[AT_F * BERT_HD];
+  __shared__ __attribute__((aligned(16))) float Of[AT_F * BERT_HD];
+  __shared__ float lse_s[AT_F];
+  __shared__ float del_s[AT_F];
   const int tid = threadIdx.x;
-  const int heads = H / HD;
-  const int kt = blockIdx.x % nkt, head = (blockIdx.x / nkt) % heads, b = blockIdx.x / (nkt * heads);
-  const long long row0 = (long long)b * L;
-  const int key = kt * BQ + tid;
+  const int heads = H / BERT_HD;
+  const AttnBlock blk = attn_block(heads, nkt);
+  const long long row0 = (long long)blk.b * L;
+  const int key = blk.tile * AT_OWN + tid;
   const bool live = key < L;
   const bool valid = live && mask[row0 + (live ? key : 0)] != 0.f;
-  const float* qbase = qkv + row0 * ld_qkv + head * HD;
-  const float* obase = dctx + row0 * ld_dctx + head * HD;
-  const float* lse_g = ws + ((long long)b * heads + head) * L;
+  const float* qbase = qkv + row0 * ld_qkv + blk.head * BERT_HD;
+  const float* obase = dctx + row0 * ld_dctx + blk.head * BERT_HD;
+  const float* lse_g = ws + ((long long)blk.b * heads + blk.head) * L;
   f32x4 kv[16], vv[16], dk[16], dv[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     kv[c] = vv[c] = dk[c] = dv[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (live) {
-      kv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + key) * ld_qkv + H + head * HD + 4 * c) * 0.125f;
-      vv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + key) * ld_qkv + 2 * H + head * HD + 4 * c);
+      kv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + key) * ld_qkv + H + blk.head * BERT_HD + 4 * c) * 0.125f;
+      vv[c] = *reinterpret_cast<const f32x4*>(qkv + (row0 + key) * ld_qkv + 2 * H + blk.head * BERT_HD + 4 * c);
     }
   }
-  for (int q0 = 0; q0 < L; q0 += F_T) {
+  for (int q0 = 0; q0 < L; q0 += AT_F) {
     __syncthreads();
-    for (int i = tid; i < F_T * 16; i += 64) {
-      const int qi = i >> 4, c = i & 15;
-      f32x4 a{0.f, 0.f, 0.f, 0.f}, o{0.f, 0.f, 0.f, 0.f};
-      if (q0 + qi < L) {
-        a = *reinterpret_cast<const f32x4*>(qbase + (long long)(q0 + qi) * ld_qkv + 4 * c);
-        o = *reinterpret_cast<const f32x4*>(obase + (long long)(q0 + qi) * ld_dctx + 4 * c);
-      }
-      *reinterpret_cast<f32x4*>(Qf + qi * HD + 4 * c) = a;
-      *reinterpret_cast<f32x4*>(Of + qi * HD + 4 * c) = o;
-    }
-    if (tid < F_T) {
+    stage_rows_f32(Qf, qbase, ld_qkv, Of, obase, ld_dctx, q0, L, tid);
+    if (tid < AT_F) {
       const bool in = q0 + tid < L;
       lse_s[tid] = in ? lse_g[q0 + tid] : INFINITY;
       del_s[tid] = in ? lse_g[nstat + q0 + tid] : 0.f;
     }
     __syncthreads();
-    const int nq = L - q0 < F_T ? L - q0 : F_T;
+    const int nq = L - q0 < AT_F ? L - q0 : AT_F;
     for (int qi = 0; qi < nq; ++qi) {
       const float ls = lse_s[qi];
       if (ls == INFINITY) continue;                           // the same for every thread: a sample without a valid key
       f32x4 d4{0.f, 0.f, 0.f, 0.f}, e4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
-        d4 += kv[c] * *reinterpret_cast<const f32x4*>(Qf + qi * HD + 4 * c);
-        e4 += vv[c] * *reinterpret_cast<const f32x4*>(Of + qi * HD + 4 * c);
+        d4 += kv[c] * *reinterpret_cast<const f32x4*>(Qf + qi * BERT_HD + 4 * c);
+        e4 += vv[c] * *reinterpret_cast<const f32x4*>(Of + qi * BERT_HD + 4 * c);
       }
       const float p = valid ? expf(((d4.x + d4.y) + (d4.z + d4.w)) - ls) : 0.f;
       const float ds = p * (((e4.x + e4.y) + (e4.z + e4.w)) - del_s[qi]);
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
-        dv[c] += p * *reinterpret_cast<const f32x4*>(Of + qi * HD + 4 * c);
-        dk[c] += ds * *reinterpret_cast<const f32x4*>(Qf + qi * HD + 4 * c);
+        dv[c] += p * *reinterpret_cast<const f32x4*>(Of + qi * BERT_HD + 4 * c);
+        dk[c] += ds * *reinterpret_cast<const f32x4*>(Qf + qi * BERT_HD + 4 * c);
       }
     }
   }
   if (live) {
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-      *reinterpret_cast<f32x4*>(dqkv + (row0 + key) * ld_dqkv + H + head * HD + 4 * c) = dk[c] * 0.125f;
-      *reinterpret_cast<f32x4*>(dqkv + (row0 + key) * ld_dqkv + 2 * H + head * HD + 4 * c) = dv[c];
+      *reinterpret_cast<f32x4*>(dqkv + (row0 + key) * ld_dqkv + H + blk.head * BERT_HD + 4 * c) = dk[c] * 0.125f;
+      *reinterpret_cast<f32x4*>(dqkv + (row0 + key) * ld_dqkv + 2 * H + blk.head * BERT_HD + 4 * c) = dv[c];
     }
   }
 }
@@ -457,22 +371,15 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     sg[j] = sb[j] = gam[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (lane + 64 * j < nq) gam[j] = *reinterpret_cast<const f32x4*>(a.gamma + 4 * (lane + 64 * j));
+    if (ln_chunk(lane, j) < nq) gam[j] = *reinterpret_cast<const f32x4*>(a.gamma + 4 * ln_chunk(lane, j));
   }
   for (long long r = (long long)blockIdx.x * 4 + w; r < a.M; r += (long long)gridDim.x * 4) {
     f32x4 v[4], G[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = lane + 64 * j;
-      v[j] = G[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (c < nq) {
-        v[j] = ld4<F32>(a.y, r * a.ld_y + 4 * c);
-        if (a.x) v[j] += ld4<F32>(a.x, r * a.ld_x + 4 * c);
-        G[j] = ld4<F32>(a.g, r * a.ld_g + 4 * c);
-        if (a.g2) G[j] += ld4<F32>(a.g2, r * a.ld_g2 + 4 * c);
-      }
-    }
-    // mean and rstd: bert_ln_row's two passes, operation for operation
+    bert_ln_load<F32>(v, a.y, r * a.ld_y, a.x, r * a.ld_x, lane, nq);
+    bert_ln_load<F32>(G, a.g, r * a.ld_g, a.g2, r * a.ld_g2, lane, nq);
+    // Mean and rstd in bert_ln_row's two passes, written out here and NOT shared with it: the compiler contracts the forward's
+    // v - mu (and its squares) into fused multiply-adds and leaves these apart, so the two round differently in the last bit.  One
+    // function called from both compiles to the forward's form here and moves the bits this kernel has stored so far.
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
@@ -480,7 +387,7 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (lane + 64 * j < nq) {
+      if (ln_chunk(lane, j) < nq) {
         const f32x4 d = v[j] - mu;
         q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
       }
@@ -488,7 +395,7 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (lane + 64 * j < nq) {
+      if (ln_chunk(lane, j) < nq) {
         v[j] = (v[j] - mu) * rs;                              // xhat
         const f32x4 gg = G[j] * gam[j], gx = gg * v[j];
         c1 += (gg.x + gg.y) + (gg.z + gg.w);
@@ -501,7 +408,7 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
     c2 = wave_sum(c2) * inv_n;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int c = lane + 64 * j;
+      const int c = ln_chunk(lane, j);
       if (c < nq) st4<F32>(a.ds, r * a.ld_ds + 4 * c, (G[j] * gam[j] - c1 - v[j] * c2) * rs);
     }
   }
@@ -509,7 +416,7 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
   if (w > 0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int c = lane + 64 * j;
+      const int c = ln_chunk(lane, j);
       if (c < nq) {
         *reinterpret_cast<f32x4*>(&part[w - 1][4 * c]) = sg[j];
         *reinterpret_cast<f32x4*>(&part[w - 1][a.N + 4 * c]) = sb[j];
@@ -521,7 +428,7 @@ __global__ __launch_bounds__(256) void bert_add_ln_bwd_kernel(mmdeer_bert_add_ln
     float* dst = a.scratch + (long long)blockIdx.x * 2 * a.N;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int c = lane + 64 * j;
+      const int c = ln_chunk(lane, j);
       if (c < nq) {
         f32x4 tg = sg[j], tb = sb[j];
         for (int k = 0; k < 3; ++k) {                         // wave order
@@ -557,7 +464,7 @@ __global__ __launch_bounds__(256) void bert_ln_fold_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------ GELU backward
 __device__ __forceinline__ float gelu_erf_grad(float x) {
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * (0.39894228040143267794f * expf(-0.5f * x * x));
+  return 0.5f * (1.0f + erff(x * GELU_RSQRT2)) + x * (0.39894228040143267794f * expf(-0.5f * x * x));
 }
 
 template <bool F32>
@@ -571,13 +478,7 @@ __global__ __launch_bounds__(256) void bert_gelu_bwd_kernel(mmdeer_bert_gelu_bwd
   }
 }
 
-bool finite_nonneg(float e) { return e >= 0.f && e <= 3.0e38f; }     // false for a NaN
-bool hidden_ok(int H) { return H >= HD && H % HD == 0 && H <= MMDEER_BERT_MAX_HIDDEN; }
-constexpr long long TWO31 = 1ll << 31;
-
-bool attn_shape_ok(int B, int L, int H) { return hidden_ok(H) && B >= 0 && L >= 0 && (L >= 1 || B == 0) && L <= MMDEER_BERT_MAX_TOKENS; }
-long long attn_ws_bytes(int B, int L, int H) { return 2ll * B * (H / HD) * L * (long long)sizeof(float); }
-bool ln_n_ok(int N) { return N >= 4 && N % 4 == 0 && N <= MMDEER_BERT_MAX_HIDDEN; }
+long long attn_ws_bytes(int B, int L, int H) { return 2ll * B * (H / BERT_HD) * L * (long long)sizeof(float); }
 int ln_blocks(int M) { return (M + 3) / 4 < LN_PARTS ? (M + 3) / 4 : LN_PARTS; }
 
 }  // namespace
@@ -588,20 +489,18 @@ using namespace mmdeer;
 extern "C" {
 
 long long mmdeer_bert_attn_bwd_workspace(int32_t B, int32_t L, int32_t H) {
-  if (!attn_shape_ok(B, L, H)) return -1;
+  if (attn_shape_fault(B, L, H)) return -1;
   return attn_ws_bytes(B, L, H);
 }
 
 int mmdeer_bert_attn_bwd(const mmdeer_bert_attn_bwd_args* a) {
   MMDEER_CHECK(a, "bert_attn_bwd: NULL args");
-  MMDEER_CHECK(hidden_ok(a->H), "bert_attn_bwd: unsupported H = %d (a multiple of 64, 64 .. %d)", a->H, MMDEER_BERT_MAX_HIDDEN);
-  MMDEER_CHECK(a->B >= 0 && a->L >= 0 && (a->L >= 1 || a->B == 0), "bert_attn_bwd: bad shape (B %d, L %d: L >= 1 with B > 0)", a->B, a->L);
-  MMDEER_CHECK(a->L <= MMDEER_BERT_MAX_TOKENS, "bert_attn_bwd: L = %d is above %d tokens", a->L, MMDEER_BERT_MAX_TOKENS);
-  MMDEER_CHECK(a->ld_qkv >= 3 * a->H && a->ld_qkv % 8 == 0, "bert_attn_bwd: bad leading dimension ld_qkv = %d (>= 3 H, a multiple of 8)", a->ld_qkv);
-  MMDEER_CHECK(a->ld_dqkv >= 3 * a->H && a->ld_dqkv % 8 == 0, "bert_attn_bwd: bad leading dimension ld_dqkv = %d (>= 3 H, a multiple of 8)", a->ld_dqkv);
-  MMDEER_CHECK(a->ld_dctx >= a->H && a->ld_dctx % 8 == 0, "bert_attn_bwd: bad leading dimension ld_dctx = %d (>= H, a multiple of 8)", a->ld_dctx);
+  TRY(attn_shape_check("bert_attn_bwd", a->B, a->L, a->H));
+  MMDEER_CHECK(ld_ok(a->ld_qkv, 3 * a->H, 8), "bert_attn_bwd: bad leading dimension ld_qkv = %d (>= 3 H, a multiple of 8)", a->ld_qkv);
+  MMDEER_CHECK(ld_ok(a->ld_dqkv, 3 * a->H, 8), "bert_attn_bwd: bad leading dimension ld_dqkv = %d (>= 3 H, a multiple of 8)", a->ld_dqkv);
+  MMDEER_CHECK(ld_ok(a->ld_dctx, a->H, 8), "bert_attn_bwd: bad leading dimension ld_dctx = %d (>= H, a multiple of 8)", a->ld_dctx);
   const long long rows = (long long)a->B * a->L;
-  MMDEER_CHECK(rows * a->ld_qkv < TWO31 && rows * a->ld_dqkv < TWO31 && rows * a->ld_dctx < TWO31,
+  MMDEER_CHECK(under_2_31(rows, a->ld_qkv) && under_2_31(rows, a->ld_dqkv) && under_2_31(rows, a->ld_dctx),
                "bert_attn_bwd: qkv, dqkv or dctx has 2^31 elements or more");
   if (rows == 0) return 0;
   MMDEER_CHECK(a->qkv && a->mask && a->dctx && a->dqkv && a->workspace, "bert_attn_bwd: NULL pointer (qkv, mask, dctx, dqkv, workspace)");
@@ -609,7 +508,7 @@ int mmdeer_bert_attn_bwd(const mmdeer_bert_attn_bwd_args* a) {
                a->workspace_bytes, attn_ws_bytes(a->B, a->L, a->H));
   MMDEER_CHECK(al16(a->qkv) && al16(a->dctx) && al16(a->dqkv) && al16(a->workspace) && al4(a->mask),
                "bert_attn_bwd: misaligned pointer (qkv, dctx, dqkv, workspace 16 bytes; mask 4 bytes)");
-  const int heads = a->H / HD, nt = (a->L + BQ - 1) / BQ;
+  const int heads = a->H / BERT_HD, nt = (a->L + AT_OWN - 1) / AT_OWN;
   const long long nstat = (long long)a->B * heads * a->L;
   const unsigned grid = (unsigned)((long long)a->B * heads * nt);       // < 2^31 / 192
   hipStream_t st = (hipStream_t)a->stream;
@@ -639,12 +538,12 @@ int mmdeer_bert_add_ln_bwd(const mmdeer_bert_add_ln_bwd_args* a) {
   MMDEER_CHECK(a, "bert_add_ln_bwd: NULL args");
   MMDEER_CHECK(ln_n_ok(a->N), "bert_add_ln_bwd: unsupported N = %d (a multiple of 4, 4 .. %d)", a->N, MMDEER_BERT_MAX_HIDDEN);
   MMDEER_CHECK(a->M >= 0, "bert_add_ln_bwd: bad shape (M %d)", a->M);
-  auto ld_ok = [&](int ld) { return ld >= a->N && ld % 4 == 0; };
-  MMDEER_CHECK(ld_ok(a->ld_y) && ld_ok(a->ld_g) && ld_ok(a->ld_ds) && (!a->x || ld_ok(a->ld_x)) && (!a->g2 || ld_ok(a->ld_g2)),
+  auto ld4_ok = [&](int ld) { return ld_ok(ld, a->N, 4); };
+  MMDEER_CHECK(ld4_ok(a->ld_y) && ld4_ok(a->ld_g) && ld4_ok(a->ld_ds) && (!a->x || ld4_ok(a->ld_x)) && (!a->g2 || ld4_ok(a->ld_g2)),
                "bert_add_ln_bwd: bad leading dimension (ld_y %d, ld_x %d, ld_g %d, ld_g2 %d, ld_ds %d: >= N, multiples of 4)", a->ld_y, a->ld_x,
                a->ld_g, a->ld_g2, a->ld_ds);
   MMDEER_CHECK(finite_nonneg(a->eps), "bert_add_ln_bwd: eps must be finite and >= 0");
-  auto small = [&](int ld) { return (long long)a->M * ld < TWO31; };
+  auto small = [&](int ld) { return under_2_31(a->M, ld); };
   MMDEER_CHECK(small(a->ld_y) && small(a->ld_g) && small(a->ld_ds) && (!a->x || small(a->ld_x)) && (!a->g2 || small(a->ld_g2)),
                "bert_add_ln_bwd: an operand has 2^31 elements or more");
   MMDEER_CHECK(!a->dgamma == !a->dbeta, "bert_add_ln_bwd: dgamma and dbeta go together (both or neither)");
@@ -656,7 +555,7 @@ int mmdeer_bert_add_ln_bwd(const mmdeer_bert_add_ln_bwd_args* a) {
   MMDEER_CHECK(!sums || a->scratch_elems >= need, "bert_add_ln_bwd: scratch too small (%lld elements, %lld needed)", a->scratch_elems, need);
   MMDEER_CHECK(al16(a->gamma) && al16(a->dgamma) && al16(a->dbeta) && (!sums || al16(a->scratch)) && al_act4(a->act_f32, {a->y, a->x, a->g, a->g2, a->ds}),
                "bert_add_ln_bwd: misaligned pointer (gamma, dgamma, dbeta, scratch 16 bytes; y, x, g, g2, ds 4 act elements)");
-  const unsigned grid = sums ? (unsigned)ln_blocks(a->M) : (unsigned)((a->M + 3) / 4 < 65536 ? (a->M + 3) / 4 : 65536);
+  const unsigned grid = sums ? (unsigned)ln_blocks(a->M) : row_grid(a->M);
   MMDEER_LAUNCH_ACT(bert_add_ln_bwd_kernel, a->act_f32, dim3(grid), dim3(256), (hipStream_t)a->stream, *a, sums);
   if (sums) {
     hipLaunchKernelGGL(bert_ln_fold_kernel, dim3((a->N / 2 + 15) / 16), dim3(256), 0, (hipStream_t)a->stream, (const float*)a->scratch, a->dgamma,
@@ -670,16 +569,15 @@ int mmdeer_bert_gelu_bwd(const mmdeer_bert_gelu_bwd_args* a) {
   MMDEER_CHECK(a, "bert_gelu_bwd: NULL args");
   MMDEER_CHECK(a->N >= 4 && a->N % 4 == 0, "bert_gelu_bwd: unsupported N = %d (a multiple of 4)", a->N);
   MMDEER_CHECK(a->M >= 0, "bert_gelu_bwd: bad shape (M %d)", a->M);
-  MMDEER_CHECK(a->ld_x >= a->N && a->ld_x % 4 == 0 && a->ld_g >= a->N && a->ld_g % 4 == 0 && a->ld_dx >= a->N && a->ld_dx % 4 == 0,
+  MMDEER_CHECK(ld_ok(a->ld_x, a->N, 4) && ld_ok(a->ld_g, a->N, 4) && ld_ok(a->ld_dx, a->N, 4),
                "bert_gelu_bwd: bad leading dimension (ld_x %d, ld_g %d, ld_dx %d: >= N, multiples of 4)", a->ld_x, a->ld_g, a->ld_dx);
-  MMDEER_CHECK((long long)a->M * a->ld_x < TWO31 && (long long)a->M * a->ld_g < TWO31 && (long long)a->M * a->ld_dx < TWO31,
+  MMDEER_CHECK(under_2_31(a->M, a->ld_x) && under_2_31(a->M, a->ld_g) && under_2_31(a->M, a->ld_dx),
                "bert_gelu_bwd: an operand has 2^31 elements or more");
   if (a->M == 0) return 0;
   MMDEER_CHECK(a->x && a->g && a->dx, "bert_gelu_bwd: NULL pointer (x, g, dx)");
   MMDEER_CHECK(al_act4(a->act_f32, {a->x, a->g, a->dx}), "bert_gelu_bwd: misaligned pointer (x, g, dx: 4 act elements)");
   const long long chunks = (long long)a->M * (a->N / 4);
-  const unsigned grid = (unsigned)((chunks + 255) / 256 < 16384 ? (chunks + 255) / 256 : 16384);
-  MMDEER_LAUNCH_ACT(bert_gelu_bwd_kernel, a->act_f32, dim3(grid), dim3(256), (hipStream_t)a->stream, *a, chunks);
+  MMDEER_LAUNCH_ACT(bert_gelu_bwd_kernel, a->act_f32, dim3(chunk_grid(chunks)), dim3(256), (hipStream_t)a->stream, *a, chunks);
   return 0;
 }
 
