@@ -4,7 +4,7 @@ and EnhancedTextEncoder is the reference's no-BERT configuration on token ids an
 ``forward_embeddings`` takes the caller's own contextual embeddings in place of BERT's last_hidden_state), or, constructed
 with ``bert=BertEncoder(config)``, its BERT configuration: the trunk on HIP, frozen, or with ``finetune_layers=k`` its last k
 layers trained as the reference trains layers 6-11 (mmdeer.bert; parameters named as transformers.BertModel's, so a checkpoint
-of the reference's ``self.bert`` loads; no dropout inside the trunk; tokenisation and pretrained weights stay outside).  EnhancedVideoEncoder is
+of the reference's ``self.bert`` loads; ``dropout=True`` runs the reference's hidden and attention dropout inside the trunk in train(), off by default; tokenisation and pretrained weights stay outside).  EnhancedVideoEncoder is
 the reference's encoder downstream of its spatial CNN, on (B, T, 512) per-frame features (mmdeer.video; frame tensors raise);
 FrameVideoEncoder is the same encoder from frames, its Conv2d backbone run on HIP, forward only (mmdeer.frames)."""
 from mmdeer.side import EnhancedAudioEncoder  # noqa: F401

@@ -3,9 +3,10 @@
 
     python tools/bert_ab_equal.py <library A> <library B> [--out listing.json]
 
-One fresh child process per library, one after the other (the library is chosen as tools/bench_with_lib.py chooses it: the ABI is
-the same in both); a child that ends abnormally ends the tool before the next one starts.  The child runs the operator tests of
-tests/test_gpu_bert.py and tests/test_gpu_bert_backward.py themselves, every parametrised case in fp32 and bf16, with a library
+One fresh child process per library, one after the other (the library is chosen as tools/bench_with_lib.py chooses it: both must
+export every symbol of this tree's headers, so a build from before a header was added does not load); a child that ends abnormally
+ends the tool before the next one starts.  The child runs the operator tests of tests/test_gpu_bert.py, tests/test_gpu_bert_backward.py
+and tests/test_gpu_bert_dropout.py themselves, every parametrised case in fp32 and bf16, with a library
 handle that after each ``mmdeer_bert_*`` call prints the sha256 of what the call stored -- so the shapes, masks, paddings and
 inputs are the tests' own:
   mmdeer_bert_attn_fwd / _bwd      L in {1, 37, 64, 65, 129, 512}, 2 and 12 heads, the five masks (a dead sample among them), scores
@@ -13,6 +14,7 @@ inputs are the tests' own:
   mmdeer_bert_embed_fwd            (B, L) in {(1, 1), (1, 5), (2, 67)} x H in {128, 768, 1024}, with and without type ids
   mmdeer_bert_add_ln_fwd / _bwd    the tests' M x N, with and without x / g2, in place, with and without the column sums
   mmdeer_bert_gelu_fwd / _bwd      the erf grids, out of place and in place
+  the five dropout entries         (include/mmdeer_bert_drop.h) the dropout tests' attention, add-LN and embedding cases, p in {0, 0.1, 0.5}
 Then one forward + backward of the tiny and the 768-wide module with finetune_layers 1 and 2 (the tests' ``backward_once``):
 last_hidden_state, every hidden state, every parameter gradient, and again every launch on the way.
 The parent compares the two listings and exits 1 at the first difference, naming the case and the tensor."""
@@ -40,6 +42,11 @@ STORED = {
                                "dbeta": lambda a: (1, 0, a.N, "f32")},
     "mmdeer_bert_gelu_bwd": {"dx": lambda a: (a.M, a.ld_dx, a.N, "act")},
 }
+STORED.update({
+    "mmdeer_bert_embed_drop_fwd": STORED["mmdeer_bert_embed_fwd"], "mmdeer_bert_attn_drop_fwd": STORED["mmdeer_bert_attn_fwd"],
+    "mmdeer_bert_drop_add_ln_fwd": STORED["mmdeer_bert_add_ln_fwd"], "mmdeer_bert_attn_drop_bwd": STORED["mmdeer_bert_attn_bwd"],
+    "mmdeer_bert_drop_add_ln_bwd": {**STORED["mmdeer_bert_add_ln_bwd"], "dy": lambda a: (a.M, a.ld_dy, a.N, "act")},
+})
 
 
 def child(lib_path):
@@ -57,6 +64,7 @@ def child(lib_path):
     from mmdeer import _lib
     from tests import test_gpu_bert as TF
     from tests import test_gpu_bert_backward as TB
+    from tests import test_gpu_bert_dropout as TD
     from tests.test_cpu_bert_backward import upstream
 
     real, where, out = _lib.load(), ["", 0], sys.stdout
@@ -114,7 +122,9 @@ def child(lib_path):
     for fn in (TF.test_attention_against_float64, TF.test_attention_at_512_tokens, TF.test_attention_with_large_scores,
                TF.test_embed_ln_against_float64, TF.test_add_ln_against_float64, TF.test_gelu_is_the_erf_form,
                TB.test_attention_backward_against_float64, TB.test_attention_backward_at_512_tokens,
-               TB.test_attention_backward_with_large_scores, TB.test_add_ln_backward_against_float64, TB.test_gelu_backward_is_the_erf_forms):
+               TB.test_attention_backward_with_large_scores, TB.test_add_ln_backward_against_float64, TB.test_gelu_backward_is_the_erf_forms,
+               TD.test_attention_dropout_against_float64, TD.test_attention_dropout_at_512_tokens, TD.test_drop_add_ln_against_float64,
+               TD.test_embed_dropout_on_the_golden_tables):
         for kw in cases(fn):
             where[:] = [f"{fn.__name__}[{' '.join(f'{k}={v}' for k, v in sorted(kw.items()))}]", 0]
             with contextlib.redirect_stdout(io.StringIO()):

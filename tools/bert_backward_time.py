@@ -35,7 +35,8 @@ TAIL = 6
 
 def yardstick(cfg, sd, dt, dev):
     import transformers
-    hf = transformers.BertConfig(**{k: v for k, v in cfg.items() if k not in ("add_pooling_layer", "position_embedding_type")},
+    hf = transformers.BertConfig(**{k: v for k, v in cfg.items() if k not in ("add_pooling_layer", "position_embedding_type", "hidden_dropout_prob",
+                                                                             "attention_probs_dropout_prob")},
                                  hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     model = transformers.BertModel(hf, add_pooling_layer=False)
     model.load_state_dict({k: v for k, v in sd.items() if not k.startswith("pooler.")}, strict=True)

@@ -49,9 +49,20 @@ Activation gradients are stored in the compute dtype; parameter gradients are su
 backward runs store the same bits) and returned in the parameters' dtype.  A tail parameter switched back to
 ``requires_grad=False`` gets no gradient.  There is no gradient with respect to the ids, and ``hidden_states`` are graph-free copies.
 
-THE ONE DIFFERENCE in training: there is NO dropout inside the trunk in either mode (``.train()`` changes nothing).  The
-reference's BERT trains with ``hidden_dropout_prob = attention_probs_dropout_prob = 0.1``; this trunk fine-tunes as
-``BertConfig(hidden_dropout_prob=0, attention_probs_dropout_prob=0)`` does.
+DROPOUT is off by default: ``BertEncoder(config, compute_dtype, finetune_layers)`` has none in either mode (``.train()`` changes
+nothing), whatever the config's probabilities say -- it fine-tunes as ``BertConfig(hidden_dropout_prob=0, attention_probs_dropout_prob=0)``
+does.  ``dropout=True`` is the reference's training configuration (its BERT trains with both probabilities 0.1, BertConfig's
+defaults): in ``training`` mode ``hidden_dropout_prob`` is live on the embeddings and behind the dense of BertSelfOutput and BertOutput,
+and ``attention_probs_dropout_prob`` on the attention probabilities, in ALL layers, the frozen ones and ``no_grad`` calls included,
+whatever ``finetune_layers`` is; ``eval()`` stores the bits of a ``dropout=False`` encoder.  The sites run inside the launches above
+(include/mmdeer_bert_drop.h: ``mmdeer_bert_embed_drop_fwd``, ``mmdeer_bert_attn_drop_fwd``, ``mmdeer_bert_drop_add_ln_fwd``, and in the
+backward ``mmdeer_bert_drop_add_ln_bwd`` for launches 1 and 7, whose second output dy = ds o m feeds the two GEMMs behind each while ds
+goes on by the residual branch, and ``mmdeer_bert_attn_drop_bwd``): no extra launch in either direction, the tape is unchanged (y
+and y2 are kept pre-dropout) and no mask is stored -- the library's counter hash regenerates it from (``dropout_seed``, step, site,
+row, column), with one site id per (layer, place) from a block that no other module uses (``SITE_EMBED``, ``site(layer, place)``).  A
+site whose probability is 0 runs its plain entry.  ``_train_step`` advances by one per forward in which dropout is live; the backward
+of a forward uses that forward's step; two runs of the same step store the same bits.  Not built: a captured graph replays the step
+it captured, because the step is a host value of each launch (feeding these entries a device-resident counter is a later change).
 
 One deviation from ``BertModel`` in the forward: a sample whose mask has no valid token gets zeros from every attention layer where
 the reference averages V uniformly (include/mmdeer_bert.h), and, mirrored in the backward, zeros in all of its dqkv; everything
@@ -73,7 +84,16 @@ MAX_TOKENS = _lib.BERT_CONSTANTS["BERT_MAX_TOKENS"]
 # bert-base-uncased
 DEFAULTS = {"vocab_size": 30522, "hidden_size": 768, "num_hidden_layers": 12, "num_attention_heads": 12, "intermediate_size": 3072,
             "max_position_embeddings": 512, "type_vocab_size": 2, "layer_norm_eps": 1e-12, "hidden_act": "gelu", "initializer_range": 0.02,
-            "position_embedding_type": "absolute", "pad_token_id": 0, "add_pooling_layer": True}
+            "position_embedding_type": "absolute", "pad_token_id": 0, "add_pooling_layer": True,
+            "hidden_dropout_prob": 0.1, "attention_probs_dropout_prob": 0.1}       # read only with dropout=True
+# dropout site ids (include/mmdeer_bert_drop.h): one for the embeddings, then per layer attention, self-output, output
+SITE_EMBED = _lib.BERT_DROP_CONSTANTS["BERT_DROP_SITE_EMBED"]
+SITE_LAYER0 = _lib.BERT_DROP_CONSTANTS["BERT_DROP_SITE_LAYER0"]
+_ATTN, _SELF_OUT, _OUT = 0, 1, 2
+
+
+def site(layer: int, place: int) -> int:
+    return SITE_LAYER0 + 4 * layer + place
 
 
 def _config(config) -> dict:
@@ -104,12 +124,25 @@ def _named(**children) -> nn.Module:
 
 
 class BertEncoder(nn.Module):
-    """``BertModel(BertConfig(**config))`` on HIP; ``finetune_layers=k`` trains its last ``k`` layers (the module docstring has both
-    launch plans and what is not built)."""
+    """``BertModel(BertConfig(**config))`` on HIP; ``finetune_layers=k`` trains its last ``k`` layers; ``dropout=True`` makes the config's
+    two dropout probabilities live in ``train()``, drawn from ``dropout_seed`` and a step counter (the module docstring has both
+    launch plans, the dropout sites and what is not built)."""
 
-    def __init__(self, config=None, compute_dtype: str = "bf16", finetune_layers: int = 0):
+    def __init__(self, config=None, compute_dtype: str = "bf16", finetune_layers: int = 0, dropout: bool = False, dropout_seed: int = 0):
         super().__init__()
         c = self.config = _config(config)
+        if not isinstance(dropout, bool):
+            raise ValueError(f"BertEncoder: dropout must be a bool (got {dropout!r})")
+        if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, int) or not 0 <= dropout_seed < 2 ** 64:
+            raise ValueError(f"BertEncoder: dropout_seed must be an integer in 0 .. 2^64 - 1 (got {dropout_seed!r})")
+        self.dropout, self.dropout_seed, self._train_step = dropout, dropout_seed, 0       # counter-hash dropout: seed + one tick per training forward
+        self.p_hidden = self.p_attn = 0.0
+        if dropout:
+            for key in ("hidden_dropout_prob", "attention_probs_dropout_prob"):
+                v = c[key]
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) < 1.0:       # a NaN fails both comparisons
+                    raise ValueError(f"BertEncoder: {key} must be a number in [0, 1) (got {v!r})")
+            self.p_hidden, self.p_attn = float(c["hidden_dropout_prob"]), float(c["attention_probs_dropout_prob"])
         if isinstance(finetune_layers, bool) or not isinstance(finetune_layers, int) or not 0 <= finetune_layers <= int(c["num_hidden_layers"]):
             raise ValueError(f"BertEncoder: finetune_layers must be an integer in 0 .. num_hidden_layers = {int(c['num_hidden_layers'])} "
                              f"(got {finetune_layers!r})")
@@ -201,12 +234,26 @@ class BertEncoder(nn.Module):
         self._packed, self._packed_key = packed, key
         return packed
 
-    def _add_ln(self, y, x, gamma, beta, out):
-        a = _lib.BertAddLnArgs()
+    def _add_ln(self, y, x, gamma, beta, out, drop=None, site_id=-1):
+        """out = LayerNorm(y + x), or LayerNorm(drop(y) + x) with ``drop`` = (seed, step) where the hidden probability is not 0"""
+        live = drop is not None and self.p_hidden > 0
+        a = _lib.BertDropAddLnArgs() if live else _lib.BertAddLnArgs()
         a.y, a.x, a.gamma, a.beta, a.out, a.eps = y.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), self.eps
         a.M, a.N, a.ld_y, a.ld_x, a.ld_out = y.shape[0], y.shape[1], y.stride(0), x.stride(0), out.stride(0)
         a.act_f32, a.stream = int(self.compute_dtype == "fp32"), _lib.current_stream()
-        _lib.check(_lib.load().mmdeer_bert_add_ln_fwd(C.byref(a)))
+        if live:
+            a.site, a.dropout_p, (a.seed, a.offset) = site_id, self.p_hidden, drop
+            _lib.check(_lib.load().mmdeer_bert_drop_add_ln_fwd(C.byref(a)))
+        else:
+            _lib.check(_lib.load().mmdeer_bert_add_ln_fwd(C.byref(a)))
+
+    def _drop(self):
+        """(seed, step) of this forward where dropout is live, else None; the counter advances by one per live forward"""
+        if self.dropout and self.training and (self.p_hidden > 0 or self.p_attn > 0):
+            d = (int(self.dropout_seed), self._train_step)
+            self._train_step += 1
+            return d
+        return None
 
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, token_type_ids: Optional[torch.Tensor] = None,
                 output_hidden_states: bool = False) -> BertEncoderOutput:
@@ -243,6 +290,7 @@ class BertEncoder(nn.Module):
         dev = input_ids.device
         if B == 0:
             return BertEncoderOutput(torch.empty(0, L, H, dtype=dt, device=dev), () if output_hidden_states else None)
+        drop = self._drop()
         with torch.no_grad():
             lib, stream, M, I = _lib.load(), _lib.current_stream(), B * L, int(self.config["intermediate_size"])
             w = self._operands()
@@ -252,16 +300,21 @@ class BertEncoder(nn.Module):
             x, y = torch.empty(M, H, dtype=dt, device=dev), torch.empty(M, H, dtype=dt, device=dev)
             qkv, ctx, h = torch.empty(M, 3 * H, dtype=dt, device=dev), torch.empty(M, H, dtype=dt, device=dev), torch.empty(M, I, dtype=dt, device=dev)
             word, pos, typ, g0, b0 = w["emb"]
-            a = _lib.BertEmbedArgs()
+            embed_drop = drop is not None and self.p_hidden > 0
+            a = _lib.BertEmbedDropArgs() if embed_drop else _lib.BertEmbedArgs()
             a.ids, a.type_ids, a.word, a.pos, a.type = ids.data_ptr(), _lib.ptr(tts), word.data_ptr(), pos.data_ptr(), typ.data_ptr()
             a.gamma, a.beta, a.x, a.eps = g0.data_ptr(), b0.data_ptr(), x.data_ptr(), self.eps
             a.B, a.L, a.H, a.ld_x, a.act_f32, a.stream = B, L, H, H, f32, stream
             a.V, a.P, a.T = self.config["vocab_size"], self.config["max_position_embeddings"], self.config["type_vocab_size"]
-            _lib.check(lib.mmdeer_bert_embed_fwd(C.byref(a)))
+            if embed_drop:
+                a.site, a.dropout_p, (a.seed, a.offset) = SITE_EMBED, self.p_hidden, drop
+                _lib.check(lib.mmdeer_bert_embed_drop_fwd(C.byref(a)))
+            else:
+                _lib.check(lib.mmdeer_bert_embed_fwd(C.byref(a)))
             states = [x.clone()] if output_hidden_states else None
-            for p in w["layers"][:first_tail if tail else nl]:
+            for li, p in enumerate(w["layers"][:first_tail if tail else nl]):
                 # x1 takes y's buffer (x is free from there), the GELU is in place, and y2 and the layer's output take x's
-                _layer_fwd(self, x, p, m, B, L, qkv, ctx, y, x1=y, h=h, gh=h, y2=x, out=x)
+                _layer_fwd(self, x, p, m, B, L, qkv, ctx, y, x1=y, h=h, gh=h, y2=x, out=x, drop=drop, layer=li)
                 if output_hidden_states:
                     states.append(x.clone())
             shaped = lambda t: t.reshape(B, L, H)             # noqa: E731
@@ -269,36 +322,45 @@ class BertEncoder(nn.Module):
                 return BertEncoderOutput(shaped(x), tuple(shaped(s) for s in states) if output_hidden_states else None)
         del qkv, ctx, h, y
         params = [p for lyr in self.encoder.layer[first_tail:] for p in lyr.parameters()]
-        out = _TailFn.apply(self, x, m, B, L, w["layers"][first_tail:], states, *params)
+        out = _TailFn.apply(self, x, m, B, L, w["layers"][first_tail:], states, (drop, first_tail), *params)
         return BertEncoderOutput(shaped(out), tuple(shaped(s) for s in states) if output_hidden_states else None)
 
 
-def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out):
+def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out, drop=None, layer=0):
     """One BertLayer's forward on the caller's buffers: the eight launches of the module docstring.  ``p``: the layer's packed
-    operands.  Buffers may alias as the frozen path's do (x1 = y, gh = h, y2 = out = x): each is written after its last reader."""
+    operands.  Buffers may alias as the frozen path's do (x1 = y, gh = h, y2 = out = x): each is written after its last reader.
+    ``drop``: (seed, step) where dropout is live: layer ``layer``'s three sites then run their drop entries, in the same launches."""
     lib, c, stream = _lib.load(), enc.compute_dtype, _lib.current_stream()
     f32, (M, H), I = int(c == "fp32"), x.shape, h.shape[1]
     ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=c)
-    at = _lib.BertAttnArgs()
+    attn_drop = drop is not None and enc.p_attn > 0
+    at = _lib.BertAttnDropArgs() if attn_drop else _lib.BertAttnArgs()
     at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), ctx.data_ptr()
     at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
-    _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
+    if attn_drop:
+        at.site, at.dropout_p, (at.seed, at.offset) = site(layer, _ATTN), enc.p_attn, drop
+        _lib.check(lib.mmdeer_bert_attn_drop_fwd(C.byref(at)))
+    else:
+        _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
     ops.linear_into(ctx, p["wo"], p["bo"], y, compute=c)
-    enc._add_ln(y, x, p["g1"], p["b1"], x1)
+    enc._add_ln(y, x, p["g1"], p["b1"], x1, drop, site(layer, _SELF_OUT))
     ops.linear_into(x1, p["wi"], p["bi"], h, compute=c)
     ge = _lib.BertGeluArgs()
     ge.x, ge.out, ge.M, ge.N, ge.ld_x, ge.ld_out, ge.act_f32, ge.stream = h.data_ptr(), gh.data_ptr(), M, I, I, I, f32, stream
     _lib.check(lib.mmdeer_bert_gelu_fwd(C.byref(ge)))
     ops.linear_into(gh, p["wo2"], p["bo2"], y2, compute=c)
-    enc._add_ln(y2, x1, p["g2"], p["b2"], out)
+    enc._add_ln(y2, x1, p["g2"], p["b2"], out, drop, site(layer, _OUT))
 
 
-def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool):
-    """mmdeer_bert_add_ln_bwd -> (ds, dgamma, dbeta); the sums only when wanted"""
+def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool, drop=None, site_id=-1):
+    """mmdeer_bert_add_ln_bwd -> (ds, dy, dgamma, dbeta); the sums only when wanted.  ds is the gradient of x and dy that of y: one
+    tensor, unless ``drop`` = (seed, step) makes it mmdeer_bert_drop_add_ln_bwd, whose dy = ds o m."""
     lib, (M, N) = _lib.load(), y.shape
+    live = drop is not None and enc.p_hidden > 0
     ds = torch.empty_like(y)
+    dy = torch.empty_like(y) if live else ds
     dgamma = dbeta = scratch = None
-    a = _lib.BertAddLnBwdArgs()
+    a = _lib.BertDropAddLnBwdArgs() if live else _lib.BertAddLnBwdArgs()
     if want_sums:
         dgamma, dbeta = torch.empty(N, device=y.device), torch.empty(N, device=y.device)
         a.scratch_elems = lib.mmdeer_bert_add_ln_bwd_scratch(M, N)
@@ -307,8 +369,12 @@ def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool):
     a.dgamma, a.dbeta, a.scratch, a.eps = _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scratch), enc.eps
     a.M, a.N, a.ld_y, a.ld_x, a.ld_g, a.ld_g2, a.ld_ds = M, N, y.stride(0), x.stride(0), g.stride(0), g2.stride(0) if g2 is not None else 0, N
     a.act_f32, a.stream = int(enc.compute_dtype == "fp32"), _lib.current_stream()
-    _lib.check(lib.mmdeer_bert_add_ln_bwd(C.byref(a)))
-    return ds, dgamma, dbeta
+    if live:
+        a.dy, a.ld_dy, a.site, a.dropout_p, (a.seed, a.offset) = dy.data_ptr(), N, site_id, enc.p_hidden, drop
+        _lib.check(lib.mmdeer_bert_drop_add_ln_bwd(C.byref(a)))
+    else:
+        _lib.check(lib.mmdeer_bert_add_ln_bwd(C.byref(a)))
+    return ds, dy, dgamma, dbeta
 
 
 # the parameters of one BertLayer in nn.Module.parameters() order, as _TailFn receives them
@@ -317,21 +383,22 @@ _Q_W, _Q_B, _K_W, _K_B, _V_W, _V_B, _O_W, _O_B, _LN1_W, _LN1_B, _I_W, _I_B, _O2_
 
 class _TailFn(torch.autograd.Function):
     """The fine-tuned tail as one autograd node (the module docstring has both launch plans).  ``packed``: the tail layers' packed
-    operands; ``states``: the caller's list of hidden-state copies, or None."""
+    operands; ``states``: the caller's list of hidden-state copies, or None; ``drop``: ((seed, step) or None, the index of the
+    tail's first layer): the backward regenerates this forward's masks from it, whatever forwards ran in between."""
 
     @staticmethod
-    def forward(ctx, enc, x, m, B, L, packed, states, *params):
+    def forward(ctx, enc, x, m, B, L, packed, states, drop, *params):
         (M, H), I = x.shape, int(enc.config["intermediate_size"])
         new = lambda n: torch.empty(M, n, dtype=x.dtype, device=x.device)      # noqa: E731
         tape = []
-        for p in packed:
+        for li, p in enumerate(packed):
             qkv, cx, y, x1, h, gh, y2, out = new(3 * H), new(H), new(H), new(H), new(I), new(I), new(H), new(H)
-            _layer_fwd(enc, x, p, m, B, L, qkv, cx, y, x1, h, gh, y2, out)
+            _layer_fwd(enc, x, p, m, B, L, qkv, cx, y, x1, h, gh, y2, out, drop=drop[0], layer=drop[1] + li)
             tape.append((x, qkv, cx, y, x1, h, gh, y2))
             x = out
             if states is not None:
                 states.append(x.clone())
-        ctx.enc, ctx.mask, ctx.BL, ctx.packed, ctx.tape = enc, m, (B, L), packed, tape
+        ctx.enc, ctx.mask, ctx.BL, ctx.packed, ctx.tape, ctx.drop = enc, m, (B, L), packed, tape, drop
         ctx.dtypes = [p.dtype for p in params]
         return x
 
@@ -339,7 +406,8 @@ class _TailFn(torch.autograd.Function):
     def backward(ctx, g):
         from . import opseq
         enc, m, (B, L), c = ctx.enc, ctx.mask, ctx.BL, ctx.enc.compute_dtype
-        needs = ctx.needs_input_grad[7:]
+        needs = ctx.needs_input_grad[8:]
+        drop, first = ctx.drop
         lib, f32 = _lib.load(), int(c == "fp32")
         dt = ops._act_dtype(c)
         ex = opseq.Exec(c)
@@ -365,12 +433,14 @@ class _TailFn(torch.autograd.Function):
             p = ctx.packed[li]
             x, qkv, cx, y, x1, h, gh, y2 = ctx.tape.pop()
             sums = lambda a, b: needs[16 * li + a] or needs[16 * li + b]      # noqa: E731
-            ds2, grads[16 * li + _LN2_W], grads[16 * li + _LN2_B] = _ln_bwd(enc, g, g2, y2, x1, p["g2"], sums(_LN2_W, _LN2_B))
+            ds2, dy2, grads[16 * li + _LN2_W], grads[16 * li + _LN2_B] = _ln_bwd(enc, g, g2, y2, x1, p["g2"], sums(_LN2_W, _LN2_B), drop,
+                                                                                 site(first + li, _OUT))
             del g, g2, y2
-            dw(li, _O2_W, _O2_B, ds2, gh, H, I)
+            dw(li, _O2_W, _O2_B, dy2, gh, H, I)
             del gh
             dh = torch.empty(M, I, dtype=dt, device=dev)
-            ex.dx(ds2, H, p["wo2"], dh, I, M)
+            ex.dx(dy2, H, p["wo2"], dh, I, M)
+            del dy2
             ga = _lib.BertGeluBwdArgs()
             ga.x, ga.g, ga.dx, ga.M, ga.N, ga.ld_x, ga.ld_g, ga.ld_dx = h.data_ptr(), dh.data_ptr(), dh.data_ptr(), M, I, I, I, I
             ga.act_f32, ga.stream = f32, ex.s
@@ -380,17 +450,24 @@ class _TailFn(torch.autograd.Function):
             dx1 = torch.empty(M, H, dtype=dt, device=dev)
             ex.dx(dh, I, p["wi"], dx1, H, M)
             del dh
-            ds1, grads[16 * li + _LN1_W], grads[16 * li + _LN1_B] = _ln_bwd(enc, dx1, ds2, y, x, p["g1"], sums(_LN1_W, _LN1_B))
+            ds1, dy1, grads[16 * li + _LN1_W], grads[16 * li + _LN1_B] = _ln_bwd(enc, dx1, ds2, y, x, p["g1"], sums(_LN1_W, _LN1_B), drop,
+                                                                                 site(first + li, _SELF_OUT))
             del dx1, ds2, y, x1
-            dw(li, _O_W, _O_B, ds1, cx, H, H)
+            dw(li, _O_W, _O_B, dy1, cx, H, H)
             dctx = torch.empty(M, H, dtype=dt, device=dev)
-            ex.dx(ds1, H, p["wo"], dctx, H, M)
+            ex.dx(dy1, H, p["wo"], dctx, H, M)
+            del dy1
             dqkv = torch.empty(M, 3 * H, dtype=dt, device=dev)
-            ab = _lib.BertAttnBwdArgs()
+            attn_drop = drop is not None and enc.p_attn > 0
+            ab = _lib.BertAttnDropBwdArgs() if attn_drop else _lib.BertAttnBwdArgs()
             ab.qkv, ab.mask, ab.dctx, ab.dqkv = qkv.data_ptr(), m.data_ptr(), dctx.data_ptr(), dqkv.data_ptr()
             ab.workspace, ab.workspace_bytes = ws.data_ptr(), ws_bytes
             ab.B, ab.L, ab.H, ab.ld_qkv, ab.ld_dctx, ab.ld_dqkv, ab.act_f32, ab.stream = B, L, H, 3 * H, H, 3 * H, f32, ex.s
-            _lib.check(lib.mmdeer_bert_attn_bwd(C.byref(ab)))
+            if attn_drop:
+                ab.site, ab.dropout_p, (ab.seed, ab.offset) = site(first + li, _ATTN), enc.p_attn, drop
+                _lib.check(lib.mmdeer_bert_attn_drop_bwd(C.byref(ab)))
+            else:
+                _lib.check(lib.mmdeer_bert_attn_bwd(C.byref(ab)))
             del dctx, cx, qkv
             if any(needs[16 * li + i] for i in (_Q_W, _Q_B, _K_W, _K_B, _V_W, _V_B)):
                 gw, gb = torch.empty(3 * H, H, device=dev), torch.empty(3 * H, device=dev)
@@ -405,4 +482,4 @@ class _TailFn(torch.autograd.Function):
             del dqkv, ds1
         ctx.tape.clear()
         out = [gr.to(d) if gr is not None and need else None for gr, d, need in zip(grads, ctx.dtypes, needs)]
-        return (None, None, None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, None, None, *out)

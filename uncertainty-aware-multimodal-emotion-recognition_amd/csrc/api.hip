@@ -13,6 +13,7 @@
 #include "../../include/mmdeer_frames_bwd.h"
 #include "../../include/mmdeer_bert.h"
 #include "../../include/mmdeer_bert_bwd.h"
+#include "../../include/mmdeer_bert_drop.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -571,6 +572,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(bn2d_bwd_args) SZ(conv2d_wgrad_args) SZ(conv2d_dgrad_args)   // mmdeer_frames_bwd.h
   SZ(bert_embed_args) SZ(bert_attn_args) SZ(bert_add_ln_args) SZ(bert_gelu_args)   // mmdeer_bert.h
   SZ(bert_attn_bwd_args) SZ(bert_add_ln_bwd_args) SZ(bert_gelu_bwd_args)   // mmdeer_bert_bwd.h
+  SZ(bert_embed_drop_args) SZ(bert_attn_drop_args) SZ(bert_drop_add_ln_args) SZ(bert_attn_drop_bwd_args) SZ(bert_drop_add_ln_bwd_args)   // mmdeer_bert_drop.h
 #undef SZ
   return -1;
 }

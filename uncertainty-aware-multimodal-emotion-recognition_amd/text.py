@@ -180,8 +180,9 @@ class TemporalTextEncoder(nn.Module):
     ``last_hidden_state`` as it comes, fp32 or bf16; everything behind the trunk trains as without it.  A frozen trunk
     (``finetune_layers == 0``) runs under ``no_grad``, as does any trunk while grad is disabled.  A trunk built with
     ``finetune_layers=k`` is called with grad when grad is enabled: the gradient of the embeddings that ``forward_embeddings``
-    produces flows on into the trunk's last ``k`` layers (the reference fine-tunes layers 6-11 of 12: k = 6).  The trunk has no
-    dropout in either mode, where the reference's BERT trains with 0.1."""
+    produces flows on into the trunk's last ``k`` layers (the reference fine-tunes layers 6-11 of 12: k = 6).  The trunk follows
+    this module's ``train()`` / ``eval()``: built with ``dropout=True`` (the reference's training configuration: hidden and attention
+    dropout 0.1 in every layer) its dropout is live in ``train()``, with a seed and step counter of its own; by default it has none."""
 
     def __init__(self, config: Optional[Dict] = None, compute_dtype: str = "fp32", bert: Optional[BertEncoder] = None):
         super().__init__()
