@@ -199,15 +199,47 @@ class BertEncoder(nn.Module):
                 m.bias.zero_()
 
     # ---------------------------------------------------------------------------------------------------------------------
+    def _operands_key(self):
+        """what the packed operands were built from: the compute dtype and every parameter's (_version, data_ptr), per layer"""
+        stamp = lambda m: tuple((p._version, p.data_ptr()) for p in m.parameters())                        # noqa: E731
+        return (ops._act_dtype(self.compute_dtype), stamp(self.embeddings), tuple(stamp(lyr) for lyr in self.encoder.layer))
+
+    def operand_mirrors(self):
+        """{parameter: the view of the packed operands that holds it} for every trainable parameter of the tail (the operands are
+        built first if need be): rows of ``wqkv`` for query / key / value, slices of ``bqkv``, and ``wo``, ``bo``, ``g1``, ... whole.  An
+        optimiser that stores each updated parameter into its view too (``optim.ModuleAdamW``: the compute dtype's rounding is
+        ``.to(dtype)``'s) and then calls ``operands_current()`` spares the rebuild after its step.  The views are those of the operands
+        as they are NOW: a rebuild (a parameter changed by anything else) makes new ones."""
+        packed, H = self._operands(), self.hidden_size
+        out = {}
+        for lyr, w in zip(self.encoder.layer, packed["layers"]):
+            s, so = getattr(lyr.attention, "self"), lyr.attention.output
+            pairs = [(lin.weight, w["wqkv"][j * H:(j + 1) * H]) for j, lin in enumerate((s.query, s.key, s.value))]
+            pairs += [(lin.bias, w["bqkv"][j * H:(j + 1) * H]) for j, lin in enumerate((s.query, s.key, s.value))]
+            pairs += [(so.dense.weight, w["wo"]), (so.dense.bias, w["bo"]), (so.LayerNorm.weight, w["g1"]), (so.LayerNorm.bias, w["b1"]),
+                      (lyr.intermediate.dense.weight, w["wi"]), (lyr.intermediate.dense.bias, w["bi"]), (lyr.output.dense.weight, w["wo2"]),
+                      (lyr.output.dense.bias, w["bo2"]), (lyr.output.LayerNorm.weight, w["g2"]), (lyr.output.LayerNorm.bias, w["b2"])]
+            out.update({p: t for p, t in pairs if p.requires_grad})
+        return out
+
+    def operands_current(self) -> None:
+        """Restamp the fine-tuned tail's packed operands from its parameters as they are: the caller has written every parameter it
+        changed into ``operand_mirrors()``'s views, so the next ``_operands()`` returns the same object without rebuilding.  Without
+        built operands nothing happens."""
+        if self._packed is not None:
+            dt, emb, layers = self._packed_key
+            first = len(self.encoder.layer) - self.finetune_layers          # only the tail can have been trained: the other stamps stay,
+            stamp = lambda m: tuple((p._version, p.data_ptr()) for p in m.parameters())      # noqa: E731  (and still catch a change from elsewhere)
+            self._packed_key = (dt, emb, layers[:first] + tuple(stamp(lyr) for lyr in self.encoder.layer[first:]))
+
     def _operands(self):
         """The packed operands: the [3H, H] QKV weight and its bias, compute-dtype copies of the matrices, fp32 vectors.  Built once and
         rebuilt when a parameter changed: the key is every parameter's (_version, data_ptr), which an in-place update
         (load_state_dict, an optimiser step) and a replaced storage (.to(), .data = ...) both move.  The key is kept per layer and
         for the embeddings, so a step on the tail repacks the tail's layers only: the returned dict is a new object whenever
         anything changed, and holds the SAME entry for every layer (and the embeddings) that did not."""
-        dt = ops._act_dtype(self.compute_dtype)
-        stamp = lambda m: tuple((p._version, p.data_ptr()) for p in m.parameters())                        # noqa: E731
-        key = (dt, stamp(self.embeddings), tuple(stamp(lyr) for lyr in self.encoder.layer))
+        key = self._operands_key()
+        dt = key[0]
         if self._packed is not None and key == self._packed_key:
             return self._packed
         same = self._packed is not None and self._packed_key[0] == dt

@@ -14,6 +14,7 @@
 #include "../../include/mmdeer_bert.h"
 #include "../../include/mmdeer_bert_bwd.h"
 #include "../../include/mmdeer_bert_drop.h"
+#include "../../include/mmdeer_optim.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -573,6 +574,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(bert_embed_args) SZ(bert_attn_args) SZ(bert_add_ln_args) SZ(bert_gelu_args)   // mmdeer_bert.h
   SZ(bert_attn_bwd_args) SZ(bert_add_ln_bwd_args) SZ(bert_gelu_bwd_args)   // mmdeer_bert_bwd.h
   SZ(bert_embed_drop_args) SZ(bert_attn_drop_args) SZ(bert_drop_add_ln_args) SZ(bert_attn_drop_bwd_args) SZ(bert_drop_add_ln_bwd_args)   // mmdeer_bert_drop.h
+  SZ(adamw_multi_tensor) SZ(adamw_multi_class) SZ(adamw_multi_args)   // mmdeer_optim.h
 #undef SZ
   return -1;
 }

@@ -25,6 +25,24 @@ struct AdamTable {
   float beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, max_norm, grad_scale;
 };
 
+// ---- the element update, stated once for every optimiser kernel (optim.hip, optim_multi.hip)
+struct AdamCoef { float gs, b1, b2, eps, wd, ibc1, isbc2; };
+
+// torch.optim.AdamW (decoupled decay): p *= 1 - lr*wd; m, v EMAs; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// (no contraction: torch applies these as separate operations, and the element-wise and the tile form of the update must agree bit for bit)
+__device__ __forceinline__ void adamw_update4(f32x4& p, f32x4 g, f32x4& m, f32x4& v, float lr, const AdamCoef& k) {
+#pragma clang fp contract(off)
+  g = g * k.gs;
+  p *= 1.f - lr * k.wd;
+  m = m * k.b1 + g * (1.f - k.b1);
+  v = v * k.b2 + g * g * (1.f - k.b2);
+  const float step = lr * k.ibc1;
+  p.x -= step * m.x / (sqrtf(v.x) * k.isbc2 + k.eps);
+  p.y -= step * m.y / (sqrtf(v.y) * k.isbc2 + k.eps);
+  p.z -= step * m.z / (sqrtf(v.z) * k.isbc2 + k.eps);
+  p.w -= step * m.w / (sqrtf(v.w) * k.isbc2 + k.eps);
+}
+
 // ---- matrices whose derived bf16 images are written by the update itself (bf16 mode): the update of such a matrix runs tile by tile
 // (64 x 64), the updated tile is rounded to bf16 once, kept in LDS and stored in every layout the forward / backward kernels read --
 // row-major (the packed copy), fragment-major images of W and W^T (chain.h), W^T row-major, head-major rows (tri_fused.hip), a

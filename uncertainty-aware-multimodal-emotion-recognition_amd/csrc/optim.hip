@@ -42,23 +42,6 @@ __global__ __launch_bounds__(256) void sumsq_segments_kernel(const AdamTable t) 
   if (threadIdx.x == 0) T.partials[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
 }
 
-struct AdamCoef { float gs, b1, b2, eps, wd, ibc1, isbc2; };
-
-// torch.optim.AdamW (decoupled decay): p *= 1 - lr*wd; m, v EMAs; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-// (no contraction: torch applies these as separate operations, and the element-wise and the tile form of the update must agree bit for bit)
-__device__ __forceinline__ void adamw_update4(f32x4& p, f32x4 g, f32x4& m, f32x4& v, float lr, const AdamCoef& k) {
-#pragma clang fp contract(off)
-  g = g * k.gs;
-  p *= 1.f - lr * k.wd;
-  m = m * k.b1 + g * (1.f - k.b1);
-  v = v * k.b2 + g * g * (1.f - k.b2);
-  const float step = lr * k.ibc1;
-  p.x -= step * m.x / (sqrtf(v.x) * k.isbc2 + k.eps);
-  p.y -= step * m.y / (sqrtf(v.y) * k.isbc2 + k.eps);
-  p.z -= step * m.z / (sqrtf(v.z) * k.isbc2 + k.eps);
-  p.w -= step * m.w / (sqrtf(v.w) * k.isbc2 + k.eps);
-}
-
 // The tile path of the fused update (optim.h: AdamImaged): one workgroup per 64 x 64 tile of an imaged matrix.
 template <typename TT, typename TI>      // (references into the kernel-argument segment: constant address space)
 __device__ __forceinline__ void adamw_tile(const TT& T, const TI& IM, int tile, const AdamCoef& k, bf16_t* wdst) {

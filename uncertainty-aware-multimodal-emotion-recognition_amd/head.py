@@ -256,7 +256,8 @@ class ComposedDEER(nn.Module):
     ``alpha``, ``beta`` (B, D), ``mu``, ``predictions``, ``uncertainties``, ``total_uncertainty``) and the fusion's extras.  The
     way to a trainable model at another geometry, e.g. ``ComposedDEER(HierarchicalMultimodalFusion(40, 128, 300),
     MultiDimensionalDEER(512))``.  ``compute_loss`` is ``losses.MultiTaskDEERLoss`` unless ``loss`` is given; there is no flat
-    gradient buffer, so ``DEERTrainer`` trains it through autograd + ``torch.optim.AdamW``."""
+    gradient buffer, so ``DEERTrainer`` trains it through autograd + ``torch.optim.AdamW``, or with
+    ``TrainingConfig(module_optimizer=True)`` + ``optim.ModuleAdamW`` (clip + AdamW as one device-side step)."""
 
     def __init__(self, fusion: nn.Module, head: MultiDimensionalDEER, loss: Optional[nn.Module] = None):
         super().__init__()

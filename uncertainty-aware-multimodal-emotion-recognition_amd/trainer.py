@@ -20,7 +20,7 @@ import torch
 
 from .metrics import StreamingMetrics, validation_metrics
 from .model import MultimodalDEER
-from .optim import FlatAdamW, FusedAdamW
+from .optim import FlatAdamW, FusedAdamW, ModuleAdamW
 
 
 @dataclass
@@ -32,6 +32,7 @@ class TrainingConfig:
     num_epochs: int = 100
     scheduler_type: str = "cosine"
     fused_optimizer: bool = True   # clip + AdamW + weight pack on the device (optim.FusedAdamW); False: torch.optim.AdamW
+    module_optimizer: bool = False # models that train through autograd, on a GPU: clip + AdamW as one device-side step (optim.ModuleAdamW) instead of clip_grad_norm_ + torch.optim.AdamW
     use_graph: bool = False        # replay train_step (Stack B: train_step_fused) as a captured HIP graph for full batches of one shape (needs fused_optimizer)
     warmup_epochs: int = 5
     patience: int = 10
@@ -108,6 +109,10 @@ class DEERTrainer:
             # clip_grad_norm_ + AdamW + weight pack as one device-side step (optim.FusedAdamW)
             return FusedAdamW(self.model, groups, lr=lr, weight_decay=self.config.weight_decay, eps=1e-8,
                               max_grad_norm=self.config.gradient_clip)
+        if self.generic and self.config.module_optimizer and self.device.type == "cuda":
+            # the same three groups; gradient_clip runs inside the step (train_epoch skips its clip_grad_norm_)
+            return ModuleAdamW.for_module(self.model, groups, lr=lr, weight_decay=self.config.weight_decay, eps=1e-8,
+                                          max_grad_norm=self.config.gradient_clip)
         return torch.optim.AdamW(groups, weight_decay=self.config.weight_decay, eps=1e-8)
 
     def _create_scheduler(self):
@@ -194,8 +199,11 @@ class DEERTrainer:
                     self.optimizer.zero_grad(set_to_none=True)
                     ld = self.model.compute_loss(self.model(a, v, t), y)
                     (ld["total_loss"] * w).backward()                       # weighted_loss.backward() (:211-216)
-                    norms.append(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.config.gradient_clip))
-                    self.optimizer.step()
+                    if isinstance(self.optimizer, ModuleAdamW):
+                        norms.append(self.optimizer.step())                 # the clip is inside the step; returns the pre-clip norm
+                    else:
+                        norms.append(torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.config.gradient_clip))
+                        self.optimizer.step()
                     bs = a.shape[0]
                     sums += torch.stack([ld[k].detach().double() for k in keys]) * bs
                     total += bs
