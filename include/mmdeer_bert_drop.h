@@ -16,7 +16,11 @@
  *   attention site                      row = (b * heads + h) * L + i (the query), col = j (the key)
  * The caller chooses the site ids; mmdeer/bert.py uses MMDEER_BERT_DROP_SITE_EMBED for the embeddings and
  * MMDEER_BERT_DROP_SITE_LAYER0 + 4 * layer + {0: attention, 1: self-output, 2: output}, a block above every other site id of the
- * package (all below 200). */
+ * package (all below 200).
+ *
+ * THE DEVICE COUNTER.  include/mmdeer_graph.h declares a twin mmdeer_<entry>_dev(args, offset_dev) of each entry, which adds a
+ * device-resident counter to `offset` when the kernel runs (HIP-graph replays).  The entries here are its NULL-counter case: the same
+ * kernels, in which every wave forms key(seed, offset, site) once, in scalar registers, before its first element. */
 #ifndef MMDEER_BERT_DROP_H_
 #define MMDEER_BERT_DROP_H_
 

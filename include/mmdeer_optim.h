@@ -45,7 +45,10 @@
  * smaller than mmdeer_adamw_multi_table_bytes or not 16-byte aligned, ntensors < 0, nclasses outside 1 .. MAX_CLASSES, a class with
  * step < 1, a non-finite or non-positive lr, a negative or non-finite weight_decay; eps non-finite or <= 0, a beta outside [0, 1),
  * a non-finite grad_scale or max_grad_norm; per tensor a NULL or misaligned param / grad, a misaligned mirror, count < 0, a class
- * index out of range, a moment range [moment_off, moment_off + count) that passes moment_elems or overlaps another tensor's. */
+ * index out of range, a moment range [moment_off, moment_off + count) that passes moment_elems or overlaps another tensor's.
+ *
+ * THE CAPTURABLE STEP.  include/mmdeer_graph.h declares mmdeer_adamw_multi_dev: the same step with the classes' lr, weight decay and
+ * step COUNT in device memory and a table upload made of launches alone, for a stream capture. */
 #ifndef MMDEER_OPTIM_H_
 #define MMDEER_OPTIM_H_
 

@@ -98,6 +98,12 @@ _OPTIM_NAMES = {"mmdeer_adamw_multi_tensor": "AdamWMultiTensor", "mmdeer_adamw_m
 OPTIM_CONSTANTS, _OPTIM_CLASSES, OPTIM_SYMBOLS = _header.parse(_header.read(_header.OPTIM_HEADER_PATH), _OPTIM_NAMES, {})
 globals().update({cls.__name__: cls for cls in _OPTIM_CLASSES.values()})    # AdamWMultiTensor, AdamWMultiClass, AdamWMultiArgs
 OPTIM_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _OPTIM_CLASSES.items()}
+# include/mmdeer_graph.h, the companion header of the device step counters (the _dev twins of the dropout entries, the capturable
+# optimiser step): tables of its own again; the older headers' structs it takes by reference are opaque there (c_void_p: pass byref)
+_GRAPH_NAMES = {"mmdeer_adamw_multi_class_dev": "AdamWMultiClassDev", "mmdeer_adamw_multi_dev_args": "AdamWMultiDevArgs"}
+GRAPH_CONSTANTS, _GRAPH_CLASSES, GRAPH_SYMBOLS = _header.parse(_header.read(_header.GRAPH_HEADER_PATH), _GRAPH_NAMES, {})
+globals().update({cls.__name__: cls for cls in _GRAPH_CLASSES.values()})    # AdamWMultiClassDev, AdamWMultiDevArgs
+GRAPH_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _GRAPH_CLASSES.items()}
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -112,7 +118,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS + GRAPH_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -146,7 +152,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         lib = bind(C.CDLL(path), require_all=True)
         if lib.mmdeer_abi_version() != ABI_VERSION:
             raise RuntimeError("libmmdeer_hip.so ABI version mismatch")
-        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS, **BERT_BWD_STRUCTS, **BERT_DROP_STRUCTS, **OPTIM_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
+        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS, **BERT_BWD_STRUCTS, **BERT_DROP_STRUCTS, **OPTIM_STRUCTS, **GRAPH_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
             if lib.mmdeer_sizeof(cname.encode()) != C.sizeof(cls):
                 raise RuntimeError(f"mmdeer: ctypes layout of mmdeer_{cname} ({C.sizeof(cls)} bytes) differs from the library's "
                                    f"({lib.mmdeer_sizeof(cname.encode())})")

@@ -61,8 +61,14 @@ goes on by the residual branch, and ``mmdeer_bert_attn_drop_bwd``): no extra lau
 and y2 are kept pre-dropout) and no mask is stored -- the library's counter hash regenerates it from (``dropout_seed``, step, site,
 row, column), with one site id per (layer, place) from a block that no other module uses (``SITE_EMBED``, ``site(layer, place)``).  A
 site whose probability is 0 runs its plain entry.  ``_train_step`` advances by one per forward in which dropout is live; the backward
-of a forward uses that forward's step; two runs of the same step store the same bits.  Not built: a captured graph replays the step
-it captured, because the step is a host value of each launch (feeding these entries a device-resident counter is a later change).
+of a forward uses that forward's step; two runs of the same step store the same bits.
+
+A CAPTURED GRAPH replays the kernel arguments it recorded, so the host's step would freeze.  ``set_step_counter(t)``, ``t`` a one-element
+int64 tensor on the module's device, moves the step onto the device: live forward number k = 0, 1, ... since ``take_step_count()``
+last returned passes offset = k and the counter's address to the ``_dev`` twins of the five entries (include/mmdeer_bert_drop.h), which
+hash step = k + *t, read when the kernel runs; the backward of a forward uses the same pair.  Whoever owns the graph adds
+``take_step_count()`` to ``t`` at the end of the captured region (``mmdeer.train_graph.capture_train_step`` does), so that each replay
+draws the masks of the next step.  ``set_step_counter(None)`` returns to the host counter; without a counter nothing changes.
 
 One deviation from ``BertModel`` in the forward: a sample whose mask has no valid token gets zeros from every attention layer where
 the reference averages V uniformly (include/mmdeer_bert.h), and, mirrored in the backward, zeros in all of its dqkv; everything
@@ -136,6 +142,7 @@ class BertEncoder(nn.Module):
         if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, int) or not 0 <= dropout_seed < 2 ** 64:
             raise ValueError(f"BertEncoder: dropout_seed must be an integer in 0 .. 2^64 - 1 (got {dropout_seed!r})")
         self.dropout, self.dropout_seed, self._train_step = dropout, dropout_seed, 0       # counter-hash dropout: seed + one tick per training forward
+        self._step_counter, self._counter_k = None, 0                                      # ... or a device counter + the live forwards since it was read
         self.p_hidden = self.p_attn = 0.0
         if dropout:
             for key in ("hidden_dropout_prob", "attention_probs_dropout_prob"):
@@ -267,25 +274,46 @@ class BertEncoder(nn.Module):
         return packed
 
     def _add_ln(self, y, x, gamma, beta, out, drop=None, site_id=-1):
-        """out = LayerNorm(y + x), or LayerNorm(drop(y) + x) with ``drop`` = (seed, step) where the hidden probability is not 0"""
+        """out = LayerNorm(y + x), or LayerNorm(drop(y) + x) with ``drop`` = (seed, step[, counter]) where the hidden probability is not 0"""
         live = drop is not None and self.p_hidden > 0
         a = _lib.BertDropAddLnArgs() if live else _lib.BertAddLnArgs()
         a.y, a.x, a.gamma, a.beta, a.out, a.eps = y.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), self.eps
         a.M, a.N, a.ld_y, a.ld_x, a.ld_out = y.shape[0], y.shape[1], y.stride(0), x.stride(0), out.stride(0)
         a.act_f32, a.stream = int(self.compute_dtype == "fp32"), _lib.current_stream()
         if live:
-            a.site, a.dropout_p, (a.seed, a.offset) = site_id, self.p_hidden, drop
-            _lib.check(_lib.load().mmdeer_bert_drop_add_ln_fwd(C.byref(a)))
+            a.site, a.dropout_p = site_id, self.p_hidden
+            _drop_call("mmdeer_bert_drop_add_ln_fwd", a, drop)
         else:
             _lib.check(_lib.load().mmdeer_bert_add_ln_fwd(C.byref(a)))
 
     def _drop(self):
-        """(seed, step) of this forward where dropout is live, else None; the counter advances by one per live forward"""
+        """(seed, step) of this forward where dropout is live -- (seed, step, device counter) with a device counter set --, else None;
+        the host counter, or with a device counter the count of live forwards since it was read, advances by one per live forward"""
         if self.dropout and self.training and (self.p_hidden > 0 or self.p_attn > 0):
+            if self._step_counter is not None:
+                d = (int(self.dropout_seed), self._counter_k, self._step_counter)
+                self._counter_k += 1
+                return d
             d = (int(self.dropout_seed), self._train_step)
             self._train_step += 1
             return d
         return None
+
+    def set_step_counter(self, t: Optional[torch.Tensor]) -> None:
+        """Take the dropout step from the device: ``t`` is a one-element int64 tensor on this module's device (the module docstring
+        has the arithmetic), or None to return to the host counter."""
+        if t is not None:
+            dev = self.embeddings.word_embeddings.weight.device
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != 1 or t.device != dev:
+                raise ValueError(f"set_step_counter: expected a one-element int64 tensor on {dev}, got "
+                                 f"{(t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        self._step_counter, self._counter_k = t, 0
+
+    def take_step_count(self) -> int:
+        """How many live forwards ran since the last call (or since the counter was set); the count restarts at 0.  The owner of a
+        captured graph adds it to the counter."""
+        k, self._counter_k = self._counter_k, 0
+        return k
 
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, token_type_ids: Optional[torch.Tensor] = None,
                 output_hidden_states: bool = False) -> BertEncoderOutput:
@@ -339,8 +367,8 @@ class BertEncoder(nn.Module):
             a.B, a.L, a.H, a.ld_x, a.act_f32, a.stream = B, L, H, H, f32, stream
             a.V, a.P, a.T = self.config["vocab_size"], self.config["max_position_embeddings"], self.config["type_vocab_size"]
             if embed_drop:
-                a.site, a.dropout_p, (a.seed, a.offset) = SITE_EMBED, self.p_hidden, drop
-                _lib.check(lib.mmdeer_bert_embed_drop_fwd(C.byref(a)))
+                a.site, a.dropout_p = SITE_EMBED, self.p_hidden
+                _drop_call("mmdeer_bert_embed_drop_fwd", a, drop)
             else:
                 _lib.check(lib.mmdeer_bert_embed_fwd(C.byref(a)))
             states = [x.clone()] if output_hidden_states else None
@@ -358,10 +386,22 @@ class BertEncoder(nn.Module):
         return BertEncoderOutput(shaped(out), tuple(shaped(s) for s in states) if output_hidden_states else None)
 
 
+def _drop_call(entry: str, a, drop) -> None:
+    """Dropout entry ``entry`` of the library on ``a`` with ``drop`` = (seed, step): the plain entry at the host's step; or
+    (seed, step[, counter]), ``counter`` a one-element int64 device tensor: its ``_dev`` twin, which adds the counter to the step on the
+    device."""
+    lib = _lib.load()
+    a.seed, a.offset = drop[0], drop[1]
+    if len(drop) < 3:
+        _lib.check(getattr(lib, entry)(C.byref(a)))
+    else:
+        _lib.check(getattr(lib, entry + "_dev")(C.byref(a), drop[2].data_ptr()))
+
+
 def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out, drop=None, layer=0):
     """One BertLayer's forward on the caller's buffers: the eight launches of the module docstring.  ``p``: the layer's packed
     operands.  Buffers may alias as the frozen path's do (x1 = y, gh = h, y2 = out = x): each is written after its last reader.
-    ``drop``: (seed, step) where dropout is live: layer ``layer``'s three sites then run their drop entries, in the same launches."""
+    ``drop``: (seed, step[, counter]) where dropout is live: layer ``layer``'s three sites then run their drop entries, in the same launches."""
     lib, c, stream = _lib.load(), enc.compute_dtype, _lib.current_stream()
     f32, (M, H), I = int(c == "fp32"), x.shape, h.shape[1]
     ops.linear_into(x, p["wqkv"], p["bqkv"], qkv, compute=c)
@@ -370,8 +410,8 @@ def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out, drop=None, l
     at.qkv, at.mask, at.ctx = qkv.data_ptr(), m.data_ptr(), ctx.data_ptr()
     at.B, at.L, at.H, at.ld_qkv, at.ld_ctx, at.act_f32, at.stream = B, L, H, 3 * H, H, f32, stream
     if attn_drop:
-        at.site, at.dropout_p, (at.seed, at.offset) = site(layer, _ATTN), enc.p_attn, drop
-        _lib.check(lib.mmdeer_bert_attn_drop_fwd(C.byref(at)))
+        at.site, at.dropout_p = site(layer, _ATTN), enc.p_attn
+        _drop_call("mmdeer_bert_attn_drop_fwd", at, drop)
     else:
         _lib.check(lib.mmdeer_bert_attn_fwd(C.byref(at)))
     ops.linear_into(ctx, p["wo"], p["bo"], y, compute=c)
@@ -386,7 +426,7 @@ def _layer_fwd(enc, x, p, m, B, L, qkv, ctx, y, x1, h, gh, y2, out, drop=None, l
 
 def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool, drop=None, site_id=-1):
     """mmdeer_bert_add_ln_bwd -> (ds, dy, dgamma, dbeta); the sums only when wanted.  ds is the gradient of x and dy that of y: one
-    tensor, unless ``drop`` = (seed, step) makes it mmdeer_bert_drop_add_ln_bwd, whose dy = ds o m."""
+    tensor, unless ``drop`` = (seed, step[, counter]) makes it mmdeer_bert_drop_add_ln_bwd, whose dy = ds o m."""
     lib, (M, N) = _lib.load(), y.shape
     live = drop is not None and enc.p_hidden > 0
     ds = torch.empty_like(y)
@@ -402,8 +442,8 @@ def _ln_bwd(enc, g, g2, y, x, gamma, want_sums: bool, drop=None, site_id=-1):
     a.M, a.N, a.ld_y, a.ld_x, a.ld_g, a.ld_g2, a.ld_ds = M, N, y.stride(0), x.stride(0), g.stride(0), g2.stride(0) if g2 is not None else 0, N
     a.act_f32, a.stream = int(enc.compute_dtype == "fp32"), _lib.current_stream()
     if live:
-        a.dy, a.ld_dy, a.site, a.dropout_p, (a.seed, a.offset) = dy.data_ptr(), N, site_id, enc.p_hidden, drop
-        _lib.check(lib.mmdeer_bert_drop_add_ln_bwd(C.byref(a)))
+        a.dy, a.ld_dy, a.site, a.dropout_p = dy.data_ptr(), N, site_id, enc.p_hidden
+        _drop_call("mmdeer_bert_drop_add_ln_bwd", a, drop)
     else:
         _lib.check(lib.mmdeer_bert_add_ln_bwd(C.byref(a)))
     return ds, dy, dgamma, dbeta
@@ -415,7 +455,7 @@ _Q_W, _Q_B, _K_W, _K_B, _V_W, _V_B, _O_W, _O_B, _LN1_W, _LN1_B, _I_W, _I_B, _O2_
 
 class _TailFn(torch.autograd.Function):
     """The fine-tuned tail as one autograd node (the module docstring has both launch plans).  ``packed``: the tail layers' packed
-    operands; ``states``: the caller's list of hidden-state copies, or None; ``drop``: ((seed, step) or None, the index of the
+    operands; ``states``: the caller's list of hidden-state copies, or None; ``drop``: ((seed, step[, counter]) or None, the index of the
     tail's first layer): the backward regenerates this forward's masks from it, whatever forwards ran in between."""
 
     @staticmethod
@@ -496,8 +536,8 @@ class _TailFn(torch.autograd.Function):
             ab.workspace, ab.workspace_bytes = ws.data_ptr(), ws_bytes
             ab.B, ab.L, ab.H, ab.ld_qkv, ab.ld_dctx, ab.ld_dqkv, ab.act_f32, ab.stream = B, L, H, 3 * H, H, 3 * H, f32, ex.s
             if attn_drop:
-                ab.site, ab.dropout_p, (ab.seed, ab.offset) = site(first + li, _ATTN), enc.p_attn, drop
-                _lib.check(lib.mmdeer_bert_attn_drop_bwd(C.byref(ab)))
+                ab.site, ab.dropout_p = site(first + li, _ATTN), enc.p_attn
+                _drop_call("mmdeer_bert_attn_drop_bwd", ab, drop)
             else:
                 _lib.check(lib.mmdeer_bert_attn_bwd(C.byref(ab)))
             del dctx, cx, qkv

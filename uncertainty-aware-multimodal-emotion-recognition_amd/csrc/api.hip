@@ -15,6 +15,7 @@
 #include "../../include/mmdeer_bert_bwd.h"
 #include "../../include/mmdeer_bert_drop.h"
 #include "../../include/mmdeer_optim.h"
+#include "../../include/mmdeer_graph.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -575,6 +576,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(bert_attn_bwd_args) SZ(bert_add_ln_bwd_args) SZ(bert_gelu_bwd_args)   // mmdeer_bert_bwd.h
   SZ(bert_embed_drop_args) SZ(bert_attn_drop_args) SZ(bert_drop_add_ln_args) SZ(bert_attn_drop_bwd_args) SZ(bert_drop_add_ln_bwd_args)   // mmdeer_bert_drop.h
   SZ(adamw_multi_tensor) SZ(adamw_multi_class) SZ(adamw_multi_args)   // mmdeer_optim.h
+  SZ(adamw_multi_class_dev) SZ(adamw_multi_dev_args)   // mmdeer_graph.h
 #undef SZ
   return -1;
 }

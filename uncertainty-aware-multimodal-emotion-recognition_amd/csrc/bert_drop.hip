@@ -11,7 +11,13 @@
 //                    the column term is the per-lane scalar.
 // Attention applies keep alone to the operands and the factor 1 / (1 - p) in fp32 to the accumulators (the header has the algebra):
 // the softmax sum l and the log-sum-exp are those of the undropped probabilities.
+//
+// The key is formed ON THE DEVICE, once per wave before its first element: every kernel takes the DropCtx and the site and calls
+// common.h's drop_key, whose operands are kernel arguments and -- where the context carries offset_dev -- one 64-bit word behind a
+// uniform pointer: a scalar load and four mix32 in scalar registers.  The plain entries are the NULL-counter case of the same kernels.
+// No kernel of this file writes the counter.
 #include "../../include/mmdeer_bert_drop.h"
+#include "../../include/mmdeer_graph.h"
 
 #include "../../include/mmdeer_bert_bwd.h"
 #include "bert_dev.h"
@@ -72,7 +78,8 @@ __device__ __forceinline__ void ln_load_drop(f32x4 (&v)[4], const void* y, long 
 }
 
 template <bool F32>
-__global__ __launch_bounds__(256) void bert_embed_drop_kernel(mmdeer_bert_embed_drop_args a, long long rows, DropCtx dc, unsigned key) {
+__global__ __launch_bounds__(256) void bert_embed_drop_kernel(mmdeer_bert_embed_drop_args a, long long rows, DropCtx dc) {
+  const unsigned key = drop_key(dc, a.site);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nq = a.H >> 2;
   for (long long r = (long long)blockIdx.x * 4 + w; r < rows; r += (long long)gridDim.x * 4) {
     const long long raw = a.ids[r], traw = a.type_ids ? a.type_ids[r] : 0;
@@ -92,7 +99,8 @@ __global__ __launch_bounds__(256) void bert_embed_drop_kernel(mmdeer_bert_embed_
 }
 
 template <bool F32>
-__global__ __launch_bounds__(256) void bert_drop_add_ln_kernel(mmdeer_bert_drop_add_ln_args a, DropCtx dc, unsigned key) {
+__global__ __launch_bounds__(256) void bert_drop_add_ln_kernel(mmdeer_bert_drop_add_ln_args a, DropCtx dc) {
+  const unsigned key = drop_key(dc, a.site);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (long long r = (long long)blockIdx.x * 4 + w; r < a.M; r += (long long)gridDim.x * 4) {
     f32x4 v[4];
@@ -105,7 +113,9 @@ __global__ __launch_bounds__(256) void bert_drop_add_ln_kernel(mmdeer_bert_drop_
 // bert.hip's bert_attn_bf16_kernel with the keep decision on the operand of the second product.  grid, threads and LDS are its.
 __global__ __launch_bounds__(128) void bert_attn_drop_bf16_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                                                                   bf16_t* __restrict__ ctx, int L, int H, int ld_qkv, int ld_ctx, int nqt,
-                                                                  unsigned key, unsigned thresh, float scale) {
+                                                                  DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[AT_K * ROW_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Vt[BERT_HD * KT_LD];
   __shared__ __attribute__((aligned(16))) unsigned char vb[AT_K];
@@ -184,8 +194,9 @@ __global__ __launch_bounds__(128) void bert_attn_drop_bf16_kernel(const bf16_t* 
 
 // ------------------------------------------------------------------------------------------------ attention forward, fp32
 __global__ __launch_bounds__(64) void bert_attn_drop_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ mask, float* __restrict__ ctx,
-                                                                int L, int H, int ld_qkv, int ld_ctx, int nqt, unsigned key, unsigned thresh,
-                                                                float scale) {
+                                                                int L, int H, int ld_qkv, int ld_ctx, int nqt, DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) float Kf[AT_F * BERT_HD];
   __shared__ __attribute__((aligned(16))) float Vf[AT_F * BERT_HD];
   __shared__ float mk[AT_F];
@@ -238,8 +249,9 @@ __global__ __launch_bounds__(64) void bert_attn_drop_f32_kernel(const float* __r
 __global__ __launch_bounds__(128) void bert_attn_drop_dq_bf16_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                                                                      const bf16_t* __restrict__ dctx, bf16_t* __restrict__ dqkv,
                                                                      float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx,
-                                                                     int ld_dqkv, int nqt, long long nstat, unsigned key, unsigned thresh,
-                                                                     float scale) {
+                                                                     int ld_dqkv, int nqt, long long nstat, DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[AT_K * ROW_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Vs[AT_K * ROW_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Kt[BERT_HD * KT_LD];
@@ -345,8 +357,9 @@ __global__ __launch_bounds__(128) void bert_attn_drop_dq_bf16_kernel(const bf16_
 __global__ __launch_bounds__(128) void bert_attn_drop_dkdv_bf16_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                                                                        const bf16_t* __restrict__ dctx, bf16_t* __restrict__ dqkv,
                                                                        const float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx,
-                                                                       int ld_dqkv, int nkt, long long nstat, unsigned key, unsigned thresh,
-                                                                       float scale) {
+                                                                       int ld_dqkv, int nkt, long long nstat, DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) bf16_t Qs[AT_Q * ROW_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Os[AT_Q * ROW_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Qt[BERT_HD * QT_LD];
@@ -434,7 +447,9 @@ __global__ __launch_bounds__(128) void bert_attn_drop_dkdv_bf16_kernel(const bf1
 __global__ __launch_bounds__(64) void bert_attn_drop_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ mask,
                                                                    const float* __restrict__ dctx, float* __restrict__ dqkv,
                                                                    float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx, int ld_dqkv,
-                                                                   int nqt, long long nstat, unsigned key, unsigned thresh, float scale) {
+                                                                   int nqt, long long nstat, DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) float Kf[AT_F * BERT_HD];
   __shared__ __attribute__((aligned(16))) float Vf[AT_F * BERT_HD];
   __shared__ __attribute__((aligned(16))) float Df[AT_OWN * DF_LD];      // thread t's dO row at t * DF_LD: read by its owner alone
@@ -514,8 +529,9 @@ __global__ __launch_bounds__(64) void bert_attn_drop_dq_f32_kernel(const float* 
 __global__ __launch_bounds__(64) void bert_attn_drop_dkdv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ mask,
                                                                      const float* __restrict__ dctx, float* __restrict__ dqkv,
                                                                      const float* __restrict__ ws, int L, int H, int ld_qkv, int ld_dctx,
-                                                                     int ld_dqkv, int nkt, long long nstat, unsigned key, unsigned thresh,
-                                                                     float scale) {
+                                                                     int ld_dqkv, int nkt, long long nstat, DropCtx dc, int site) {
+  const unsigned key = drop_key(dc, site), thresh = dc.thresh;
+  const float scale = dc.scale;
   __shared__ __attribute__((aligned(16))) float Qf[AT_F * BERT_HD];
   __shared__ __attribute__((aligned(16))) float Of[AT_F * BERT_HD];
   __shared__ float lse_s[AT_F];
@@ -585,7 +601,8 @@ __global__ __launch_bounds__(64) void bert_attn_drop_dkdv_f32_kernel(const float
 // bert_bwd.hip's bert_add_ln_bwd_kernel on s = drop(y) + x, with the second store dy = ds o m; the partial sums and
 // bert_ln_fold_kernel's fixed order are restated here because that kernel is local to its file.
 template <bool F32>
-__global__ __launch_bounds__(256) void bert_drop_add_ln_bwd_kernel(mmdeer_bert_drop_add_ln_bwd_args a, int sums, DropCtx dc, unsigned key) {
+__global__ __launch_bounds__(256) void bert_drop_add_ln_bwd_kernel(mmdeer_bert_drop_add_ln_bwd_args a, int sums, DropCtx dc) {
+  const unsigned key = drop_key(dc, a.site);
   __shared__ __attribute__((aligned(16))) float part[3][2 * MMDEER_BERT_MAX_HIDDEN];      // waves 1 .. 3: [dgamma | dbeta]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nq = a.N >> 2;
   const float inv_n = 1.0f / (float)a.N;
@@ -693,6 +710,11 @@ int drop_check(const char* op, float p, int site) {
   MMDEER_CHECK(site >= 0, "%s: site must be >= 0 (got %d)", op, site);
   return 0;
 }
+// ... and a device counter that a 64-bit load cannot take (the host never dereferences it)
+int counter_check(const char* op, const uint64_t* offset_dev) {
+  MMDEER_CHECK(((uintptr_t)offset_dev & 7) == 0, "%s: offset_dev must be 8-byte aligned", op);
+  return 0;
+}
 
 }  // namespace
 }  // namespace mmdeer
@@ -701,9 +723,12 @@ using namespace mmdeer;
 
 extern "C" {
 
-int mmdeer_bert_embed_drop_fwd(const mmdeer_bert_embed_drop_args* a) {
+int mmdeer_bert_embed_drop_fwd(const mmdeer_bert_embed_drop_args* a) { return mmdeer_bert_embed_drop_fwd_dev(a, nullptr); }
+
+int mmdeer_bert_embed_drop_fwd_dev(const mmdeer_bert_embed_drop_args* a, const uint64_t* offset_dev) {
   MMDEER_CHECK(a, "bert_embed_drop_fwd: NULL args");
   TRY(drop_check("bert_embed_drop_fwd", a->dropout_p, a->site));
+  TRY(counter_check("bert_embed_drop_fwd", offset_dev));
   if (a->dropout_p == 0.f) {
     mmdeer_bert_embed_args p{a->ids, a->type_ids, a->word, a->pos, a->type, a->gamma, a->beta, a->x, a->eps,
                              a->B,   a->L,        a->H,    a->V,   a->P,    a->T,     a->ld_x, a->act_f32, a->stream};
@@ -723,14 +748,17 @@ int mmdeer_bert_embed_drop_fwd(const mmdeer_bert_embed_drop_args* a) {
   MMDEER_CHECK(al8(a->ids) && al8(a->type_ids) && al16(a->word) && al16(a->pos) && al16(a->type) && al16(a->gamma) && al16(a->beta) &&
                    al_act4(a->act_f32, {a->x}),
                "bert_embed_drop_fwd: misaligned pointer (ids 8 bytes; tables, gamma, beta 16 bytes; x 4 act elements)");
-  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset);
-  MMDEER_LAUNCH_ACT(bert_embed_drop_kernel, a->act_f32, dim3(row_grid(rows)), dim3(256), (hipStream_t)a->stream, *a, rows, dc, drop_key(dc, a->site));
+  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset, offset_dev);
+  MMDEER_LAUNCH_ACT(bert_embed_drop_kernel, a->act_f32, dim3(row_grid(rows)), dim3(256), (hipStream_t)a->stream, *a, rows, dc);
   return 0;
 }
 
-int mmdeer_bert_attn_drop_fwd(const mmdeer_bert_attn_drop_args* a) {
+int mmdeer_bert_attn_drop_fwd(const mmdeer_bert_attn_drop_args* a) { return mmdeer_bert_attn_drop_fwd_dev(a, nullptr); }
+
+int mmdeer_bert_attn_drop_fwd_dev(const mmdeer_bert_attn_drop_args* a, const uint64_t* offset_dev) {
   MMDEER_CHECK(a, "bert_attn_drop_fwd: NULL args");
   TRY(drop_check("bert_attn_drop_fwd", a->dropout_p, a->site));
+  TRY(counter_check("bert_attn_drop_fwd", offset_dev));
   if (a->dropout_p == 0.f) {
     mmdeer_bert_attn_args p{a->qkv, a->mask, a->ctx, a->B, a->L, a->H, a->ld_qkv, a->ld_ctx, a->act_f32, a->stream};
     return mmdeer_bert_attn_fwd(&p);
@@ -746,21 +774,23 @@ int mmdeer_bert_attn_drop_fwd(const mmdeer_bert_attn_drop_args* a) {
                "bert_attn_drop_fwd: misaligned pointer (qkv 16 bytes, mask 4 bytes, ctx 4 act elements)");
   const int nqt = (a->L + AT_OWN - 1) / AT_OWN;
   const unsigned grid = (unsigned)((long long)a->B * (a->H / BERT_HD) * nqt);     // < 2^31 / 192
-  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset);
-  const unsigned key = drop_key(dc, a->site);
+  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset, offset_dev);
   if (a->act_f32)
     hipLaunchKernelGGL(bert_attn_drop_f32_kernel, dim3(grid), dim3(64), 0, (hipStream_t)a->stream, (const float*)a->qkv, a->mask, (float*)a->ctx,
-                       a->L, a->H, a->ld_qkv, a->ld_ctx, nqt, key, dc.thresh, dc.scale);
+                       a->L, a->H, a->ld_qkv, a->ld_ctx, nqt, dc, a->site);
   else
     hipLaunchKernelGGL(bert_attn_drop_bf16_kernel, dim3(grid), dim3(128), 0, (hipStream_t)a->stream, (const bf16_t*)a->qkv, a->mask,
-                       (bf16_t*)a->ctx, a->L, a->H, a->ld_qkv, a->ld_ctx, nqt, key, dc.thresh, dc.scale);
+                       (bf16_t*)a->ctx, a->L, a->H, a->ld_qkv, a->ld_ctx, nqt, dc, a->site);
   MMDEER_HIP(hipGetLastError());
   return 0;
 }
 
-int mmdeer_bert_drop_add_ln_fwd(const mmdeer_bert_drop_add_ln_args* a) {
+int mmdeer_bert_drop_add_ln_fwd(const mmdeer_bert_drop_add_ln_args* a) { return mmdeer_bert_drop_add_ln_fwd_dev(a, nullptr); }
+
+int mmdeer_bert_drop_add_ln_fwd_dev(const mmdeer_bert_drop_add_ln_args* a, const uint64_t* offset_dev) {
   MMDEER_CHECK(a, "bert_drop_add_ln_fwd: NULL args");
   TRY(drop_check("bert_drop_add_ln_fwd", a->dropout_p, a->site));
+  TRY(counter_check("bert_drop_add_ln_fwd", offset_dev));
   if (a->dropout_p == 0.f) {
     mmdeer_bert_add_ln_args p{a->y, a->x, a->gamma, a->beta, a->out, a->eps, a->M, a->N, a->ld_y, a->ld_x, a->ld_out, a->act_f32, a->stream};
     return mmdeer_bert_add_ln_fwd(&p);
@@ -776,16 +806,19 @@ int mmdeer_bert_drop_add_ln_fwd(const mmdeer_bert_drop_add_ln_args* a) {
   MMDEER_CHECK(a->y && a->gamma && a->beta && a->out, "bert_drop_add_ln_fwd: NULL pointer (y, gamma, beta, out)");
   MMDEER_CHECK(al16(a->gamma) && al16(a->beta) && al_act4(a->act_f32, {a->y, a->x, a->out}),
                "bert_drop_add_ln_fwd: misaligned pointer (gamma, beta 16 bytes; y, x, out 4 act elements)");
-  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset);
-  MMDEER_LAUNCH_ACT(bert_drop_add_ln_kernel, a->act_f32, dim3(row_grid(a->M)), dim3(256), (hipStream_t)a->stream, *a, dc, drop_key(dc, a->site));
+  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset, offset_dev);
+  MMDEER_LAUNCH_ACT(bert_drop_add_ln_kernel, a->act_f32, dim3(row_grid(a->M)), dim3(256), (hipStream_t)a->stream, *a, dc);
   return 0;
 }
 
 long long mmdeer_bert_attn_drop_bwd_workspace(int32_t B, int32_t L, int32_t H) { return mmdeer_bert_attn_bwd_workspace(B, L, H); }
 
-int mmdeer_bert_attn_drop_bwd(const mmdeer_bert_attn_drop_bwd_args* a) {
+int mmdeer_bert_attn_drop_bwd(const mmdeer_bert_attn_drop_bwd_args* a) { return mmdeer_bert_attn_drop_bwd_dev(a, nullptr); }
+
+int mmdeer_bert_attn_drop_bwd_dev(const mmdeer_bert_attn_drop_bwd_args* a, const uint64_t* offset_dev) {
   MMDEER_CHECK(a, "bert_attn_drop_bwd: NULL args");
   TRY(drop_check("bert_attn_drop_bwd", a->dropout_p, a->site));
+  TRY(counter_check("bert_attn_drop_bwd", offset_dev));
   if (a->dropout_p == 0.f) {
     mmdeer_bert_attn_bwd_args p{a->qkv, a->mask, a->dctx, a->dqkv, a->workspace, a->workspace_bytes, a->B, a->L, a->H, a->ld_qkv, a->ld_dctx,
                                 a->ld_dqkv, a->act_f32, a->stream};
@@ -808,22 +841,19 @@ int mmdeer_bert_attn_drop_bwd(const mmdeer_bert_attn_drop_bwd_args* a) {
   const long long nstat = (long long)a->B * heads * a->L;
   const unsigned grid = (unsigned)((long long)a->B * heads * nt);       // < 2^31 / 192
   hipStream_t st = (hipStream_t)a->stream;
-  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset);
-  const unsigned key = drop_key(dc, a->site);
+  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset, offset_dev);
   if (a->act_f32) {
     hipLaunchKernelGGL(bert_attn_drop_dq_f32_kernel, dim3(grid), dim3(64), 0, st, (const float*)a->qkv, a->mask, (const float*)a->dctx,
-                       (float*)a->dqkv, a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, key, dc.thresh, dc.scale);
+                       (float*)a->dqkv, a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, dc, a->site);
     MMDEER_HIP(hipGetLastError());
     hipLaunchKernelGGL(bert_attn_drop_dkdv_f32_kernel, dim3(grid), dim3(64), 0, st, (const float*)a->qkv, a->mask, (const float*)a->dctx,
-                       (float*)a->dqkv, (const float*)a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, key, dc.thresh,
-                       dc.scale);
+                       (float*)a->dqkv, (const float*)a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, dc, a->site);
   } else {
     hipLaunchKernelGGL(bert_attn_drop_dq_bf16_kernel, dim3(grid), dim3(128), 0, st, (const bf16_t*)a->qkv, a->mask, (const bf16_t*)a->dctx,
-                       (bf16_t*)a->dqkv, a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, key, dc.thresh, dc.scale);
+                       (bf16_t*)a->dqkv, a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, dc, a->site);
     MMDEER_HIP(hipGetLastError());
     hipLaunchKernelGGL(bert_attn_drop_dkdv_bf16_kernel, dim3(grid), dim3(128), 0, st, (const bf16_t*)a->qkv, a->mask, (const bf16_t*)a->dctx,
-                       (bf16_t*)a->dqkv, (const float*)a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, key, dc.thresh,
-                       dc.scale);
+                       (bf16_t*)a->dqkv, (const float*)a->workspace, a->L, a->H, a->ld_qkv, a->ld_dctx, a->ld_dqkv, nt, nstat, dc, a->site);
   }
   MMDEER_HIP(hipGetLastError());
   return 0;
@@ -831,9 +861,12 @@ int mmdeer_bert_attn_drop_bwd(const mmdeer_bert_attn_drop_bwd_args* a) {
 
 long long mmdeer_bert_drop_add_ln_bwd_scratch(int32_t M, int32_t N) { return mmdeer_bert_add_ln_bwd_scratch(M, N); }
 
-int mmdeer_bert_drop_add_ln_bwd(const mmdeer_bert_drop_add_ln_bwd_args* a) {
+int mmdeer_bert_drop_add_ln_bwd(const mmdeer_bert_drop_add_ln_bwd_args* a) { return mmdeer_bert_drop_add_ln_bwd_dev(a, nullptr); }
+
+int mmdeer_bert_drop_add_ln_bwd_dev(const mmdeer_bert_drop_add_ln_bwd_args* a, const uint64_t* offset_dev) {
   MMDEER_CHECK(a, "bert_drop_add_ln_bwd: NULL args");
   TRY(drop_check("bert_drop_add_ln_bwd", a->dropout_p, a->site));
+  TRY(counter_check("bert_drop_add_ln_bwd", offset_dev));
   MMDEER_CHECK(ln_n_ok(a->N), "bert_drop_add_ln_bwd: unsupported N = %d (a multiple of 4, 4 .. %d)", a->N, MMDEER_BERT_MAX_HIDDEN);
   MMDEER_CHECK(a->M >= 0, "bert_drop_add_ln_bwd: bad shape (M %d)", a->M);
   auto ld4_ok = [&](int ld) { return ld_ok(ld, a->N, 4); };
@@ -863,8 +896,8 @@ int mmdeer_bert_drop_add_ln_bwd(const mmdeer_bert_drop_add_ln_bwd_args* a) {
     return mmdeer_bert_add_ln_bwd(&p);
   }
   const unsigned grid = sums ? (unsigned)ln_blocks(a->M) : row_grid(a->M);
-  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset);
-  MMDEER_LAUNCH_ACT(bert_drop_add_ln_bwd_kernel, a->act_f32, dim3(grid), dim3(256), (hipStream_t)a->stream, *a, sums, dc, drop_key(dc, a->site));
+  const DropCtx dc = make_drop(a->dropout_p, a->seed, a->offset, offset_dev);
+  MMDEER_LAUNCH_ACT(bert_drop_add_ln_bwd_kernel, a->act_f32, dim3(grid), dim3(256), (hipStream_t)a->stream, *a, sums, dc);
   if (sums) {
     hipLaunchKernelGGL(bert_drop_ln_fold_kernel, dim3((a->N / 2 + 15) / 16), dim3(256), 0, (hipStream_t)a->stream, (const float*)a->scratch,
                        a->dgamma, a->dbeta, a->N, (int)grid);

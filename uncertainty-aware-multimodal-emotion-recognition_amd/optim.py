@@ -218,6 +218,14 @@ _MAX_CLASSES = _lib.OPTIM_CONSTANTS["ADAMW_MULTI_MAX_CLASSES"]
 _SCRATCH = _lib.OPTIM_CONSTANTS["ADAMW_MULTI_SCRATCH"]
 
 
+def _capturing() -> bool:
+    """is the current stream being captured?  (without a device torch raises: nothing captures there)"""
+    try:
+        return bool(torch.cuda.is_current_stream_capturing())
+    except Exception:       # noqa: BLE001
+        return False
+
+
 class ModuleAdamW(torch.optim.Optimizer):
     """``clip_grad_norm_(params, max_grad_norm)`` + ``torch.optim.AdamW`` for ANY list of fp32 CUDA parameters that train through
     autograd into ordinary ``.grad`` tensors (the encoders, the DEER head modules, ``ComposedDEER``, the alternative fusions,
@@ -243,10 +251,23 @@ class ModuleAdamW(torch.optim.Optimizer):
     ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.AdamW``'s format (per parameter ``step``, ``exp_avg``, ``exp_avg_sq``, and
     ``param_groups`` with its keys): a checkpoint moves between the two optimisers in both directions.  The moments live in two flat
     buffers; ``state[p]['exp_avg']`` is a view of one.  ``table_uploads`` counts the uploads of the device-side tensor table: one at
-    the first step, one more whenever a gradient comes back at another address or another set of parameters has gradients."""
+    the first step, one more whenever a gradient comes back at another address or another set of parameters has gradients.
+
+    ``capturable=True`` makes ``step()`` one call of ``mmdeer_adamw_multi_dev``, which a stream capture can record (``torch.cuda.graph``,
+    ``mmdeer.train_graph.capture_train_step``): what a replay must see change lives on the device.  The classes are the GROUPS; each
+    has a 16-byte record (lr, weight_decay, steps done) in ``class_buffer``; the first launch adds 1 to the step counts and the second
+    forms the bias corrections from them, so every replay is the next step.  ``state[p]['step']`` is a device scalar, a view of its
+    group's count.  lr and weight_decay are read from the records: ``step()`` (and a replay, through ``refresh_hyper()``) rewrites them
+    with one small copy when ``param_groups`` moved -- outside a capture; inside one a change raises.  The table upload is made of
+    launches (no copy, no wait), so the first captured step, whose gradients sit at new addresses, uploads inside the graph.  Because
+    the step count is device data there is one count per group: the parameters of a group that take part must all have done the same
+    number of steps, and once the first step has run a step whose set of parameters with a gradient differs from the first step's
+    raises ``RuntimeError`` naming the parameter.  ``state_dict()`` reads the counts back (one small copy to the host) and stays
+    ``torch.optim.AdamW``'s format.  A NON-capturable ``step()`` inside a capture raises before any library call: its upload waits
+    for the stream and its step is a host value."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 max_grad_norm: float = 0.0, mirrors=None):
+                 max_grad_norm: float = 0.0, mirrors=None, capturable: bool = False):
         if not (lr > 0 and eps > 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and weight_decay >= 0):
             raise ValueError("ModuleAdamW: bad hyper-parameters")
         # torch.optim.AdamW's own group keys (amsgrad, maximize, foreach, ...) with its defaults: a state_dict loads into either
@@ -269,6 +290,13 @@ class ModuleAdamW(torch.optim.Optimizer):
         self._sig = self._records = self._classes = None
         self._owners = []                   # for_module: the submodules whose operand_mirrors() the mirrors came from
         self._owner_packed = []
+        self._module = None                 # for_module: the module itself (train_graph looks for step counters under it)
+        self._names = {}                    # for_module: id(parameter) -> its name, for messages
+        self.capturable = bool(capturable)
+        self._cls = None                    # capturable: (classes, 4) int32 on the device: lr bits, weight_decay bits, steps done, 0
+        self._cls_groups = None             # ... the group of each class
+        self._cls_hyper = None              # ... the host shadow [(lr, weight_decay)] of what the records hold
+        self._live0 = None                  # ... the parameters that had a gradient at the first step
         self.table_uploads = 0
         self.last_grad_norm: Optional[torch.Tensor] = None
 
@@ -302,7 +330,8 @@ class ModuleAdamW(torch.optim.Optimizer):
         for m in owners:
             mirrors.update({p: t for p, t in m.operand_mirrors().items() if id(p) in mine})
         opt = cls(groups, mirrors=mirrors, **kw)
-        opt._owners = owners
+        opt._owners, opt._module = owners, module
+        opt._names = {id(p): n for n, p in module.named_parameters()}
         opt._owner_packed = [m._operands() for m in owners]
         return opt
 
@@ -355,6 +384,11 @@ class ModuleAdamW(torch.optim.Optimizer):
     def step(self, closure=None, grad_scale: float = 1.0):
         if closure is not None:
             raise NotImplementedError("ModuleAdamW: closures are not supported")
+        if self.capturable:
+            return self._step_capturable(float(grad_scale))
+        if _capturing():
+            raise RuntimeError("ModuleAdamW.step() inside a stream capture: its step count is a host value and its table upload waits for "
+                               "the stream.  Build the optimiser with capturable=True")
         self._check_groups()
         # one pass over the parameters: who has a gradient, where it is, and the class (group, step count) of each, in order of first
         # appearance.  The full checks run only when something moved (below): an unchanged signature means the same tensors as before.
@@ -438,7 +472,188 @@ class ModuleAdamW(torch.optim.Optimizer):
         self.last_grad_norm = norm
         return norm
 
+    # ---- capturable=True ------------------------------------------------------------------------------------------------
+    def _name(self, i):
+        p = self._params[i]
+        return self._names.get(id(p), f"#{i} of shape {tuple(p.shape)}")
+
+    @property
+    def class_buffer(self) -> Optional[torch.Tensor]:
+        """capturable: the device records (classes, 4) int32 -- lr and weight_decay as float32 bits, the steps done, 0"""
+        return self._cls
+
+    def _hyper(self):
+        out = []
+        for gi in self._cls_groups:
+            g = self.param_groups[gi]
+            lr, wd = float(g["lr"]), float(g["weight_decay"])
+            if not (lr > 0 and lr != float("inf") and 0 <= wd != float("inf")):       # false for a NaN
+                raise ValueError(f"ModuleAdamW: group {gi}: lr must be finite and positive and weight_decay finite and >= 0 (got {lr}, {wd})")
+            out.append((lr, wd))
+        return out
+
+    def _sync_steps(self):
+        """the device step counts into the host's per-parameter shadow (one small copy; not inside a capture)"""
+        if self._cls is not None and self._live0 is not None:
+            done = self._cls[:, 2].cpu().tolist()
+            cls_of_group = {gi: c for c, gi in enumerate(self._cls_groups)}
+            for i in self._live0:
+                self._steps[i] = int(done[cls_of_group[self._group_of[i]]])
+
+    def refresh_hyper(self) -> None:
+        """capturable: rewrite the device records' lr and weight_decay if ``param_groups`` moved since they were written (an LR
+        scheduler stepped).  One small copy on the current stream; inside a capture a change raises instead."""
+        if self._cls is None:
+            return
+        hyper = self._hyper()
+        if hyper != self._cls_hyper:
+            if _capturing():
+                raise RuntimeError("ModuleAdamW(capturable=True): lr / weight_decay changed inside a stream capture; change param_groups "
+                                   "between replays")
+            self._cls.view(torch.float32)[:, :2].copy_(torch.tensor(hyper, dtype=torch.float32))
+            self._cls_hyper = hyper
+
+    def snapshot(self) -> Dict:
+        """capturable: the moments, the device step counts and which parameters have state, as they are now (``restore`` puts them
+        back in place: warm-up steps before a capture are then no training steps)"""
+        self._sync_steps()
+        clone = lambda t: None if t is None else t.clone()       # noqa: E731
+        return {"m": clone(self._m), "v": clone(self._v), "cls": clone(self._cls), "steps": list(self._steps),
+                "stateful": {id(p) for p in self._params if self.state.get(p)}}
+
+    def restore(self, snap: Dict) -> None:
+        """Write a ``snapshot()`` back IN PLACE (addresses stay: a captured graph keeps reading these buffers).  Buffers and records
+        that did not exist at the snapshot are zeroed (no moments, no steps done), and state entries made since are dropped."""
+        for mine, was in ((self._m, snap["m"]), (self._v, snap["v"])):
+            if mine is not None:
+                mine.copy_(was) if was is not None and was.shape == mine.shape else mine.zero_()
+        self._steps = list(snap["steps"])
+        if self._cls is not None:
+            if snap["cls"] is not None and snap["cls"].shape == self._cls.shape:
+                self._cls[:, 2].copy_(snap["cls"][:, 2])
+            else:
+                cls_of_group = {gi: c for c, gi in enumerate(self._cls_groups)}
+                done = [0] * len(self._cls_groups)
+                for i in self._live0 or ():
+                    done[cls_of_group[self._group_of[i]]] = self._steps[i]
+                self._cls[:, 2].copy_(torch.tensor(done, dtype=torch.int32))
+        for p in self._params:
+            if id(p) not in snap["stateful"]:
+                self.state.pop(p, None)
+
+    def _step_capturable(self, grad_scale: float):
+        self._check_groups()
+        live = [i for i, p in enumerate(self._params) if p.grad is not None]
+        if self._live0 is not None and tuple(live) != self._live0:
+            odd = sorted(set(live) ^ set(self._live0))[0]
+            raise RuntimeError(f"ModuleAdamW(capturable=True): parameter {self._name(odd)} "
+                               f"{'has' if odd in live else 'has no'} gradient, unlike at the first step: the step counts are device data, "
+                               "one per group, so the set of parameters that take part is fixed by the first step")
+        if not live:
+            dev = self._params[0].device if self._params else "cpu"
+            self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            return self.last_grad_norm
+        dev = self._params[live[0]].device
+        pptr, gptr = tuple(self._params[i].data_ptr() for i in live), tuple(self._params[i].grad.data_ptr() for i in live)
+        sig = (tuple(live), pptr, gptr)
+        upload = sig != self._sig
+        if upload:
+            for i in live:
+                p = self._params[i]
+                g = p.grad
+                if not p.is_cuda or p.dtype != torch.float32 or g.dtype != torch.float32 or p.device != dev or g.device != dev:
+                    raise RuntimeError("ModuleAdamW: parameters and gradients must be fp32 tensors on one CUDA device (there is no CPU path); "
+                                       f"got {p.dtype} on {p.device}, gradient {g.dtype} on {g.device}")
+                if not p.is_contiguous() or not g.is_contiguous() or g.numel() != p.numel():
+                    raise RuntimeError(f"ModuleAdamW: parameters and gradients must be contiguous (parameter {tuple(p.shape)}, strides "
+                                       f"{p.stride()}; gradient strides {g.stride()})")
+        self._buffers(dev)
+        for k, m in enumerate(self._owners):
+            if m._packed is not self._owner_packed[k]:
+                self._refresh_owner_mirrors()
+                upload = True
+                break
+        if self._live0 is None:
+            # the first step (or the first after load_state_dict): classes = the groups that take part, in order of first appearance
+            groups, done = [], []
+            for i in live:
+                gi = self._group_of[i]
+                if gi not in groups:
+                    groups.append(gi)
+                    done.append(self._steps[i])
+                elif self._steps[i] != done[groups.index(gi)]:
+                    raise RuntimeError(f"ModuleAdamW(capturable=True): parameter {self._name(i)} has done {self._steps[i]} steps and another "
+                                       f"of its group {done[groups.index(gi)]}: the step count is one device value per group")
+            if len(groups) > _MAX_CLASSES:
+                raise NotImplementedError(f"ModuleAdamW: {len(groups)} groups in one step; the kernels take {_MAX_CLASSES} classes")
+            if _capturing():
+                raise RuntimeError("ModuleAdamW(capturable=True): run one step before the capture (it builds the device records)")
+            self._cls_groups = groups
+            self._cls_hyper = self._hyper()
+            rec = torch.zeros(len(groups), 4, dtype=torch.int32)
+            rec.view(torch.float32)[:, :2] = torch.tensor(self._cls_hyper, dtype=torch.float32)
+            rec[:, 2] = torch.tensor(done, dtype=torch.int32)
+            self._cls = rec.to(dev)
+        else:
+            self.refresh_hyper()
+        lib = _lib.load()
+        if upload:
+            cls_of_group = {gi: c for c, gi in enumerate(self._cls_groups)}
+            rec = (_lib.AdamWMultiTensor * len(live))()
+            for r, i in zip(rec, live):
+                p, t = self._params[i], self._mirrors[i]
+                r.param, r.grad, r.count, r.moment_off, r.cls = p.data_ptr(), p.grad.data_ptr(), p.numel(), self._offs[i], cls_of_group[self._group_of[i]]
+                if t is not None:
+                    if t.device != dev:
+                        raise RuntimeError("ModuleAdamW: a mirror is not on its parameter's device")
+                    r.mirror, r.mirror_f32 = t.data_ptr(), int(t.dtype == torch.float32)
+            need = lib.mmdeer_adamw_multi_table_bytes(rec, len(live))
+            if need < 0:
+                _lib.check(-1)
+            if self._table is None or self._table.device != dev or self._table.numel() < need:
+                self._table = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            self._records = rec
+        a = _lib.AdamWMultiDevArgs()
+        a.tensors = C.cast(self._records, C.c_void_p)     # (an opaque type in mmdeer_graph.h; self._records keeps the array alive)
+        a.ntensors, a.nclasses, a.classes = len(live), len(self._cls_groups), self._cls.data_ptr()
+        g0 = self.param_groups[0]
+        a.beta1, a.beta2, a.eps = float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"])
+        a.exp_avg, a.exp_avg_sq, a.moment_elems = self._m.data_ptr(), self._v.data_ptr(), self._m.numel()
+        a.table, a.table_bytes, a.upload = self._table.data_ptr(), self._table.numel(), int(upload)
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+        a.scratch, a.grad_norm = self._scratch.data_ptr(), norm.data_ptr()
+        a.max_grad_norm, a.grad_scale, a.stream = self.max_grad_norm, grad_scale, _lib.current_stream()
+        _lib.check(lib.mmdeer_adamw_multi_dev(C.byref(a)))
+        if upload:
+            self._sig = sig
+            self.table_uploads += 1
+        if self._live0 is None:
+            self._live0 = tuple(live)
+        cls_of_group = {gi: c for c, gi in enumerate(self._cls_groups)}
+        for i in live:
+            p = self._params[i]
+            st = self.state[p]
+            if "exp_avg" not in st:
+                st["exp_avg"], st["exp_avg_sq"] = self._views(i)
+            st["step"] = self._cls[cls_of_group[self._group_of[i]], 2]
+        torch.autograd.graph.increment_version([self._params[i] for i in live])
+        for m in self._owners:
+            m.operands_current()
+        self.last_grad_norm = norm
+        return norm
+
     def state_dict(self) -> Dict:
+        if self.capturable:
+            self._sync_steps()
+            sd = super().state_dict()
+            index = {}
+            for g in sd["param_groups"]:
+                for k in g["params"]:
+                    index[k] = len(index)
+            # torch.optim.AdamW's format: a float32 scalar per parameter (the live entries are views of the device records)
+            sd["state"] = {k: {**st, "step": torch.tensor(float(self._steps[index[k]]), dtype=torch.float32)} if "step" in st else st
+                           for k, st in sd["state"].items()}
+            return sd
         for i, p in enumerate(self._params):
             st = self.state.get(p)
             if st and "step" in st:
@@ -449,6 +664,7 @@ class ModuleAdamW(torch.optim.Optimizer):
         super().load_state_dict(state)
         self._check_groups()
         self._sig = None
+        self._live0 = self._cls = self._cls_groups = self._cls_hyper = None      # capturable: the next step rebuilds the device records
         for i, p in enumerate(self._params):
             st = self.state.get(p)
             if not st:

@@ -193,6 +193,7 @@ class TemporalTextEncoder(nn.Module):
         self.compute_dtype = compute_dtype
         ops._act_dtype(compute_dtype)
         self.dropout_seed, self._train_step = config.get("dropout_seed", 0), 0     # counter-hash dropout: seed + one tick per training forward
+        self._step_counter, self._counter_k = None, 0                              # ... or a device counter + the live forwards since it was read
         if self.hidden_dim % 32:
             raise NotImplementedError("hidden_dim must be a multiple of 32")
         if bert is not None and not isinstance(bert, BertEncoder):
@@ -225,10 +226,34 @@ class TemporalTextEncoder(nn.Module):
 
     def _drop(self):
         if self.training and self.dropout > 0:
+            if self._step_counter is not None:       # the step on the device: opseq.set_drop forwards the counter as offset_dev
+                d = (self.dropout, int(self.dropout_seed), self._counter_k, self._step_counter)
+                self._counter_k += 1
+                return d
             d = (self.dropout, int(self.dropout_seed), self._train_step)
             self._train_step += 1
             return d
         return None
+
+    def set_step_counter(self, t: Optional[torch.Tensor]) -> None:
+        """Take the dropout step from the device, for a captured graph: ``t`` is a one-element int64 tensor on this module's device,
+        or None to return to the host counter.  Live forward number k = 0, 1, ... since ``take_step_count()`` last returned hashes
+        step k + *t, read when the kernels run; the owner of the graph adds ``take_step_count()`` to ``t`` at the end of the captured
+        region (``mmdeer.train_graph.capture_train_step``).  A ``bert=`` trunk gets the same call; give it a counter of its own
+        afterwards where its step differs."""
+        if t is not None:
+            dev = self.token_attention[0].weight.device
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != 1 or t.device != dev:
+                raise ValueError(f"set_step_counter: expected a one-element int64 tensor on {dev}, got "
+                                 f"{(t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        self._step_counter, self._counter_k = t, 0
+        if self.bert is not None:
+            self.bert.set_step_counter(t)
+
+    def take_step_count(self) -> int:
+        """live forwards since the last call (or since the counter was set); restarts at 0"""
+        k, self._counter_k = self._counter_k, 0
+        return k
 
     def extract_linguistic_features(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         """(B, L) ids and mask -> (B, 10) fp32, the reference's features (encoders.py:648-699) from one launch."""
