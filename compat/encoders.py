@@ -6,12 +6,15 @@ with ``bert=BertEncoder(config)``, its BERT configuration: the trunk on HIP, fro
 layers trained as the reference trains layers 6-11 (mmdeer.bert; parameters named as transformers.BertModel's, so a checkpoint
 of the reference's ``self.bert`` loads; ``dropout=True`` runs the reference's hidden and attention dropout inside the trunk in train(), off by default; tokenisation and pretrained weights stay outside).  EnhancedVideoEncoder is
 the reference's encoder downstream of its spatial CNN, on (B, T, 512) per-frame features (mmdeer.video; frame tensors raise);
-FrameVideoEncoder is the same encoder from frames, its Conv2d backbone run on HIP, forward only (mmdeer.frames)."""
+FrameVideoEncoder is the same encoder from frames, its Conv2d backbone run on HIP, forward only (mmdeer.frames).  ModalityEncoder,
+create_encoders_from_config and get_encoder_output_dims are the reference's unified interface over the three (mmdeer.encoders: a
+refusal of an encoder propagates where the reference substitutes zeros)."""
 from mmdeer.side import EnhancedAudioEncoder  # noqa: F401
 from mmdeer.bert import BertEncoder  # noqa: F401
 from mmdeer.text import TemporalTextEncoder as EnhancedTextEncoder  # noqa: F401
 from mmdeer.video import TemporalVideoEncoder as EnhancedVideoEncoder  # noqa: F401
 from mmdeer.frames import FrameVideoEncoder  # noqa: F401
+from mmdeer.encoders import ModalityEncoder, create_encoders_from_config, get_encoder_output_dims  # noqa: F401
 
 
 def _out_of_scope(name):

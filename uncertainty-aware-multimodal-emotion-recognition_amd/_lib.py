@@ -104,6 +104,8 @@ _GRAPH_NAMES = {"mmdeer_adamw_multi_class_dev": "AdamWMultiClassDev", "mmdeer_ad
 GRAPH_CONSTANTS, _GRAPH_CLASSES, GRAPH_SYMBOLS = _header.parse(_header.read(_header.GRAPH_HEADER_PATH), _GRAPH_NAMES, {})
 globals().update({cls.__name__: cls for cls in _GRAPH_CLASSES.values()})    # AdamWMultiClassDev, AdamWMultiDevArgs
 GRAPH_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _GRAPH_CLASSES.items()}
+# include/mmdeer_drop_dev.h, the companion header of the same counter for mmdeer.h's three by-value dropout entries: symbols only
+DROP_DEV_CONSTANTS, _DROP_DEV_CLASSES, DROP_DEV_SYMBOLS = _header.parse(_header.read(_header.DROP_DEV_HEADER_PATH), {}, {})
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -118,7 +120,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS + GRAPH_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS + GRAPH_SYMBOLS + DROP_DEV_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args

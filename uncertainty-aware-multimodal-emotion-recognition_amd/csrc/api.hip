@@ -16,6 +16,7 @@
 #include "../../include/mmdeer_bert_drop.h"
 #include "../../include/mmdeer_optim.h"
 #include "../../include/mmdeer_graph.h"
+#include "../../include/mmdeer_drop_dev.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -377,19 +378,39 @@ int mmdeer_layernorm_bwd(const void* dout, const void* y, const float* mean, con
   return launch_reduce_partials(t, s);
 }
 
+// the device step counter of include/mmdeer_drop_dev.h: one 8-byte-aligned uint64_t that the host never dereferences
+static int counter_ok(const char* op, const uint64_t* offset_dev) {
+  MMDEER_CHECK(((uintptr_t)offset_dev & 7) == 0, "%s: offset_dev must be 8-byte aligned", op);
+  return 0;
+}
+
 int mmdeer_trimodal_attn_fwd(const void* qkv, void* obar, float* probs, float* attn_w, float* av_w, int B,
                              int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream) {
+  return mmdeer_trimodal_attn_fwd_dev(qkv, obar, probs, attn_w, av_w, B, act_f32, training, dropout_p, seed, offset, stream, nullptr);
+}
+int mmdeer_trimodal_attn_fwd_dev(const void* qkv, void* obar, float* probs, float* attn_w, float* av_w, int B,
+                                 int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream,
+                                 const uint64_t* offset_dev) {
   MMDEER_CHECK(B >= 0, "trimodal_attn_fwd: batch must be >= 0 (got %d)", B);
   MMDEER_CHECK(B == 0 || (qkv && obar && probs), "trimodal_attn_fwd: NULL pointer (qkv / obar / probs)");
-  const DropCtx dc = make_drop(dropout_p, seed, offset);
-  return launch_tri_attn_fwd(qkv, obar, probs, attn_w, av_w, B, act_f32, (training && dropout_p > 0.f) ? 1 : 0, dc, (hipStream_t)stream);
+  TRY(counter_ok("trimodal_attn_fwd", offset_dev));
+  const int train = (training && dropout_p > 0.f) ? 1 : 0;      // the kernel draws (and reads the counter) only when train
+  const DropCtx dc = make_drop(dropout_p, seed, offset, train ? offset_dev : nullptr);
+  return launch_tri_attn_fwd(qkv, obar, probs, attn_w, av_w, B, act_f32, train, dc, (hipStream_t)stream);
 }
 int mmdeer_trimodal_attn_bwd(const void* qkv, const void* dobar, const float* probs, void* dqkv, int B,
                              int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream) {
+  return mmdeer_trimodal_attn_bwd_dev(qkv, dobar, probs, dqkv, B, act_f32, training, dropout_p, seed, offset, stream, nullptr);
+}
+int mmdeer_trimodal_attn_bwd_dev(const void* qkv, const void* dobar, const float* probs, void* dqkv, int B,
+                                 int act_f32, int training, float dropout_p, uint64_t seed, uint64_t offset, void* stream,
+                                 const uint64_t* offset_dev) {
   MMDEER_CHECK(B >= 0, "trimodal_attn_bwd: batch must be >= 0 (got %d)", B);
   MMDEER_CHECK(B == 0 || (qkv && dobar && probs && dqkv), "trimodal_attn_bwd: NULL pointer (qkv / dobar / probs / dqkv)");
-  const DropCtx dc = make_drop(dropout_p, seed, offset);
-  return launch_tri_attn_bwd(qkv, dobar, probs, dqkv, B, act_f32, (training && dropout_p > 0.f) ? 1 : 0, dc, (hipStream_t)stream);
+  TRY(counter_ok("trimodal_attn_bwd", offset_dev));
+  const int train = (training && dropout_p > 0.f) ? 1 : 0;
+  const DropCtx dc = make_drop(dropout_p, seed, offset, train ? offset_dev : nullptr);
+  return launch_tri_attn_bwd(qkv, dobar, probs, dqkv, B, act_f32, train, dc, (hipStream_t)stream);
 }
 
 int mmdeer_pack_qkv_headmajor(const float* in_proj_weight, void* whm_bf16, void* stream) {
@@ -468,8 +489,13 @@ int mmdeer_nig_loss(const float* gamma, const float* nu, const float* alpha, con
 
 int mmdeer_dropout_mask(int site, int rows, int cols, float dropout_p, uint64_t seed, uint64_t offset,
                         unsigned char* out, void* stream) {
+  return mmdeer_dropout_mask_dev(site, rows, cols, dropout_p, seed, offset, out, stream, nullptr);
+}
+int mmdeer_dropout_mask_dev(int site, int rows, int cols, float dropout_p, uint64_t seed, uint64_t offset,
+                            unsigned char* out, void* stream, const uint64_t* offset_dev) {
   MMDEER_CHECK(out != nullptr, "dropout_mask: out is NULL");
-  const DropCtx dc = make_drop(dropout_p, seed, offset);
+  TRY(counter_ok("dropout_mask", offset_dev));
+  const DropCtx dc = make_drop(dropout_p, seed, offset, dropout_p > 0.f ? offset_dev : nullptr);     // no dropout: no step to read
   return launch_dropout_mask(dc, site, rows, cols, out, (hipStream_t)stream);
 }
 

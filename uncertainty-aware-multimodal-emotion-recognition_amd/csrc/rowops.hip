@@ -330,9 +330,10 @@ __global__ __launch_bounds__(256) void pad_cols_kernel(const PadTable t) {
 
 __global__ __launch_bounds__(256) void dropout_mask_kernel(DropCtx d, int site, int rows, int cols, unsigned char* out) {
   const long long total = (long long)rows * cols;
+  const unsigned key = drop_key(d, site);     // once per wave, before its first element: one read of the device step counter, if any
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
     const unsigned r = (unsigned)(e / cols), c = (unsigned)(e - (long long)r * cols);
-    out[e] = drop_keep(d, site, r, c) ? 1 : 0;
+    out[e] = drop_rand1(key, r, c) < d.thresh ? 1 : 0;
   }
 }
 

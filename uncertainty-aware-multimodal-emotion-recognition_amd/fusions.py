@@ -20,6 +20,7 @@ from torch import nn
 
 from . import _lib, ops
 from .opseq import Exec
+from .stepcount import DropOwner
 
 _SITE_ENC, _SITE_CONCAT = 96, 97
 
@@ -48,7 +49,8 @@ def _convert(ex: Exec, src: torch.Tensor, dt) -> torch.Tensor:
 
 class _Drop:
     """Dropout state of a module: seed + a counter that advances once per training forward (the masks are the library's counter
-    hash of (seed, step, site, row, column); the backward regenerates nothing -- ReLU outputs carry their own zeros)."""
+    hash of (seed, step, site, row, column); the backward regenerates nothing -- ReLU outputs carry their own zeros).  Its owner is a
+    ``stepcount.DropOwner``: ``step`` is the owner's host step, and with a device counter set on the owner the tuple carries it."""
 
     def __init__(self, seed: int = 0):
         self.seed, self.step = int(seed), 0
@@ -56,9 +58,7 @@ class _Drop:
     def next(self, module: nn.Module, p: float):
         if not module.training or p <= 0:
             return None
-        d = (p, self.seed, self.step)
-        self.step += 1
-        return d
+        return module._drop_step(p, self.seed)
 
 
 # ------------------------------------------------------------------------------------------------ autograd building blocks
@@ -311,7 +311,7 @@ class BilinearFusion(nn.Module):
         return linear(modality_features[0], self.linear, self.compute_dtype)
 
 
-class AdaptiveFusionGating(nn.Module):
+class AdaptiveFusionGating(nn.Module, DropOwner):
     """``fusion.AdaptiveFusionGating`` (src/models/fusion.py:421-501).  As in the reference, a strategy name missing from
     ``fusion_modules`` is skipped, an empty strategy list falls back to the concatenation Linear, and listing 'concatenation'
     raises ``TypeError`` (the reference hands that ``nn.Linear`` the tuple of modality tensors, :479)."""
@@ -357,7 +357,7 @@ class AdaptiveFusionGating(nn.Module):
         return {"fused_features": weighted, "strategy_weights": weights}
 
 
-class ConcatFusion(nn.Sequential):
+class ConcatFusion(nn.Sequential, DropOwner):
     """The concatenation fallback of ``create_fusion_module`` (src/models/fusion.py:584-592): an ``nn.Sequential`` of
     Linear, ReLU, Dropout, LayerNorm (same child indices, hence the same ``state_dict`` keys) whose forward is one GEMM + one
     LayerNorm launch."""

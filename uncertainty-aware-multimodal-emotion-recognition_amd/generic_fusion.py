@@ -26,6 +26,7 @@ from torch import nn
 from . import _lib
 from .fusions import _Drop, _LinActLnFn, _act, _convert, _dt, linear
 from .opseq import Exec
+from .stepcount import DropOwner, counter_ptr
 
 _SITE_AV, _SITE_AVF, _SITE_TRI_ATTN, _SITE_TRIF, _SITE_OUT = 81, 82, 83, 84, 85
 
@@ -86,8 +87,12 @@ class _TriAttnFn(torch.autograd.Function):
         probs = torch.empty(B, 8, 4, dtype=torch.float32, device=x.device)
         attn_w = torch.empty(B, 2, 2, dtype=torch.float32, device=x.device) if want_weights else None
         p, seed, step = (drop[0], drop[1], drop[2]) if drop else (0.0, 0, 0)
-        _lib.check(lib.mmdeer_trimodal_attn_fwd(x.data_ptr(), obar.data_ptr(), probs.data_ptr(), attn_w.data_ptr() if want_weights else None,
-                                                None, B, int(dt == torch.float32), int(bool(drop)), p, seed, step, s))
+        args = (x.data_ptr(), obar.data_ptr(), probs.data_ptr(), attn_w.data_ptr() if want_weights else None, None, B, int(dt == torch.float32),
+                int(bool(drop)), p, seed, step, s)
+        if counter_ptr(drop) is None:
+            _lib.check(lib.mmdeer_trimodal_attn_fwd(*args))
+        else:           # the step on the device (a captured graph): the same kernel, include/mmdeer_drop_dev.h
+            _lib.check(lib.mmdeer_trimodal_attn_fwd_dev(*args, counter_ptr(drop)))
         ctx.save_for_backward(x, probs)
         ctx.meta = (compute_dtype, drop, qkv.dtype)
         ctx.mark_non_differentiable(*( [attn_w] if want_weights else []))
@@ -103,8 +108,11 @@ class _TriAttnFn(torch.autograd.Function):
         ga = _convert(ex, g, dt)
         dqkv = torch.empty_like(x)
         p, seed, step = (drop[0], drop[1], drop[2]) if drop else (0.0, 0, 0)
-        _lib.check(ex.lib.mmdeer_trimodal_attn_bwd(x.data_ptr(), ga.data_ptr(), probs.data_ptr(), dqkv.data_ptr(), B, int(dt == torch.float32),
-                                                   int(bool(drop)), p, seed, step, ex.s))
+        args = (x.data_ptr(), ga.data_ptr(), probs.data_ptr(), dqkv.data_ptr(), B, int(dt == torch.float32), int(bool(drop)), p, seed, step, ex.s)
+        if counter_ptr(drop) is None:
+            _lib.check(ex.lib.mmdeer_trimodal_attn_bwd(*args))
+        else:
+            _lib.check(ex.lib.mmdeer_trimodal_attn_bwd_dev(*args, counter_ptr(drop)))
         return dqkv.to(xdt), None, None, None
 
 
@@ -116,7 +124,7 @@ def _lin_relu_drop_ln(d_in: int, d_out: int, p: float) -> nn.Sequential:
     return nn.Sequential(nn.Linear(d_in, d_out), nn.ReLU(), nn.Dropout(p), nn.LayerNorm(d_out))
 
 
-class GenericHierarchicalFusion(nn.Module):
+class GenericHierarchicalFusion(nn.Module, DropOwner):
     """See the module docstring.  ``forward(audio, video, text)`` returns the reference's output dictionary (fusion.py:164-171)."""
 
     def __init__(self, audio_dim: int, video_dim: int, text_dim: int, fusion_dim: int = 512, intermediate_dim: int = 256,
@@ -186,7 +194,7 @@ class GenericHierarchicalFusion(nn.Module):
         xtok = torch.stack([x0, x1], dim=1).reshape(2 * B, self.fusion_dim)       # row 2b + t
         tm = tri.modality_attention
         qkv = _LinearRaw.apply(xtok, tm.in_proj_weight, tm.in_proj_bias, cd)
-        tdrop = (drop[0], drop[1] + 7919, drop[2]) if drop else None
+        tdrop = (drop[0], drop[1] + 7919) + drop[2:] if drop else None       # (a device step counter rides along)
         obar, attn_w = _TriAttnFn.apply(qkv, cd, tdrop, True)
         pooled = linear(obar, tm.out_proj, cd)
         ff = tri.final_fusion
@@ -197,7 +205,11 @@ class GenericHierarchicalFusion(nn.Module):
         if drop:
             lib = _lib.load()
             keep = torch.empty(2 * B, H, dtype=torch.uint8, device=fused.device)
-            _lib.check(lib.mmdeer_dropout_mask(_SITE_AV, 2 * B, H, drop[0], drop[1], drop[2], keep.data_ptr(), _lib.current_stream()))
+            if counter_ptr(drop) is None:
+                _lib.check(lib.mmdeer_dropout_mask(_SITE_AV, 2 * B, H, drop[0], drop[1], drop[2], keep.data_ptr(), _lib.current_stream()))
+            else:
+                _lib.check(lib.mmdeer_dropout_mask_dev(_SITE_AV, 2 * B, H, drop[0], drop[1], drop[2], keep.data_ptr(), _lib.current_stream(),
+                                                       counter_ptr(drop)))
             w = keep.float().mean(dim=1, keepdim=True) / (1.0 - drop[0])
             a2v, v2a = w[:B], w[B:]
         else:

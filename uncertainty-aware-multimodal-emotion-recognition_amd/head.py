@@ -17,6 +17,7 @@ from torch import nn
 
 from . import _lib, fusions, ops
 from .opseq import Exec
+from .stepcount import DropOwner
 
 NIG_KEYS = ("mu", "nu", "alpha", "beta", "aleatoric_uncertainty", "epistemic_uncertainty", "uncertainty")
 DIM_NAMES = ("valence", "arousal", "dominance")
@@ -136,7 +137,7 @@ def _check_input(x: torch.Tensor, input_dim: int) -> None:
     ops._check_dev(x)
 
 
-class DEERLayer(nn.Module):
+class DEERLayer(nn.Module, DropOwner):
     """``deer.DEERLayer`` (reference src/models/deer.py:30-108): ``evidence_net`` = Linear(input_dim, hidden_dim), ReLU, Dropout,
     Linear(hidden_dim, hidden_dim // 2), ReLU, Dropout, Linear(hidden_dim // 2, 4 output_dim); Xavier-uniform weights and zero
     biases (drawn from a generator seeded with ``seed``).  ``forward(x[B, input_dim])`` -> the seven (B, output_dim) fp32 tensors of
@@ -183,7 +184,7 @@ class DEERLayer(nn.Module):
         return dict(zip(NIG_KEYS, outs))
 
 
-class MultiDimensionalDEER(nn.Module):
+class MultiDimensionalDEER(nn.Module, DropOwner):
     """``deer.MultiDimensionalDEER`` (reference src/models/deer.py:198-266): the shared ``feature_processor`` (two Linear-ReLU-
     Dropout layers, torch's default ``nn.Linear`` initialisation), one ``DEERLayer(hidden_dim, 1, hidden_dim // 2)`` per
     emotion dimension in ``deer_heads``, ``dimension_names``.  ``forward(x[B, input_dim])`` -> ``{dim}_{key}`` (B, 1) for the

@@ -708,6 +708,22 @@ class HierarchicalMultimodalFusion(nn.Module):
             self._generic.train(mode)
         return self
 
+    # the dropout step-counter protocol (stepcount.py) of the fusion that runs: the operator path's own; the default geometry's step
+    # belongs to MultimodalDEER, whose capture is MultimodalDEER.capture_train_step, so a device counter is refused there
+    @property
+    def _train_step(self) -> int:
+        return self._generic._train_step if self._generic is not None else self._core._step
+
+    def set_step_counter(self, t) -> None:
+        if self._generic is not None:
+            self._generic.set_step_counter(t)
+        elif t is not None:
+            raise NotImplementedError("HierarchicalMultimodalFusion at the default geometry runs MultimodalDEER's fused pass, which takes "
+                                      "its dropout step through MultimodalDEER.capture_train_step, not through set_step_counter")
+
+    def take_step_count(self) -> int:
+        return self._generic.take_step_count() if self._generic is not None else 0
+
     def forward(self, audio_features, video_features, text_features, uncertainties=None) -> Dict[str, torch.Tensor]:
         if self.use_uncertainty_weighting and uncertainties is not None:
             # Same failure as the reference: with `uncertainties` given and use_uncertainty_weighting=True its forward calls

@@ -19,6 +19,7 @@ from torch import nn
 
 from . import _lib, fusions, ops
 from .opseq import Exec
+from .stepcount import StepCounted, counter_ptr
 
 
 def _xavier_(module: nn.Module) -> None:
@@ -163,7 +164,10 @@ class _DropoutFn(torch.autograd.Function):
         ex = Exec(compute_dtype, drop)
         B, N = xa.shape
         keep = torch.empty(B, N, dtype=torch.uint8, device=xa.device)
-        _lib.check(ex.lib.mmdeer_dropout_mask(site, B, N, float(drop[0]), drop[1], drop[2], keep.data_ptr(), ex.s))
+        if counter_ptr(drop) is None:
+            _lib.check(ex.lib.mmdeer_dropout_mask(site, B, N, float(drop[0]), drop[1], drop[2], keep.data_ptr(), ex.s))
+        else:           # the step on the device (a captured graph): the same kernel, include/mmdeer_drop_dev.h
+            _lib.check(ex.lib.mmdeer_dropout_mask_dev(site, B, N, float(drop[0]), drop[1], drop[2], keep.data_ptr(), ex.s, counter_ptr(drop)))
         mask = keep.to(dt)
         out = ex.add(torch.empty_like(xa), xa, mask=mask, scale=ex.scale_of(drop[0]))
         ctx.save_for_backward(mask)
@@ -204,7 +208,7 @@ class ModalityEncoders(nn.Module):
         return enc(audio, self.audio_encoder), enc(video, self.video_encoder), enc(text, self.text_encoder)
 
 
-class EnhancedAudioEncoder(nn.Module):
+class EnhancedAudioEncoder(nn.Module, StepCounted):
     """Feature branch of ``encoders.EnhancedAudioEncoder`` (reference src/models/encoders.py:65-126, 356-389) in
     evaluation mode: (B, 84) or (B, 1, 84) pre-extracted features -> (B, 512).
 
@@ -257,8 +261,7 @@ class EnhancedAudioEncoder(nn.Module):
         H = self.hidden_dim // 2
         drop = None
         if self.training and self.dropout > 0:
-            drop = (self.dropout, int(self.dropout_seed), self._train_step)
-            self._train_step += 1
+            drop = self._drop_step(self.dropout, self.dropout_seed)
         h = x
         for layer in range(self.num_layers):
             P = lambda n: getattr(self.lstm, f"{n}_l{layer}")                      # noqa: E731

@@ -156,8 +156,7 @@ class TemporalAudioEncoder(side.EnhancedAudioEncoder):
         c = self.compute_dtype
         drop = None
         if self.training and self.dropout > 0:
-            drop = (self.dropout, int(self.dropout_seed), self._train_step)
-            self._train_step += 1
+            drop = self._drop_step(self.dropout, self.dropout_seed)
         h = x.transpose(0, 1).reshape(T * B, self.enhanced_features_dim)       # time-major rows t * B + b
         for layer in range(self.num_layers):
             h = lstm_layer(h, self.lstm, layer, T, B, c)

@@ -3,13 +3,15 @@
 ``capture_train_step(step_fn, optimizer, static_inputs)`` records ``loss = step_fn(*static_inputs); loss.backward(); optimizer.step()``
 once and returns ``replay``: each call of it copies a new batch into the static inputs and replays the several hundred launches of the
 step without host work between them -- the BERT fine-tuning step (``BertEncoder(finetune_layers=k, dropout=True)`` under
-``TemporalTextEncoder``) is bound by the host's launch rate at small batches.  A replay repeats the kernel arguments of the capture, so
+``TemporalTextEncoder``) and the end-to-end step (``encoders.EndToEndDEER``: the three encoders, a fusion module, the DEER head and
+the loss) are bound by the host's launch rate at small batches.  A replay repeats the kernel arguments of the capture, so
 what must differ between steps lives on the device:
 
   dropout steps    every module under the optimiser's module (``ModuleAdamW.for_module``) or under ``modules`` that offers
                    ``set_step_counter`` gets a one-element int64 counter of its own, starting at the module's host step; at the end of
                    the captured region each counter takes the number of live forwards its module ran in the region (one small add
-                   per module, recorded with the step), so replay r draws the masks the r-th eager step would have drawn
+                   per module that drew, recorded with the step), so replay r draws the masks the r-th eager step would have drawn
+                   (``stepcount.py`` states the protocol; ``bert.py`` and ``text.py`` state it for themselves)
   Adam's step      the optimiser's device records (``ModuleAdamW(capturable=True)``)
   lr, weight decay the same records; ``replay`` refreshes them when ``param_groups`` moved (an LR scheduler between replays)
 
@@ -89,7 +91,9 @@ def capture_train_step(step_fn, optimizer, static_inputs: Sequence[torch.Tensor]
         loss.backward()
         optimizer.step()
         for m, t in counters:
-            t.add_(m.take_step_count())          # the steps this region used: the next replay starts behind them
+            k = m.take_step_count()              # the steps this region used: the next replay starts behind them
+            if k:                                # (a module that drew nothing -- a DEER head run by its owner, eval() -- costs no launch)
+                t.add_(k)
         return loss
 
     def drop_grads():

@@ -25,6 +25,7 @@ from torch import nn
 
 from . import _lib, fusions, ops, temporal
 from .opseq import Exec, set_drop
+from .stepcount import StepCounted
 
 W = 512                                           # hidden_dim of the sequence path
 _SITE_SP, _SITE_CNN, _SITE_OP = 144, 145, 146     # spatial_projection / temporal_cnn / output_projection dropout
@@ -178,7 +179,7 @@ class _TemporalCnnFn(torch.autograd.Function):
         return (dcur.to(hdt), *grads[0], *grads[1], None, None, None, None, None, None)
 
 
-class TemporalVideoEncoder(nn.Module):
+class TemporalVideoEncoder(nn.Module, StepCounted):
     """``encoders.EnhancedVideoEncoder`` (reference src/models/encoders.py:392-550) on per-frame features: (B, T, 512) or
     (B, 512) -> (B, 512) fp32.  Submodules carry the reference's names and order, so a reference checkpoint loads with
     ``strict=True``; ``spatial_backbone`` (the Conv2d stack on frames) is held for that and never run: frame tensors raise
@@ -232,8 +233,7 @@ class TemporalVideoEncoder(nn.Module):
         c = self.compute_dtype
         drop = None
         if self.training and self.dropout > 0:
-            drop = (self.dropout, int(self.dropout_seed), self._train_step)
-            self._train_step += 1
+            drop = self._drop_step(self.dropout, self.dropout_seed)
         h = x.transpose(0, 1).reshape(T * B, 512)                              # time-major rows t * B + b
         h = fusions.linear(h, self.spatial_projection[0], c, relu=True, drop=drop, site=_SITE_SP)
         if T > 1:
