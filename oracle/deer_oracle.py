@@ -521,10 +521,12 @@ def bilinear_fusion(P, feats, prefix=""):
     return y
 
 
-def adaptive_fusion(P, feats, strategies, prefix=""):
-    """AdaptiveFusionGating.forward in eval mode -- fusion.py:458-501 (strategies 'attention' / 'bilinear')."""
+def adaptive_fusion(P, feats, strategies, prefix="", mask=None, p=0.3):
+    """AdaptiveFusionGating.forward -- fusion.py:458-501 (strategies 'attention' / 'bilinear').  ``mask``: the keep-mask of the
+    feature encoder's Dropout(0.3) (:440, behind its first Linear-ReLU); None = eval mode."""
     cat = torch.cat(list(feats), dim=-1)
-    h = torch.relu(_lin(torch.relu(_lin(cat, P, prefix + "feature_encoder.0")), P, prefix + "feature_encoder.3"))
+    h = _drop(torch.relu(_lin(cat, P, prefix + "feature_encoder.0")), mask, p)
+    h = torch.relu(_lin(h, P, prefix + "feature_encoder.3"))
     w = torch.softmax(_lin(h, P, prefix + "strategy_selector.0"), dim=-1)
     outs = []
     for name in strategies:
@@ -535,9 +537,10 @@ def adaptive_fusion(P, feats, strategies, prefix=""):
     return (w.unsqueeze(-1) * torch.stack(outs, dim=1)).sum(dim=1), w
 
 
-def concat_fusion(P, x, prefix=""):
-    """The concatenation branch of create_fusion_module in eval mode -- fusion.py:584-592: LayerNorm(ReLU(Linear(x)))."""
-    return _layer_norm(torch.relu(_lin(x, P, prefix + "0")), P[prefix + "3.weight"], P[prefix + "3.bias"])
+def concat_fusion(P, x, prefix="", mask=None, p=0.3):
+    """The concatenation branch of create_fusion_module -- fusion.py:584-592: LayerNorm(Dropout(ReLU(Linear(x)))).  ``mask``: the
+    keep-mask of its Dropout; None = eval mode."""
+    return _layer_norm(_drop(torch.relu(_lin(x, P, prefix + "0")), mask, p), P[prefix + "3.weight"], P[prefix + "3.bias"])
 
 
 # --------------------------------------------------------------------------- metric

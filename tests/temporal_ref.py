@@ -104,9 +104,15 @@ def drop_mask(site: int, rows: int, cols: int, p: float, seed: int, step: int, s
     return torch.from_numpy(keep.astype(np.float64)) * (drop_threshold(p)[1] if scale is None else scale)
 
 
+def seed_offset(record) -> int:
+    """what a site record adds to the module's seed: its optional sixth entry, 0 where a record has five"""
+    return record[5] if len(record) > 5 else 0
+
+
 def draw(sites, seed: int, step: int) -> dict:
-    """{name: float64 keep * scale (rows, cols)} of a list of sites at one dropout step"""
-    return {name: drop_mask(site, rows, cols, p, seed, step) for name, site, rows, cols, p in sites}
+    """{name: float64 keep * scale (rows, cols)} of a list of sites at one dropout step; a record is (name, site, rows, cols, p) or
+    (name, site, rows, cols, p, seed offset) -- a launch that draws under the module's seed + an offset of its own"""
+    return {r[0]: drop_mask(r[1], r[2], r[3], r[4], seed + seed_offset(r), step) for r in sites}
 
 
 def sites(B: int, T: int, p: float, num_layers: int = 2) -> list:

@@ -1,15 +1,19 @@
-"""The references tests/test_gpu_dropstep.py holds the dropout training step of the audio, text and video encoders and of the
-stand-alone DEER heads to (tests/dropstep_ref.py and the training forms of temporal_ref / text_ref / video_ref / head_ref), checked on
-their own: no GPU, no launch.
+"""The references tests/test_gpu_dropstep.py holds the dropout training step of the audio, text and video encoders, of the
+stand-alone DEER heads and of the fusion modules on the operator path (HierarchicalMultimodalFusion at a non-default geometry,
+AdaptiveFusionGating, ConcatFusion) to (tests/dropstep_ref.py and the training forms of temporal_ref / text_ref / video_ref /
+head_ref / fusion_ref), checked on their own: no GPU, no launch.
 
  * all-ones masks are the unmasked forward, bit for bit (outputs and gradients, float64 and bf16-emulating);
  * with the masks of a step, outputs and autograd gradients equal an INDEPENDENT float64 composition of torch modules (two chained
    one-layer nn.LSTM with the mask multiplied in between; nn.Conv1d / nn.BatchNorm1d in .train() / ReLU / mask; nn.Linear chains)
-   to a relative distance of 1e-12;
- * every site mistake the modules could make moves the reference by at least ten times what the GPU test tolerates
-   (``test_step_test_is_sensitive``; the measured factors are in its docstring);
+   to a relative distance of 1e-12; the fusions: the modules' own nn.Linear / nn.LayerNorm / nn.Bilinear children in float64, the
+   attention written per head with the token mean in front of out_proj;
+ * every site mistake the modules could make moves the reference by at least ten times what the GPU test tolerates, for the fusions
+   by at least a hundred times (``test_step_test_is_sensitive``; the measured factors are in its docstring);
+ * the mean keep fraction of every drawn mask lies within five binomial standard deviations of 1 - p;
  * no ReLU input that reaches a gradient lies within stackb_ref.RELU_BAND of zero at the chosen input seeds;
- * the sites one step can draw are pairwise distinct, at the largest geometry the modules accept and across a ComposedDEER."""
+ * what one step can draw at -- the pairs (seed offset, site) -- is pairwise distinct, at the largest geometry the modules accept
+   and across a ComposedDEER; the trimodal attention of the operator path draws at (7919, 3)."""
 import copy
 
 import numpy as np
@@ -20,7 +24,8 @@ from torch import nn
 from mmdeer import fusions, generic_fusion, head, side, temporal, text, video
 
 from . import dropstep_ref as D
-from . import head_ref, text_ref
+from . import fusion_ref, head_ref, text_ref
+from .rowkernel_ref import SITE_TRI_ATTN
 from .stackb_ref import RELU_BAND
 
 F64 = torch.float64
@@ -175,8 +180,77 @@ def _multi_torch(ad, case, X, masks):
     return out, dict(m.named_parameters()), {}
 
 
+def _block_torch(seq, x, keep):
+    return seq[3](torch.relu(seq[0](x)) * keep)                   # Linear, ReLU, (Dropout,) LayerNorm
+
+
+def _fusion_torch(ad, case, X, masks):
+    """The operator path's own torch children in float64.  The 1-key attention: the value third of in_proj, one factor per (row,
+    head) spread over the head's 32 columns, out_proj.  The 2-token attention head by head, the token mean in front of out_proj."""
+    B = case[3]
+    m = _load(generic_fusion.GenericHierarchicalFusion(*case[:3]), ad.state(case))
+    av, tri = m.audio_visual_fusion, m.trimodal_fusion
+    E, H = m.intermediate_dim, m.heads
+    mha = av.cross_attention
+
+    def attend(kv, keep):
+        v = nn.functional.linear(kv, mha.in_proj_weight[2 * E:], mha.in_proj_bias[2 * E:])
+        return mha.out_proj(v * keep.repeat_interleave(E // H, dim=1))
+    a_att, v_att = attend(av.video_projection(X["video"]), masks["av"][:B]), attend(av.audio_projection(X["audio"]), masks["av"][B:])
+    avf = _block_torch(av.fusion_layers, torch.cat([a_att, v_att], dim=1), masks["av_fuse"])
+    tm = tri.modality_attention
+    Fd = m.fusion_dim
+    tok = [tri.audiovisual_projection(avf), tri.text_projection(X["text"])]
+    qkv = [nn.functional.linear(t, tm.in_proj_weight, tm.in_proj_bias) for t in tok]                 # per token (B, 3F)
+    keep = masks["tri_attn"]                                                                          # column 4 h + 2 t + u
+    ctx, wts = [], torch.zeros(B, 2, 2, dtype=F64)
+    for h in range(H):
+        c = slice(h * (Fd // H), (h + 1) * (Fd // H))
+        q = [t[:, :Fd][:, c] for t in qkv]
+        k = [t[:, Fd:2 * Fd][:, c] for t in qkv]
+        v = [t[:, 2 * Fd:][:, c] for t in qkv]
+        o = 0
+        for t in range(2):
+            sc = torch.stack([(q[t] * k[u]).sum(1) for u in range(2)], dim=1) / (Fd // H) ** 0.5
+            pr = torch.softmax(sc, dim=1) * keep[:, 4 * h + 2 * t:4 * h + 2 * t + 2]
+            wts[:, t] = wts[:, t] + pr.detach() / H
+            o = o + (pr[:, 0:1] * v[0] + pr[:, 1:2] * v[1]) / 2
+        ctx.append(o)
+    trif = _block_torch(tri.final_fusion, tm.out_proj(torch.cat(ctx, dim=1)), masks["tri_fuse"])
+    fused = _block_torch(m.output_projection, trif, masks["out_proj"])
+    w = masks["av"].mean(dim=1, keepdim=True)
+    outs = dict(zip(fusion_ref.FUSION_OUTS, (fused, avf, trif, wts, w[:B], w[B:])))
+    return outs, dict(m.named_parameters()), {}
+
+
+def _adaptive_torch(ad, case, X, masks):
+    m = _load(fusions.AdaptiveFusionGating(list(D.synth.FUSION_ALT_DIMS), list(ad.strategies), ad.hidden), ad.state(case))
+    feats = [X[k] for k in ad.diff_inputs]
+    enc = m.feature_encoder
+    h = torch.relu(enc[3](torch.relu(enc[0](torch.cat(feats, dim=1))) * masks["enc"]))
+    w = m.strategy_selector(h)                                                                        # Linear, Softmax
+    att, bil = m.fusion_modules["attention"], m.fusion_modules["bilinear"]
+    st = torch.stack([pr(f) for pr, f in zip(att.projections, feats)], dim=1)
+    a = torch.bmm(torch.softmax(att.attention(st), dim=1).transpose(1, 2), st).squeeze(1)
+    b = bil.bilinear(feats[0], feats[1]) + bil.additional_linear(feats[2])
+    y = torch.bmm(w.unsqueeze(1), torch.stack([a, b], dim=1)).squeeze(1)
+    return {"fused_features": y, "strategy_weights": w.detach()}, dict(m.named_parameters()), {}
+
+
+def _concat_torch(ad, case, X, masks):
+    m = _load(fusions.ConcatFusion(sum(D.synth.FUSION_ALT_DIMS), ad.width), ad.state(case))
+    return {"out": _block_torch(m, X["x"], masks["concat"])}, dict(m.named_parameters()), {}
+
+
 TORCH = {"audio": _audio_torch, "text_embeddings": _text_torch, "text_ids": _text_torch, "video": _video_torch,
-         "deer_layer": _layer_torch, "multi_dim": _multi_torch}
+         "deer_layer": _layer_torch, "multi_dim": _multi_torch, "fusion": _fusion_torch, "adaptive": _adaptive_torch,
+         "concat": _concat_torch}
+
+
+def _special_rows(ad, k):
+    """(row slices of parameter k that are analytic zeros: zero_grads + noise_grads, whether that is the whole parameter)"""
+    sl = D.rows_of(ad.zero_grads).get(k, []) + D.rows_of(ad.noise_grads).get(k, [])
+    return sl, any(s == slice(None) for s in sl)
 
 
 @pytest.mark.parametrize("name,case", D.ALL_CASES, ids=D.CASE_IDS)
@@ -189,7 +263,7 @@ def test_masked_reference_equals_an_independent_torch_composition(name, case):
     outs, params, buffers = TORCH[name](ad, case, X, masks)
     assert list(outs) == list(r["out"])
     W = ad.weights(case, outs)
-    sum((outs[k] * W[k]).sum() for k in outs).backward()
+    sum((outs[k] * W[k]).sum() for k in W).backward()
     worst = 0.0
     for k in outs:
         worst = max(worst, D.rel(outs[k], r["out"][k]))
@@ -199,14 +273,17 @@ def test_masked_reference_equals_an_independent_torch_composition(name, case):
         if g is None:
             assert params[k].grad is None or not bool(params[k].grad.any()), k
             continue
-        if k in ad.zero_grads or k in ad.noise_grads or not bool(g.any()):        # analytic zeros: noise (or nothing) on both sides
-            scale = float(r["grads"][k.replace("bias", "weight")].abs().max()) if k.endswith("bias") else 1.0
+        rows, whole = _special_rows(ad, k)
+        scale = float(r["grads"][k.replace("bias", "weight")].abs().max()) if k.endswith("bias") else 1.0
+        if whole or not bool(g.any()):                                            # analytic zeros: noise (or nothing) on both sides
             assert float(g.abs().max()) <= 1e-9 * scale and (params[k].grad is None or float(params[k].grad.abs().max()) <= 1e-9 * scale), k
             continue
+        for sl in rows:                                                           # ... in some rows of a parameter
+            assert float(g[sl].abs().max()) <= 1e-9 * scale and float(params[k].grad[sl].abs().max()) <= 1e-9 * scale, (k, sl)
         live += 1
-        worst = max(worst, D.rel(params[k].grad, g))
-        assert D.rel(params[k].grad, g) <= 1e-12, k
-    assert live >= 6
+        worst = max(worst, D.rel(D.without_rows(params[k].grad, rows), D.without_rows(g, rows)))
+        assert D.rel(D.without_rows(params[k].grad, rows), D.without_rows(g, rows)) <= 1e-12, k
+    assert live >= (4 if name == "concat" else 6)                                 # ConcatFusion has four parameters
     for k in ad.diff_inputs:
         worst = max(worst, D.rel(X[k].grad, r["dx"][k]))
         assert D.rel(X[k].grad, r["dx"][k]) <= 1e-12, k
@@ -220,7 +297,7 @@ def test_masked_reference_equals_an_independent_torch_composition(name, case):
 # ------------------------------------------------------------------------------------------------------------------- sensitivity
 def _renumber(which, to):
     def f(ad, case, sites, masks):
-        s2 = [(n, to(s) if n == which else s, r, c, p) for n, s, r, c, p in sites]
+        s2 = [(n, to(s) if n == which else s, r, c, p, *o) for n, s, r, c, p, *o in sites]
         return ad.masks(case, sites=s2)
     return f
 
@@ -249,26 +326,69 @@ def _second_batchnorm(ad, case, sites, masks):
 def _exchange(a, b):
     def f(ad, case, sites, masks):
         num = {n: s for n, s, *_ in sites}
-        return ad.masks(case, sites=[(n, num[b] if n == a else num[a] if n == b else s, r, c, p) for n, s, r, c, p in sites])
+        return ad.masks(case, sites=[(n, num[b] if n == a else num[a] if n == b else s, r, c, p, *o) for n, s, r, c, p, *o in sites])
     return f
 
 
 def _global_columns(ad, case, sites, masks):
     _, Dm, Hd = ad.geometry(case)
     w = Hd // 4
-    wide = ad.masks(case, sites=[(n, s, r, Dm * w, p) for n, s, r, c, p in sites if n.startswith("h1.")])
+    wide = ad.masks(case, sites=[(n, s, r, Dm * w, p, *o) for n, s, r, c, p, *o in sites if n.startswith("h1.")])
     return dict(masks, **{f"h1.{d}": wide[f"h1.{d}"][:, d * w:(d + 1) * w] for d in range(Dm)})
 
 
 def _heads_rotated(ad, case, sites, masks):
     Dm = ad.geometry(case)[1]
-    return ad.masks(case, sites=[(n, head._SITE_H1 + (int(n[3:]) + 1) % Dm if n.startswith("h1.") else s, r, c, p) for n, s, r, c, p in sites])
+    return ad.masks(case, sites=[(n, head._SITE_H1 + (int(n[3:]) + 1) % Dm if n.startswith("h1.") else s, r, c, p, *o) for n, s, r, c, p, *o in sites])
+
+
+def _tri_attn_at(site, offset):
+    """the trimodal attention's mask drawn at another (seed offset, site)"""
+    def f(ad, case, sites, masks):
+        return ad.masks(case, sites=[(n, site, r, c, p, offset) if n == "tri_attn" else (n, s, r, c, p, *o) for n, s, r, c, p, *o in sites])
+    return f
+
+
+def _av_halves_exchanged(ad, case, sites, masks):
+    B = case[3]
+    return dict(masks, av=torch.cat([masks["av"][B:], masks["av"][:B]], dim=0))
+
+
+def _av_redrawn(cols):
+    """the AV attention's decisions drawn on (2B, cols) at its site: cols = 1 is one decision per row (spread over the heads), cols =
+    E one per column (drop_shift = 0; the reference then takes the mask per column)"""
+    def f(ad, case, sites, masks):
+        wide = ad.masks(case, sites=[(n, s, r, cols, p, *o) for n, s, r, c, p, *o in sites if n == "av"])["av"]
+        return dict(masks, av=wide.expand(-1, fusion_ref.HEADS).contiguous() if cols == 1 else wide)
+    return f
+
+
+class _AdaptiveSecondLinear(D.Adaptive):
+    """The mistaken module: the encoder's dropout behind its SECOND Linear-ReLU (feature_encoder.3, hidden / 2 columns)."""
+
+    def sites(self, case):
+        return fusion_ref.sites_adaptive(case[0], case[1], self.hidden // 2)
+
+    def ref(self, P, X, masks, emulate=False):
+        from oracle import deer_oracle as O
+        feats = [X[k] for k in self.diff_inputs]
+        h = torch.relu(O._lin(torch.relu(O._lin(torch.cat(feats, dim=-1), P, "feature_encoder.0")), P, "feature_encoder.3")) * masks["enc"]
+        w = torch.softmax(O._lin(h, P, "strategy_selector.0"), dim=-1)
+        outs = [O.attention_fusion(P, feats, "fusion_modules.attention.")[0], O.bilinear_fusion(P, feats, "fusion_modules.bilinear.")]
+        return {"fused_features": (w.unsqueeze(-1) * torch.stack(outs, dim=1)).sum(dim=1), "strategy_weights": w.detach()}, {}
+
+
+def _second_linear(ad, case, sites, masks):
+    wrong = _AdaptiveSecondLinear()
+    return wrong, wrong.masks(case)
 
 
 def _mutations(name, case):
     ad = AD[name]
     out = {f"{n} at the neighbouring site": _renumber(n, lambda s: s + 1) for n, *_ in ad.sites(case)}
     out.update({"step + 1": _next_step, "scale 1": _scale_one})
+    if name == "concat":         # LayerNorm divides a common factor of its input out, forward and backward: see the test below
+        del out["scale 1"]
     if name in ("audio", "video") and case[1] > 1:
         for n in (("inter.0",) if name == "audio" else ("sp", "cnn")):
             out[f"{n} batch-major"] = _batch_major(n)
@@ -279,11 +399,23 @@ def _mutations(name, case):
     if name == "multi_dim":
         out["heads' layer-1 columns indexed globally"] = _global_columns
         out["head d at head d + 1's site"] = _heads_rotated
+    if name == "fusion":
+        out["the trimodal mask under the module's plain seed"] = _tri_attn_at(SITE_TRI_ATTN, 0)
+        out["the trimodal mask at generic_fusion._SITE_TRI_ATTN = 83, which nothing draws at"] = _tri_attn_at(generic_fusion._SITE_TRI_ATTN, 0)
+        out["the AV halves exchanged"] = _av_halves_exchanged
+        out["one AV mask per row instead of per (row, head)"] = _av_redrawn(1)
+        out["AV mask per column instead of per head (shift 0)"] = _av_redrawn(fusion_ref.E)
+        out["_SITE_AVF and _SITE_TRIF exchanged"] = _exchange("av_fuse", "tri_fuse")
+    if name == "adaptive":
+        out["the encoder's mask on its second Linear instead of its first"] = _second_linear
     return out
 
 
 SENSITIVITY_CASES = [("audio", (5, 3, 0.3)), ("audio", (5, 1, 0.3)), ("text_embeddings", (5, 7, 0.3)), ("text_ids", (5, 7, 0.3)),
-                     ("video", (5, 3, 0.3)), ("video", (5, 1, 0.3)), ("deer_layer", ("dl96x3x64", 5, 0.3)), ("multi_dim", ("md192x3x128", 5, 0.3))]
+                     ("video", (5, 3, 0.3)), ("video", (5, 1, 0.3)), ("deer_layer", ("dl96x3x64", 5, 0.3)), ("multi_dim", ("md192x3x128", 5, 0.3)),
+                     ("fusion", (40, 128, 300, 1, 0.3)), ("fusion", (40, 128, 300, 37, 0.3)), ("fusion", (512, 512, 512, 5, 0.5)),
+                     ("adaptive", (37, 0.3)), ("concat", (1, 0.3)), ("concat", (37, 0.3))]
+FUSION_FAMILIES = ("fusion", "adaptive", "concat")       # their mistakes must show at 100 x the bound, the others' at 10 x
 
 
 def _moved(ad, base, r2):
@@ -294,9 +426,10 @@ def _moved(ad, base, r2):
             worst = max(worst, (f"output {k}", D.out_fraction(r2["out"][k], v)), key=lambda t: t[1])
     for k, g in list(base["grads"].items()) + [("input " + k, v) for k, v in base["dx"].items()]:
         g2 = r2["grads"][k] if k in r2["grads"] else r2["dx"][k[6:]]
-        if g is None or k in ad.zero_grads or k in ad.noise_grads or not bool(g.any()):
+        rows, whole = _special_rows(ad, k)
+        if g is None or whole or not bool(g.any()):
             continue
-        worst = max(worst, (k, D.grad_fraction(g2, g)), key=lambda t: t[1])
+        worst = max(worst, (k, D.grad_fraction(D.without_rows(g2, rows), D.without_rows(g, rows))), key=lambda t: t[1])
     # the video encoder's output and gradients do not see a common factor on a mask (BatchNorm and LayerNorm divide it out): its
     # running statistics do
     for k, v in base["buffers"].items():
@@ -311,19 +444,48 @@ def test_step_test_is_sensitive(name, case):
     the case's mutations, and the mutation that gives it; pytest -s prints all of them):
     audio 5 x 3: 22265 (inter-layer rows batch-major); audio 5 x 1: 22465 (scale 1); text by embeddings: 2629 (scale 1); text by ids:
     17674 (scale 1); video 5 x 3: 24356 (output_projection's site + 1; scale 1 shows only in the running buffers, by 100288); video
-    5 x 1: 1518 (scale 1); DEERLayer: 1853 (scale 1); MultiDimensionalDEER: 1782 (head 1's layer-1 site + 1)."""
+    5 x 1: 1518 (scale 1); DEERLayer: 1853 (scale 1); MultiDimensionalDEER: 1782 (head 1's layer-1 site + 1).
+
+    The fusions on the operator path: at least 100 x.  Measured at 40/128/300 B = 1 | B = 37 | 512/512/512 B = 5, p = 0.5:
+      a neighbouring site (the weakest of the five sites, out_proj's)          28170 |  30189 |  16890
+      another step                                                             59691 | 156938 | 106336
+      a lost 1 / (1 - p) scale                                                  3858 |  10858 |  12610
+      the trimodal mask under the module's plain seed                          58804 | 135627 | 120263
+      the trimodal mask at site 83, plain seed                                118175 | 166553 |  79270
+      the AV halves exchanged                                                  42852 | 137541 |  89299
+      one AV mask per row instead of per (row, head)                           36857 | 136189 | 152353
+      the AV mask per column instead of per head (shift 0)                     69497 | 158287 | 126413
+      _SITE_AVF and _SITE_TRIF exchanged                                       45514 | 116025 | 107508
+    AdaptiveFusionGating, B = 37: the encoder's mask on its second Linear instead of its first 30019; its site + 1 63885; another step
+    38795; a lost scale 49713.  At B = 1 the one row's gate is nearly balanced (weights 0.484 / 0.516): a lost scale moves the
+    output by 21 x and every gradient of the gating path by 50 x -- a 30 % change of a gradient is 0.3 / (2 x 3e-3) of its bound
+    at most -- so that case is in test A and not in this list.  ConcatFusion, B = 1 | 37: its site + 1 20568 | 30194; another step
+    19953 | 32258; it cannot see a common scale (the test below)."""
     ad = AD[name]
     sites, masks = ad.sites(case), ad.masks(case)
     base = D.ref_step(ad, case, masks)
     least = None
+    need = 100.0 if name in FUSION_FAMILIES else 10.0
     for what, mutate in _mutations(name, case).items():
         m2 = mutate(ad, case, copy.deepcopy(sites), masks)
+        wrong, m2 = m2 if isinstance(m2, tuple) else (ad, m2)                   # a mistake no mask of the right module expresses
         assert set(m2) >= set(masks)
-        k, f = _moved(ad, base, D.ref_step(ad, case, m2))
+        k, f = _moved(ad, base, D.ref_step(wrong, case, m2))
         print(f"{name} {case}: {what}: {k} moved by {f:.0f} x its bound")
-        assert f >= 10.0, (what, k, f)
+        assert f >= need, (what, k, f)
         least = (what, f) if least is None or f < least[1] else least
     print(f"{name} {case}: least {least[1]:.0f} x ({least[0]})")
+
+
+def test_concat_fusion_does_not_see_a_common_factor_on_its_mask():
+    """Why ConcatFusion's mutations leave "scale 1" out: its one mask sits directly in front of a LayerNorm, which divides a common
+    factor out (up to its eps), so output and gradients are those of the same function: nothing test A compares moves by as much as
+    its bound (measured: 0.018 of it).  A backward that alone lost the scale is another matter: test A sees it in every gradient."""
+    ad = AD["concat"]
+    for case in ad.cases[:2]:
+        masks = ad.masks(case)
+        k, f = _moved(ad, D.ref_step(ad, case, masks), D.ref_step(ad, case, _scale_one(ad, case, None, masks)))
+        assert f < 1.0, (case, k, f)
 
 
 # ------------------------------------------------------------------------------------------------------------------- ReLU band
@@ -332,11 +494,41 @@ def test_no_relu_input_of_a_case_lies_in_the_band(name, case):
     """At the chosen input seed no ReLU input of the float64 step that reaches a gradient lies within RELU_BAND (1e-5 of the layer's
     largest input) of zero, so test A compares gradients across decisions both sides take alike, and needs no disputed-unit rule.
     The seed is the first from 0 with that property (seed 0 for 13 of the 20 cases, 1 for six; the video encoder's 37 x 3 case, with
-    150 k such units, had 3 .. 11 of them in the band at seeds 0 .. 34 and none at 35)."""
+    150 k such units, had 3 .. 11 of them in the band at seeds 0 .. 34 and none at 35).  The nine fusion cases: seed 0 for seven, 1 for
+    the fusion at B = 5, p = 0.1, and 8 at B = 37 (47 k units, 1 .. 3 of them in the band at seeds 0 .. 7)."""
     ad = AD[name]
     assert D.band_count(ad, case, ad.seed(case), RELU_BAND) == 0
     if ad.seed(case) > 0 and case[0] != 37:
         assert D.band_count(ad, case, ad.seed(case) - 1, RELU_BAND) > 0
+
+
+def test_no_relu_input_of_the_seam_lies_in_the_band():
+    """The ComposedDEER seam case of tests/test_gpu_dropstep.py: fusion and head in one step, five ReLU layers of the fusion's three
+    blocks and the head's eight; D.SEAM_INPUT_SEED is the first seed with no kept unit in the band."""
+    def count(seed):
+        return sum(int(((z.abs() <= RELU_BAND * float(z.abs().max())) & (m > 0)).sum()) for z, m in D.seam_ref(seed)["relu"])
+    assert len(D.seam_ref()["relu"]) == 3 + 2 + 2 * 3
+    assert count(D.SEAM_INPUT_SEED) == 0
+    assert all(count(s) > 0 for s in range(D.SEAM_INPUT_SEED))
+
+
+# ------------------------------------------------------------------------------------------------------------------ keep fraction
+@pytest.mark.parametrize("name", list(AD))
+def test_mean_keep_fraction_of_every_drawn_mask(name):
+    """A mask of n decisions kept with probability 1 - p has a mean keep fraction within 5 binomial standard deviations,
+    5 sqrt(p (1 - p) / n), of 1 - p (a fair draw misses that with probability 6e-7): a threshold, a probability or a shape read
+    wrongly by the CPU draw does not."""
+    seen = 0
+    for case in AD[name].cases:
+        for step in (D.STEP, D.STEP + 1):
+            masks = AD[name].masks(case, step=step)
+            for rec in AD[name].sites(case):
+                n, p = rec[2] * rec[3], rec[4]
+                keep = float((masks[rec[0]] > 0).double().mean())
+                assert tuple(masks[rec[0]].shape) == (rec[2], rec[3])
+                assert abs(keep - (1 - p)) <= 5 * (p * (1 - p) / n) ** 0.5, (name, case, rec, keep)
+                seen += 1
+    assert seen >= 2 * len(AD[name].cases)
 
 
 # ---------------------------------------------------------------------------------------------------------------- disjoint sites
@@ -350,18 +542,20 @@ def test_sites_of_one_step_are_pairwise_distinct():
         temporal.TemporalAudioEncoder({"num_layers": L + 1})
     with pytest.raises(NotImplementedError):
         head.MultiDimensionalDEER(64, emotion_dims=4)
-    audio_seq = [s for _, s, *_ in D.temporal_ref.sites(5, 3, 0.3, num_layers=L)]
-    audio_one = [s for _, s, *_ in D.temporal_ref.sites(5, 1, 0.3, num_layers=L)]
-    txt = [s for _, s, *_ in text_ref.sites(5, 512, 0.3)]
-    vid = [s for _, s, *_ in D.video_ref.sites(5, 3, 0.3)]
-    layer = [s for _, s, *_ in head_ref.sites_layer(5, 1024, 0.3)]
-    multi = [s for _, s, *_ in head_ref.sites_multi(5, 2048, 3, 0.3)]
-    assert len(audio_seq) == len(audio_one) == L and len(multi) == 6
-    for one in (audio_seq, audio_one, txt, vid, layer, multi):
+    at = lambda records: [D.drawn(r) for r in records]                # noqa: E731  what a launch draws at: (seed offset, site)
+    audio_seq, audio_one = at(D.temporal_ref.sites(5, 3, 0.3, num_layers=L)), at(D.temporal_ref.sites(5, 1, 0.3, num_layers=L))
+    txt, vid = at(text_ref.sites(5, 512, 0.3)), at(D.video_ref.sites(5, 3, 0.3))
+    layer, multi = at(head_ref.sites_layer(5, 1024, 0.3)), at(head_ref.sites_multi(5, 2048, 3, 0.3))
+    hier, alt = at(fusion_ref.sites_fusion(5, 0.3)), at(fusion_ref.sites_adaptive(5, 0.3)) + at(fusion_ref.sites_concat(5, 0.3))
+    assert len(audio_seq) == len(audio_one) == L and len(multi) == 6 and len(hier) == 5
+    for one in (audio_seq, audio_one, txt, vid, layer, multi, hier, alt):
         assert len(set(one)) == len(one), one
-    fusion = [fusions._SITE_ENC, fusions._SITE_CONCAT, generic_fusion._SITE_AV, generic_fusion._SITE_AVF, generic_fusion._SITE_TRI_ATTN,
-              generic_fusion._SITE_TRIF, generic_fusion._SITE_OUT]
+    # the operator path's trimodal attention: the library's own site under the module's seed + 7919, and the only offset draw
+    assert hier[2] == (generic_fusion._TRI_SEED_OFFSET, SITE_TRI_ATTN) == (7919, 3)
+    assert hier == [(0, generic_fusion._SITE_AV), (0, generic_fusion._SITE_AVF), (7919, 3), (0, generic_fusion._SITE_TRIF), (0, generic_fusion._SITE_OUT)]
+    assert alt == [(0, fusions._SITE_ENC), (0, fusions._SITE_CONCAT)]
     # audio_seq and audio_one share _SITE_OP: one encoder runs one of the two paths per forward
-    everything = sorted(set(audio_seq) | set(audio_one)) + txt + vid + layer + multi + fusion
+    everything = sorted(set(audio_seq) | set(audio_one)) + txt + vid + layer + multi + hier + alt
     assert len(set(everything)) == len(everything), sorted(everything)
-    assert max(everything) < 256 and min(everything) > 9              # 1 .. 9: the fused model's own sites
+    plain = [s for o, s in everything if o == 0]
+    assert len(plain) == len(everything) - 1 and max(plain) < 256 and min(plain) > 9      # 1 .. 9: the fused model's own sites

@@ -29,6 +29,10 @@ from .opseq import Exec
 from .stepcount import DropOwner, counter_ptr
 
 _SITE_AV, _SITE_AVF, _SITE_TRI_ATTN, _SITE_TRIF, _SITE_OUT = 81, 82, 83, 84, 85
+# _SITE_TRI_ATTN is NOT a drawn site: 83 is only kept out of use.  The trimodal attention takes no site from this module --
+# mmdeer_trimodal_attn_fwd / _bwd draw at the library's own SITE_TRI_ATTN (csrc/common.h: 3), which the fused model uses too -- so
+# the launch gets the module's seed + _TRI_SEED_OFFSET, which keeps its stream apart from every site drawn under the plain seed.
+_TRI_SEED_OFFSET = 7919
 
 
 class _AVAttnFn(torch.autograd.Function):
@@ -194,7 +198,7 @@ class GenericHierarchicalFusion(nn.Module, DropOwner):
         xtok = torch.stack([x0, x1], dim=1).reshape(2 * B, self.fusion_dim)       # row 2b + t
         tm = tri.modality_attention
         qkv = _LinearRaw.apply(xtok, tm.in_proj_weight, tm.in_proj_bias, cd)
-        tdrop = (drop[0], drop[1] + 7919) + drop[2:] if drop else None       # (a device step counter rides along)
+        tdrop = (drop[0], drop[1] + _TRI_SEED_OFFSET) + drop[2:] if drop else None      # (a device step counter rides along)
         obar, attn_w = _TriAttnFn.apply(qkv, cd, tdrop, True)
         pooled = linear(obar, tm.out_proj, cd)
         ff = tri.final_fusion

@@ -714,6 +714,13 @@ class HierarchicalMultimodalFusion(nn.Module):
     def _train_step(self) -> int:
         return self._generic._train_step if self._generic is not None else self._core._step
 
+    @_train_step.setter
+    def _train_step(self, v: int) -> None:
+        if self._generic is not None:
+            self._generic._train_step = v
+        else:
+            self._core._step = v
+
     def set_step_counter(self, t) -> None:
         if self._generic is not None:
             self._generic.set_step_counter(t)
