@@ -1,6 +1,6 @@
 """Parser of include/mmdeer.h: the header is the one statement of the C ABI, and the ctypes binding (_lib.py) is derived from it.
 Its companions include/mmdeer_video.h (the temporal video encoder's operators), include/mmdeer_frames.h (the Conv2d backbone on
-frames), include/mmdeer_frames_bwd.h (its backward), include/mmdeer_routes.h (the layer chains' route queries), include/mmdeer_bert.h (the BERT trunk's forward operators), include/mmdeer_bert_bwd.h (their backward) include/mmdeer_bert_drop.h (both with the trunk's dropout inside) include/mmdeer_optim.h (clip + AdamW over any list of tensors) include/mmdeer_graph.h (device step counters for HIP-graph replays) and include/mmdeer_drop_dev.h (the same counter for the three by-value dropout entries of mmdeer.h) are written in the same grammar and parsed here too.
+frames), include/mmdeer_frames_bwd.h (its backward), include/mmdeer_routes.h (the layer chains' route queries), include/mmdeer_bert.h (the BERT trunk's forward operators), include/mmdeer_bert_bwd.h (their backward) include/mmdeer_bert_drop.h (both with the trunk's dropout inside) include/mmdeer_optim.h (clip + AdamW over any list of tensors) include/mmdeer_graph.h (device step counters for HIP-graph replays) include/mmdeer_drop_dev.h (the same counter for the three by-value dropout entries of mmdeer.h) and include/mmdeer_seqlen.h (the audio encoder's recurrence and pool with per-sample lengths) are written in the same grammar and parsed here too.
 
 The header is regular: ``#define MMDEER_X <integer>``, ``typedef struct [tag] { fields } name;`` and ``type mmdeer_x(params);``.
 Anything else raises a HeaderError that quotes the text: no declaration and no preprocessor line is skipped (the include guard,
@@ -12,14 +12,14 @@ from __future__ import annotations
 import ctypes as C
 import re
 
-from .build import BERT_BWD_HEADER_PATH, BERT_DROP_HEADER_PATH, BERT_HEADER_PATH, DROP_DEV_HEADER_PATH, FRAMES_BWD_HEADER_PATH, FRAMES_HEADER_PATH, GRAPH_HEADER_PATH, HEADER_PATH, OPTIM_HEADER_PATH, ROUTES_HEADER_PATH, VIDEO_HEADER_PATH
+from .build import BERT_BWD_HEADER_PATH, BERT_DROP_HEADER_PATH, BERT_HEADER_PATH, DROP_DEV_HEADER_PATH, FRAMES_BWD_HEADER_PATH, FRAMES_HEADER_PATH, GRAPH_HEADER_PATH, HEADER_PATH, OPTIM_HEADER_PATH, ROUTES_HEADER_PATH, SEQLEN_HEADER_PATH, VIDEO_HEADER_PATH
 
 SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "float": C.c_float, "double": C.c_double, "uint64_t": C.c_uint64,
            "unsigned long long": C.c_uint64, "long long": C.c_longlong, "int64_t": C.c_int64, "size_t": C.c_size_t}
 POINTEES = {"void", "char", "unsigned char"}       # base types that occur behind a star only
 
 _DEFINE = re.compile(r"define\s+MMDEER_(\w+)\s+(\S.*)")
-_DIRECTIVE = re.compile(r"include\s*<\w+\.h>|ifndef\s+MMDEER_(VIDEO_|FRAMES_|FRAMES_BWD_|ROUTES_|BERT_|BERT_BWD_|BERT_DROP_|OPTIM_|GRAPH_|DROP_DEV_)?H_|define\s+MMDEER_(VIDEO_|FRAMES_|FRAMES_BWD_|ROUTES_|BERT_|BERT_BWD_|BERT_DROP_|OPTIM_|GRAPH_|DROP_DEV_)?H_|ifdef\s+__cplusplus|endif")    # carry no declaration
+_DIRECTIVE = re.compile(r"include\s*<\w+\.h>|ifndef\s+MMDEER_(VIDEO_|FRAMES_|FRAMES_BWD_|ROUTES_|BERT_|BERT_BWD_|BERT_DROP_|OPTIM_|GRAPH_|DROP_DEV_|SEQLEN_)?H_|define\s+MMDEER_(VIDEO_|FRAMES_|FRAMES_BWD_|ROUTES_|BERT_|BERT_BWD_|BERT_DROP_|OPTIM_|GRAPH_|DROP_DEV_|SEQLEN_)?H_|ifdef\s+__cplusplus|endif")    # carry no declaration
 _OPAQUE = re.compile(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;\s*")
 _STRUCT = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;\s*")
 _PROTO = re.compile(r"([\w\s*]+?)\b(mmdeer_\w+)\s*\(([^(){};]*)\)\s*;\s*")

@@ -106,6 +106,11 @@ globals().update({cls.__name__: cls for cls in _GRAPH_CLASSES.values()})    # Ad
 GRAPH_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _GRAPH_CLASSES.items()}
 # include/mmdeer_drop_dev.h, the companion header of the same counter for mmdeer.h's three by-value dropout entries: symbols only
 DROP_DEV_CONSTANTS, _DROP_DEV_CLASSES, DROP_DEV_SYMBOLS = _header.parse(_header.read(_header.DROP_DEV_HEADER_PATH), {}, {})
+# include/mmdeer_seqlen.h, the companion header of the audio encoder's recurrence and pool with per-sample lengths: tables of its own again
+_SEQLEN_NAMES = {"mmdeer_lstm_seq_len_args": "LstmSeqLenArgs", "mmdeer_temporal_pool_len_args": "TemporalPoolLenArgs"}
+SEQLEN_CONSTANTS, _SEQLEN_CLASSES, SEQLEN_SYMBOLS = _header.parse(_header.read(_header.SEQLEN_HEADER_PATH), _SEQLEN_NAMES, {})
+globals().update({cls.__name__: cls for cls in _SEQLEN_CLASSES.values()})    # LstmSeqLenArgs, TemporalPoolLenArgs
+SEQLEN_STRUCTS = {c.removeprefix("mmdeer_"): cls for c, cls in _SEQLEN_CLASSES.items()}
 GemmArgs = _CLASSES["mmdeer_gemm_args"]     # already a global by the update above; named here for gemm_args() below and for linters
 
 
@@ -120,7 +125,7 @@ def gemm_args(**fields):
 def bind(lib: C.CDLL, require_all: bool = False) -> C.CDLL:
     """Set restype and argtypes of every symbol of include/mmdeer.h that ``lib`` exports (``require_all``: AttributeError for one
     it does not -- ABI drift between header and library)."""
-    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS + GRAPH_SYMBOLS + DROP_DEV_SYMBOLS:
+    for name, res, args in SYMBOLS + VIDEO_SYMBOLS + FRAME_SYMBOLS + ROUTE_SYMBOLS + FRAME_BWD_SYMBOLS + BERT_SYMBOLS + BERT_BWD_SYMBOLS + BERT_DROP_SYMBOLS + OPTIM_SYMBOLS + GRAPH_SYMBOLS + DROP_DEV_SYMBOLS + SEQLEN_SYMBOLS:
         if require_all or hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -154,7 +159,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         lib = bind(C.CDLL(path), require_all=True)
         if lib.mmdeer_abi_version() != ABI_VERSION:
             raise RuntimeError("libmmdeer_hip.so ABI version mismatch")
-        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS, **BERT_BWD_STRUCTS, **BERT_DROP_STRUCTS, **OPTIM_STRUCTS, **GRAPH_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
+        for cname, cls in {**STRUCTS, **VIDEO_STRUCTS, **FRAME_STRUCTS, **FRAME_BWD_STRUCTS, **BERT_STRUCTS, **BERT_BWD_STRUCTS, **BERT_DROP_STRUCTS, **OPTIM_STRUCTS, **GRAPH_STRUCTS, **SEQLEN_STRUCTS}.items():      # the ctypes mirrors against the library's own sizeof (a field added on one side only)
             if lib.mmdeer_sizeof(cname.encode()) != C.sizeof(cls):
                 raise RuntimeError(f"mmdeer: ctypes layout of mmdeer_{cname} ({C.sizeof(cls)} bytes) differs from the library's "
                                    f"({lib.mmdeer_sizeof(cname.encode())})")

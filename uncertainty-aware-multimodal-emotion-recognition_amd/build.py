@@ -27,6 +27,7 @@ BERT_DROP_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdee
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer_optim.h")   # companion: clip + AdamW over any list of tensors
 GRAPH_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer_graph.h")   # companion: device step counters for HIP-graph replays
 DROP_DEV_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer_drop_dev.h")   # companion: the same counter for the by-value dropout entries
+SEQLEN_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "mmdeer_seqlen.h")   # companion: the audio encoder's operators with per-sample lengths
 SOURCES = ["gemm_nt.hip", "gemm_nx.hip", "gemm_tt.hip", "gemm_glds.hip", "gemm_ln.hip", "chain.hip", "gemm_tt256.hip", "gemm_nt256.hip", "gemm.hip", "rowops.hip", "attention.hip", "tri_fused.hip", "nig.hip", "nig_tail.hip", "optim.hip", "optim_multi.hip", "side.hip", "evalstats.hip", "lstm_seq.hip", "conv_time.hip", "bn_time.hip", "conv2d.hip", "bn2d.hip", "conv2d_bwd.hip", "bn2d_bwd.hip", "token_pool.hip", "bert.hip", "bert_bwd.hip", "bert_drop.hip", "stackb.hip", "stackb_train.hip", "fusions.hip", "comm.hip", "options.hip", "stackc.hip", "api.hip"]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: leading scalar kernel arguments arrive in SGPRs at wave start (gemm_glds.hip)
@@ -43,7 +44,7 @@ def _hipcc() -> str:
 
 def _newest_dep_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hip"))]
-    deps += [HEADER_PATH, VIDEO_HEADER_PATH, FRAMES_HEADER_PATH, ROUTES_HEADER_PATH, FRAMES_BWD_HEADER_PATH, BERT_HEADER_PATH, BERT_BWD_HEADER_PATH, BERT_DROP_HEADER_PATH, OPTIM_HEADER_PATH, GRAPH_HEADER_PATH, DROP_DEV_HEADER_PATH]
+    deps += [HEADER_PATH, VIDEO_HEADER_PATH, FRAMES_HEADER_PATH, ROUTES_HEADER_PATH, FRAMES_BWD_HEADER_PATH, BERT_HEADER_PATH, BERT_BWD_HEADER_PATH, BERT_DROP_HEADER_PATH, OPTIM_HEADER_PATH, GRAPH_HEADER_PATH, DROP_DEV_HEADER_PATH, SEQLEN_HEADER_PATH]
     return max(os.path.getmtime(d) for d in deps)
 
 

@@ -17,6 +17,7 @@
 #include "../../include/mmdeer_optim.h"
 #include "../../include/mmdeer_graph.h"
 #include "../../include/mmdeer_drop_dev.h"
+#include "../../include/mmdeer_seqlen.h"
 #include "attention.h"
 #include "common.h"
 #include "gemm.h"
@@ -603,6 +604,7 @@ long long mmdeer_sizeof(const char* n) {
   SZ(bert_embed_drop_args) SZ(bert_attn_drop_args) SZ(bert_drop_add_ln_args) SZ(bert_attn_drop_bwd_args) SZ(bert_drop_add_ln_bwd_args)   // mmdeer_bert_drop.h
   SZ(adamw_multi_tensor) SZ(adamw_multi_class) SZ(adamw_multi_args)   // mmdeer_optim.h
   SZ(adamw_multi_class_dev) SZ(adamw_multi_dev_args)   // mmdeer_graph.h
+  SZ(lstm_seq_len_args) SZ(temporal_pool_len_args)   // mmdeer_seqlen.h
 #undef SZ
   return -1;
 }

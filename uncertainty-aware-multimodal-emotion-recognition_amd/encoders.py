@@ -30,7 +30,8 @@ class ModalityEncoder(nn.Module):
     ``text_encoder.bert.*`` named as ``transformers.BertModel`` names them, and no embedding tables).
 
     ``forward(dict) -> dict`` encodes the modalities that are present: ``audio`` -> ``audio``, ``video`` -> ``video``,
-    ``text_input_ids`` and ``text_attention_mask`` (both) -> ``text``; an absent modality gives an absent key.
+    ``text_input_ids`` and ``text_attention_mask`` (both) -> ``text``; an absent modality gives an absent key.  The optional key
+    ``audio_lengths`` ((B,) valid steps of a padded ``audio`` batch) goes to ``TemporalAudioEncoder.forward(audio, lengths=...)``.
 
     One deviation from the reference: it catches ANY exception of an encoder, logs a warning and substitutes zeros.  Here a refusal
     (``ValueError``, ``NotImplementedError``, a CPU tensor) propagates: a batch the kernels do not take is an error, not a silent
@@ -46,8 +47,10 @@ class ModalityEncoder(nn.Module):
         self.video_encoder = FrameVideoEncoder(config, compute_dtype)
         self.text_encoder = TemporalTextEncoder(config, compute_dtype, bert=bert)
 
-    def encode_audio(self, audio_input: torch.Tensor) -> torch.Tensor:
-        return self.audio_encoder(audio_input)
+    def encode_audio(self, audio_input: torch.Tensor, lengths=None) -> torch.Tensor:
+        if lengths is None:
+            return self.audio_encoder(audio_input)
+        return self.audio_encoder(audio_input, lengths=lengths)
 
     def encode_video(self, video_input: torch.Tensor) -> torch.Tensor:
         return self.video_encoder(video_input)
@@ -57,7 +60,9 @@ class ModalityEncoder(nn.Module):
 
     def forward(self, multimodal_input: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         encoded: Dict[str, torch.Tensor] = {}
-        if "audio" in multimodal_input:
+        if "audio" in multimodal_input and multimodal_input.get("audio_lengths") is not None:
+            encoded["audio"] = self.encode_audio(multimodal_input["audio"], lengths=multimodal_input["audio_lengths"])
+        elif "audio" in multimodal_input:
             encoded["audio"] = self.encode_audio(multimodal_input["audio"])
         if "video" in multimodal_input:
             encoded["video"] = self.encode_video(multimodal_input["video"])
